@@ -18,8 +18,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
                        its launch stream inside the timed region: executed bf16-MFMA FLOP against the dense bf16 MFMA peak;
     roofline_forward - the whole CNN forward: executed MFMA FLOP per step / CNN time against the same peak, and the
                        algorithmic HBM bytes per step / CNN time against the HBM peak;
-    cpu_baseline     - the CPU oracle (restated reference path: OpenMP C solver + PyTorch-CPU network) on a bounded
-                       sample, rank 0 at N=1 only.
+    cpu_baseline     - with --full: the CPU oracle (restated reference path: OpenMP C solver + PyTorch-CPU network) on a
+                       bounded sample, rank 0 at N=1 only (null otherwise).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  --full adds, after the timed
+region, the CPU baseline and the secondary configurations (secondary_configs: training step vs eager, latency legs, the
+3-encoder network, the fp32-MFMA and six-pass bf16 forms, GEMM error figures) in config.  --dump-outputs DIR writes what the
+last timed step returned (poses, predictions) as .npy files, for output-for-output comparison of two builds.
 """
 import argparse
 import ctypes
@@ -199,6 +203,22 @@ def plan_work(plan, networks):
     return {"bf16_flop": bf16, "f32_flop": f32, "bytes": byts, "fp32_equivalent_flop": eq, "redundant_flop": redundant}
 
 
+DUMP_LIMIT = 64 << 20               # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, poses, pred):
+    """--dump-outputs: the last timed step's poses [B,4,4] and network predictions [B,C,H,W] as float32 .npy files.  Above
+    DUMP_LIMIT both keep the same frames, a sample drawn with a fixed seed, so two builds still compare frame for frame."""
+    poses, pred = poses.float().cpu().numpy(), pred.float().cpu().numpy()
+    per_frame = poses[0].nbytes + pred[0].nbytes
+    if len(pred) * per_frame > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(len(pred), DUMP_LIMIT // per_frame, replace=False))
+        poses, pred = poses[keep], pred[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "poses.npy"), poses)
+    np.save(os.path.join(out_dir, "predictions.npy"), pred)
+
+
 def respawn_under_torchrun(n, argv):
     """`python bench.py --gpus N` started without a launcher (WORLD_SIZE unset): re-execute the same command line under
     torch.distributed.run with N ranks on this node - what the driver's own launch line does.  Returns the exit status."""
@@ -318,7 +338,14 @@ def main():
                          "tiles (15.7 rounds) for a 1x1 layer; 47 frames (the default until round 4: 14.0 / 7.75 rounds) measures "
                          "1.8-2 %% lower (profiles/r4_bench_b47.json).  Default 95, also with --mlr 3 (47 there: -2.6 %%; 24 until round 4: -9 %%)")
     ap.add_argument("--hyps", type=int, default=256)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the CPU baseline and the secondary configurations (N=1 only); a plain "
+                         "run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned on rank 0 as float32 .npy files: DIR/poses.npy [B,4,4] and "
+                         "DIR/predictions.npy [B,C,60,90] (beyond %d MB in all: the same seeded sample of frames in both)"
+                         % (DUMP_LIMIT >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cnn-streams", type=int, default=1,
                     help="2: a step's CNN forward runs as two sub-batches on two HIP streams (the GEMMs of one overlap the "
                          "HBM-bound passes of the other: +9 %% images/s).  Not the default: kernel durations measured "
@@ -327,8 +354,8 @@ def main():
                     help="3: BASELINE configs[4], the 3-encoder CrossLoc network (755.96 GFLOP per frame) instead of "
                          "the single-task one the headline metric is quoted on")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary configurations (BASELINE configs[1] batch-16 training step vs PyTorch-ROCm "
-                         "eager, configs[4] 3-encoder network) that N=1 runs report outside the timed region")
+                    help="with --full: skip the secondary configurations (BASELINE configs[1] batch-16 training step vs "
+                         "PyTorch-ROCm eager, configs[4] 3-encoder network) that N=1 runs report outside the timed region")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 95
@@ -406,11 +433,13 @@ def main():
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True),
            torch.cuda.Event(enable_timing=True)) for _ in range(K)]
     all_poses = []
+    last = {}
 
     def run_steps():
         for s in range(K):
             ev[s][0].record(pipe.cnn[0])
             pred, done = pipe.forward_cnn(images, plant=coords)
+            last["pred"] = pred
             ev[s][1].record(pipe.cnn[0])                                 # stream 0 joins the others before the concat
             poses = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
             for e in done:
@@ -482,12 +511,14 @@ def main():
     assert n_rows == total_imgs
     if os.environ.get("XL_BENCH_DUMP_POSES"):          # per-rank poses of every image of every step, in step order (tests)
         np.save("%s.rank%d.npy" % (os.environ["XL_BENCH_DUMP_POSES"], rank), est.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, all_poses[-1], last["pred"])
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(net, images, coords_np, NH, args.mlr)
     secondary = {}
-    if rank == 0 and world == 1 and not args.no_secondary and not args.mlr:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and not args.mlr:
         del pipe, plan
         net.invalidate()
         torch.cuda.empty_cache()

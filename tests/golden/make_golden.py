@@ -176,6 +176,8 @@ def loss_goldens():
     out["coord_tight_dpred"] = p.grad.numpy().copy(); out["coord_tight_dunc"] = u.grad.numpy().copy()
     out.update(coord_pred=pred, coord_unc=unc, coord_gt=gt_lab, coord_poses=poses,
                coord_focal=np.array(60.0), coord_hw=np.array([H * 8, W * 8]))
+    # the pose inverse as this host's MKL rounds it (tests/test_loss_oracle.py pins the oracle to it on other hosts)
+    out["coord_poses_inv"] = torch.linalg.inv(torch.tensor(poses)).numpy()
 
     # depth
     gt_d = rng.uniform(100, 300, size=(B, 1, H, W)).astype(np.float32)

@@ -134,3 +134,36 @@ def test_a_pose_does_not_move_under_the_forward_distance_from_float64():
     print("pose movement under a +-4e-5 m coordinate perturbation, 64 frames: max %.3e m, %.3e deg; median %.3e m, %.3e deg"
           % (moved[:, 0].max(), moved[:, 1].max(), np.median(moved[:, 0]), np.median(moved[:, 1])))
     assert moved[:, 0].max() < 1e-3 and moved[:, 1].max() < 1e-3
+
+
+def test_a_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 poses and predictions of the LAST timed step - the solver keyed by the global image
+    indices of step K - 1, the planted coordinates, the network's own uncertainty channel.  A plain run (no --full) carries no CPU
+    baseline and no secondary legs."""
+    import json
+    import subprocess
+    import dsacstar
+    nb, K = 4, 2
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1", "--steps", str(K),
+                        "--warmup", "1", "--batch", str(nb), "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == K and line["ms_per_step"] > 0
+    assert line["cpu_baseline"] is None and not any(k.startswith(("train16", "latency_b1", "mlr3")) for k in line["config"])
+    poses = np.load(str(tmp_path / "out" / "poses.npy"))
+    pred = np.load(str(tmp_path / "out" / "predictions.npy"))
+    assert poses.dtype == np.float32 and poses.shape == (nb, 4, 4)
+    assert pred.dtype == np.float32 and pred.shape == (nb, 4, H // 8, W // 8)
+    coords_np = synth.make_batch(2021, nb, noise=0.5, outlier_ratio=0.3)[0]
+    assert np.array_equal(pred[:, :3], coords_np)
+    want = torch.zeros((nb, 4, 4), dtype=torch.float32, device="cuda")
+    dsacstar.forward_rgb_batch(torch.from_numpy(coords_np).cuda(), want, NH, 10.0, synth.FOCAL, W / 2.0, H / 2.0, 100.0, 100.0, 8,
+                               image0=(K - 1) * nb)
+    torch.cuda.synchronize()
+    assert np.array_equal(poses, want.cpu().numpy())
+    net, _ = _bench_network()
+    images = torch.rand((nb, 3, H, W), generator=torch.Generator(device="cpu").manual_seed(2021)).cuda()
+    with torch.no_grad():
+        sigma = net(images)[:, 3].cpu().numpy()
+    np.testing.assert_allclose(pred[:, 3], sigma, rtol=1e-5)

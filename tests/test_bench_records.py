@@ -29,3 +29,24 @@ def test_traffic_record_belongs_to_the_kernel_sources_at_head():
     assert sv is not None and sv["sample_and_score_valu_busy"] is not None and sv["sample_and_score_fp64_share_of_valu"] is not None
     roof = bench.solver_valu_roofline(95, 256, 5400, 3.9)
     assert 0.0 < roof["frac"] < 1.0 and roof["valu_busy_sample_and_score"] == sv["sample_and_score_valu_busy"]
+
+
+def test_dump_outputs_writes_float32_and_samples_the_same_frames_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: poses and predictions as float32 .npy; above DUMP_LIMIT both keep the same seeded frames."""
+    import numpy as np
+    import torch
+    import bench
+    poses = torch.arange(10 * 16, dtype=torch.float32).reshape(10, 4, 4)
+    pred = torch.arange(10 * 4 * 6 * 9, dtype=torch.float64).reshape(10, 4, 6, 9)
+    bench.dump_outputs(str(tmp_path / "all"), poses, pred)
+    p, q = np.load(str(tmp_path / "all" / "poses.npy")), np.load(str(tmp_path / "all" / "predictions.npy"))
+    assert p.dtype == q.dtype == np.float32 and np.array_equal(p, poses.numpy()) and np.array_equal(q, pred.float().numpy())
+    per_frame = 16 * 4 + 4 * 6 * 9 * 4
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * per_frame + 7)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), poses, pred)
+    p, q = np.load(str(tmp_path / "a" / "poses.npy")), np.load(str(tmp_path / "a" / "predictions.npy"))
+    assert p.shape == (3, 4, 4) and q.shape == (3, 4, 6, 9) and p.nbytes + q.nbytes <= bench.DUMP_LIMIT
+    keep = (p[:, 0, 0] / 16).astype(int)
+    assert np.array_equal(q, pred.float().numpy()[keep]) and np.all(np.diff(keep) > 0)
+    assert np.array_equal(p, np.load(str(tmp_path / "b" / "poses.npy")))

@@ -14,7 +14,7 @@ FRAMES=$(grep -o '"batch_per_gpu": [0-9]*' $OUT/pmc.log | head -1 | grep -o '[0-
 python tools/traffic_record.py $OUT/pmc_derived.csv $FRAMES "profiles/r2_pmc_summary.csv (rocprofv3 -i tools/pmc_r2.txt over bench.py --steps 2)" > /dev/null
 cp profiles/traffic.json $OUT/traffic.json
 rm -rf $OUT/pmc                                                    # keep the merged summary only (size)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
 XL_GEMM_SPLIT_BF16=0 python bench.py --no-secondary --no-cpu-baseline > $OUT/bench_fp32_mfma.json 2>/dev/null
 cd /tmp

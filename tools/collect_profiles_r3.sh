@@ -24,7 +24,7 @@ for nb in 24 44; do                                                  # HBM-side 
   rm -rf $OUT/pmc$nb
 done
 cp profiles/traffic.json $OUT/traffic.json
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 900 $OUT/bench.json
 python bench.py --no-secondary --no-cpu-baseline --batch 24 > $OUT/bench_b24.json 2>/dev/null
 python bench.py --no-secondary --no-cpu-baseline --batch 44 > $OUT/bench_b44.json 2>/dev/null

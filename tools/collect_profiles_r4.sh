@@ -24,7 +24,7 @@ for nb in 47 24; do                                                  # HBM-side 
   rm -rf $OUT/pmc$nb
 done
 cp profiles/traffic.json $OUT/traffic.json
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
 python -c "
 import json

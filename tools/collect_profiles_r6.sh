@@ -25,7 +25,7 @@ python tools/pmc_derive.py "$OUT/pmc_summary_b47.csv" "$OUT/pmc_derived_b47.csv"
 python tools/traffic_record.py "$OUT/pmc_derived_b47.csv" 47 "rocprofv3 -i tools/pmc_hbm2.txt over bench.py --batch 47 --steps 2 (profiles/r6_pmc_derived_b47.csv)" > /dev/null
 rm -rf "$OUT/pmc47"
 cp profiles/traffic.json "$OUT/traffic.json"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
 python -c "
 import json

@@ -7,7 +7,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $GRAFT_R
 cd $GRAFT_REPO_ROOT
 cp $(ls $O/kt/*/*kernel_stats.csv | head -1) $O/kstats.csv; rm -rf $O/kt
 python tools/kstats_show.py $O/kstats.csv | head -22
-python bench.py --no-cpu-baseline > $O/bench_full.json 2> $O/bench_full.err
+python bench.py --full --no-cpu-baseline > $O/bench_full.json 2> $O/bench_full.err
 python - <<PY
 import json
 try:

@@ -1,5 +1,5 @@
 #!/bin/bash
-# the complete -m gpu suite, smoke(), then the default bench line (all legs)
+# the complete -m gpu suite, smoke(), then the full bench line (--full: all legs)
 set -u
 : "${GRAFT_REPO_ROOT:?}"
 cd "$GRAFT_REPO_ROOT"
@@ -7,7 +7,7 @@ O="$GRAFT_REPO_ROOT/gpurun_out/r6_full"; mkdir -p "$O"
 ( time timeout 3000 python -m pytest tests/ -m gpu -x -q 2>&1 | tail -25 ) > "$O/tests.txt" 2>&1
 cat "$O/tests.txt"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-( time timeout 1500 python bench.py > "$O/bench.json" 2> "$O/bench.err" ) 2>&1 | tail -3
+( time timeout 1500 python bench.py --full > "$O/bench.json" 2> "$O/bench.err" ) 2>&1 | tail -3
 tail -3 "$O/bench.err"
 python - <<PY
 import json
