@@ -1409,7 +1409,21 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
             const int blocks = rb * op.B;
             size_t lds = sizeof(float) * (size_t)4 * (op.Wi + 2) * 4;
             if (lds < sizeof(float) * (size_t)4 * op.Cout * 28) lds = sizeof(float) * (size_t)4 * op.Cout * 28;
-            if (lds > 64 * 1024) return XL_ERR_UNSUPPORTED;
+            // the staged rows take 64 * (Wi + 2) bytes: up to the 160 KiB of a CU (frames up to 2558 pixels wide; the training
+            // augmentation's largest scale, 3/2 of a 720-wide frame, needs 68 KiB)
+            if (lds > 160 * 1024) return XL_ERR_UNSUPPORTED;
+            if (lds > 64 * 1024) {
+                static XlLdsLimit configured[2];     // per instantiation, tracked per device
+                const int fi = op.aux2 ? 1 : 0;
+                int cfgDev;
+                if (configured[fi].needs(lds, &cfgDev)) {
+                    const void *fn = op.aux2 ? reinterpret_cast<const void *>(conv1_wgrad_kernel<true>)
+                                             : reinterpret_cast<const void *>(conv1_wgrad_kernel<false>);
+                    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+                        return XL_ERR_HIP;
+                    configured[fi].done(lds, cfgDev);
+                }
+            }
             if (op.aux2) {
                 // GroupNorm-backward apply on load: aux2 = conv1's raw output (ld_in), w = the layer's forward table (XL_OP_GN_FINAL
                 // with out2), bias = the coefficients [B][Cout][3] of XL_OP_GNB_FINAL, flags = the GroupNorm's XL_GN_RELU_IN

@@ -73,6 +73,7 @@ struct CoordArgs {
     double *partials;
     int B, Ho, Wo, N, nblk, mode;
     float f, cx, cy, sub, minDepth, soft, hard, tol, nodata, gscale;
+    long long ps, us;                 // per-image strides (elements) of pred / dpred and of unc / dunc
 };
 
 __global__ __launch_bounds__(kT)
@@ -86,8 +87,8 @@ void coord_loss_kernel(CoordArgs a)
     const int i = blockIdx.x * kT + threadIdx.x;
     Sums s{ 0.0, 0.0, 0.0, 0.0 };
     if (i < a.N) {
-        const long long base = (long long)b * 3 * a.N + i;
-        const float X = a.pred[base], Y = a.pred[base + a.N], Z = a.pred[base + 2 * a.N];
+        const long long base = (long long)b * 3 * a.N + i, pbase = (long long)b * a.ps + i;
+        const float X = a.pred[pbase], Y = a.pred[pbase + a.N], Z = a.pred[pbase + 2 * a.N];
         const float gx = a.gt[base], gy = a.gt[base + a.N], gz = a.gt[base + 2 * a.N];
         const bool g = (gx != a.nodata) && (gy != a.nodata) && (gz != a.nodata);             // learning.py:63
         // coords_world_to_cam (coord.py:20-38)
@@ -124,7 +125,7 @@ void coord_loss_kernel(CoordArgs a)
         // 3-D / uncertainty term (coord.py:152-167)
         float lu = 0.f, dLdd = 0.f, dLds = 0.f;
         if (a.mode == 1) {
-            const float sraw = a.unc[(long long)b * a.N + i];
+            const float sraw = a.unc[(long long)b * a.us + i];
             const float sg = fmaxf(sraw, 1e-7f);
             const float d2 = d * d, d2c = fmaxf(d2, 1e-7f);
             const float s2 = sg * sg, s2c = fmaxf(s2, 1e-7f);
@@ -136,10 +137,10 @@ void coord_loss_kernel(CoordArgs a)
                     if (s2 >= 1e-7f) dLds -= d2c / (s2c * sg);
                 }
             }
-            if (a.dunc) a.dunc[(long long)b * a.N + i] = dLds * a.gscale;
+            if (a.dunc) a.dunc[(long long)b * a.us + i] = dLds * a.gscale;
         } else {
             if (g) { lu = d; dLdd = 1.f; }
-            if (a.dunc) a.dunc[(long long)b * a.N + i] = 0.f;
+            if (a.dunc) a.dunc[(long long)b * a.us + i] = 0.f;
         }
         if (a.dpred) {
             // d e / d (u,v), then through the projection, K and the rigid transform
@@ -150,9 +151,9 @@ void coord_loss_kernel(CoordArgs a)
             if (pz >= a.minDepth) gpz = -(gu * px + gv * py) / (zt * zt);
             float gxc = a.f * gpx, gyc = a.f * gpy, gzc = a.cx * gpx + a.cy * gpy + gpz;
             if (d > 0.f) { const float k = dLdd / d; gxc += k * dx; gyc += k * dy; gzc += k * dz; }
-            a.dpred[base] = (sP[0] * gxc + sP[4] * gyc + sP[8] * gzc) * a.gscale;
-            a.dpred[base + a.N] = (sP[1] * gxc + sP[5] * gyc + sP[9] * gzc) * a.gscale;
-            a.dpred[base + 2 * a.N] = (sP[2] * gxc + sP[6] * gyc + sP[10] * gzc) * a.gscale;
+            a.dpred[pbase] = (sP[0] * gxc + sP[4] * gyc + sP[8] * gzc) * a.gscale;
+            a.dpred[pbase + a.N] = (sP[1] * gxc + sP[5] * gyc + sP[9] * gzc) * a.gscale;
+            a.dpred[pbase + 2 * a.N] = (sP[2] * gxc + sP[6] * gyc + sP[10] * gzc) * a.gscale;
         }
         s.a = (double)lu; s.b = (double)lr; s.c = m ? 1.0 : 0.0; s.d = g ? 1.0 : 0.0;
     }
@@ -171,6 +172,7 @@ struct DepthArgs {
     double *partials;
     int B, N, nblk, mode;
     float minDepth, hard, nodata, gscale;
+    long long ps, us;                 // per-image strides (elements) of pred / dpred and of unc / dunc
 };
 
 __global__ __launch_bounds__(kT)
@@ -181,8 +183,8 @@ void depth_loss_kernel(DepthArgs a)
     const int i = blockIdx.x * kT + threadIdx.x;
     Sums s{ 0.0, 0.0, 0.0, 0.0 };
     if (i < a.N) {
-        const long long idx = (long long)b * a.N + i;
-        const float D = a.pred[idx], Dg = a.gt[idx];
+        const long long idx = (long long)b * a.N + i, pidx = (long long)b * a.ps + i, uidx = (long long)b * a.us + i;
+        const float D = a.pred[pidx], Dg = a.gt[idx];
         const bool g = Dg != a.nodata;
         const float diff = D - Dg;
         const float err = fabsf(diff);                                                          // depth.py:27
@@ -190,7 +192,7 @@ void depth_loss_kernel(DepthArgs a)
         const float sgn = (diff > 0.f) ? 1.f : ((diff < 0.f) ? -1.f : 0.f);
         float l = 0.f, dD = 0.f, dS = 0.f;
         if (a.mode == 1) {
-            const float sraw = a.unc[idx];
+            const float sraw = a.unc[uidx];
             const float sg = fmaxf(sraw, 1e-7f);
             const float e2 = err * err, e2c = fmaxf(e2, 1e-7f);
             const float s2 = sg * sg, s2c = fmaxf(s2, 1e-7f);
@@ -203,8 +205,8 @@ void depth_loss_kernel(DepthArgs a)
                 }
             }
         } else if (g) { l = err; dD = sgn; }
-        if (a.dpred) a.dpred[idx] = dD * a.gscale;
-        if (a.dunc) a.dunc[idx] = dS * a.gscale;
+        if (a.dpred) a.dpred[pidx] = dD * a.gscale;
+        if (a.dunc) a.dunc[uidx] = dS * a.gscale;
         s.a = (double)l; s.c = valid ? 1.0 : 0.0; s.d = g ? 1.0 : 0.0;
     }
     const Sums r = block_reduce4(s, sRed);
@@ -222,6 +224,7 @@ struct NormalArgs {
     double *partials;
     int B, N, nblk, mode;
     float hard, nodata, gscale;
+    long long ps, us;                 // per-image strides (elements) of logits / dlogits and of unc / dunc
 };
 
 __device__ __forceinline__ float logit_to_rad(float l, float &dadl)
@@ -243,7 +246,7 @@ void normal_loss_kernel(NormalArgs a)
     const int i = blockIdx.x * kT + threadIdx.x;
     Sums s{ 0.0, 0.0, 0.0, 0.0 };
     if (i < a.N) {
-        const long long b2 = (long long)b * 2 * a.N + i, b3 = (long long)b * 3 * a.N + i, b1 = (long long)b * a.N + i;
+        const long long b2 = (long long)b * a.ps + i, b3 = (long long)b * 3 * a.N + i, b1 = (long long)b * a.us + i;
         float daz, del;
         const float az = logit_to_rad(a.logits[b2], daz);
         const float el = logit_to_rad(a.logits[b2 + a.N], del);
@@ -424,6 +427,16 @@ int xl_loss_coord(const float *pred, const float *unc, const float *gt_poses, co
                   float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
                   int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream)
 {
+    return xl_loss_coord_ld(pred, unc, gt_poses, gt_coords, B, Ho, Wo, 3, 1, focal, cx, cy, subsample, min_depth, soft_clamp,
+                            hard_clamp, init_tolerance, nodata, mode, per_image_scale, dpred, dunc, workspace, out, stream);
+}
+
+int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                     int B, int Ho, int Wo, int ld_pred, int ld_unc, float focal, float cx, float cy, float subsample,
+                     float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
+                     int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream)
+{
+    if (ld_pred < 3 || ld_unc < 1) return XL_ERR_ARG;
     if (!pred || !gt_poses || !gt_coords || !workspace || !out || B <= 0 || Ho <= 0 || Wo <= 0) return XL_ERR_ARG;
     if (mode == 1 && !unc) return XL_ERR_ARG;
     CoordArgs a;
@@ -431,6 +444,7 @@ int xl_loss_coord(const float *pred, const float *unc, const float *gt_poses, co
     a.partials = workspace; a.B = B; a.Ho = Ho; a.Wo = Wo; a.N = Ho * Wo; a.nblk = (a.N + kT - 1) / kT; a.mode = mode;
     a.f = focal; a.cx = cx; a.cy = cy; a.sub = subsample; a.minDepth = min_depth; a.soft = soft_clamp;
     a.hard = hard_clamp; a.tol = init_tolerance; a.nodata = nodata;
+    a.ps = (long long)ld_pred * a.N; a.us = (long long)ld_unc * a.N;
     a.gscale = per_image_scale ? 1.0f / (float)a.N : 1.0f / ((float)B * (float)a.N);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(coord_loss_kernel, dim3(a.nblk, B), dim3(kT), 0, st, a);
@@ -442,12 +456,22 @@ int xl_loss_depth(const float *pred, const float *unc, const float *gt_depth, in
                   float min_depth, float hard_clamp, float nodata, int mode, int per_image_scale,
                   float *dpred, float *dunc, double *workspace, float *out, void *stream)
 {
+    return xl_loss_depth_ld(pred, unc, gt_depth, B, Ho, Wo, 1, 1, min_depth, hard_clamp, nodata, mode, per_image_scale, dpred,
+                            dunc, workspace, out, stream);
+}
+
+int xl_loss_depth_ld(const float *pred, const float *unc, const float *gt_depth, int B, int Ho, int Wo, int ld_pred, int ld_unc,
+                     float min_depth, float hard_clamp, float nodata, int mode, int per_image_scale,
+                     float *dpred, float *dunc, double *workspace, float *out, void *stream)
+{
+    if (ld_pred < 1 || ld_unc < 1) return XL_ERR_ARG;
     if (!pred || !gt_depth || !workspace || !out || B <= 0 || Ho <= 0 || Wo <= 0) return XL_ERR_ARG;
     if (mode == 1 && !unc) return XL_ERR_ARG;
     DepthArgs a;
     a.pred = pred; a.unc = unc; a.gt = gt_depth; a.dpred = dpred; a.dunc = dunc; a.partials = workspace;
     a.B = B; a.N = Ho * Wo; a.nblk = (a.N + kT - 1) / kT; a.mode = mode;
     a.minDepth = min_depth; a.hard = hard_clamp; a.nodata = nodata;
+    a.ps = (long long)ld_pred * a.N; a.us = (long long)ld_unc * a.N;
     a.gscale = per_image_scale ? 1.0f / (float)a.N : 1.0f / ((float)B * (float)a.N);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(depth_loss_kernel, dim3(a.nblk, B), dim3(kT), 0, st, a);
@@ -459,11 +483,21 @@ int xl_loss_normal(const float *logits, const float *unc, const float *gt_normal
                    float hard_clamp, float nodata, int mode, int per_image_scale,
                    float *dlogits, float *dunc, double *workspace, float *out, void *stream)
 {
+    return xl_loss_normal_ld(logits, unc, gt_normals, B, Ho, Wo, 2, 1, hard_clamp, nodata, mode, per_image_scale, dlogits, dunc,
+                             workspace, out, stream);
+}
+
+int xl_loss_normal_ld(const float *logits, const float *unc, const float *gt_normals, int B, int Ho, int Wo, int ld_pred,
+                      int ld_unc, float hard_clamp, float nodata, int mode, int per_image_scale,
+                      float *dlogits, float *dunc, double *workspace, float *out, void *stream)
+{
+    if (ld_pred < 2 || ld_unc < 1) return XL_ERR_ARG;
     if (!logits || !gt_normals || !workspace || !out || B <= 0 || Ho <= 0 || Wo <= 0) return XL_ERR_ARG;
     if (mode == 1 && !unc) return XL_ERR_ARG;
     NormalArgs a;
     a.logits = logits; a.unc = unc; a.gt = gt_normals; a.dlogits = dlogits; a.dunc = dunc; a.partials = workspace;
     a.B = B; a.N = Ho * Wo; a.nblk = (a.N + kT - 1) / kT; a.mode = mode; a.hard = hard_clamp; a.nodata = nodata;
+    a.ps = (long long)ld_pred * a.N; a.us = (long long)ld_unc * a.N;
     a.gscale = per_image_scale ? 1.0f / (float)a.N : 1.0f / ((float)B * (float)a.N);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(normal_loss_kernel, dim3(a.nblk, B), dim3(kT), 0, st, a);

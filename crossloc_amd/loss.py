@@ -234,3 +234,74 @@ def semantics_classification_loss(uncertainty, semantic_logits, uncertainty_map,
 
     loss, out = _FusedLoss.apply(launch, per_image, semantic_logits, None)
     return loss, out[1]
+
+
+def _bind_ld():
+    L = _bind()
+    if not hasattr(L, "_loss_ld_bound"):
+        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        L.xl_loss_coord_ld.restype = ci
+        L.xl_loss_coord_ld.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, cf, cf, cf, cf, cf, ci, ci,
+                                       vp, vp, vp, vp, vp]
+        L.xl_loss_depth_ld.restype = ci
+        L.xl_loss_depth_ld.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, ci, vp, vp, vp, vp, vp]
+        L.xl_loss_normal_ld.restype = ci
+        L.xl_loss_normal_ld.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, ci, ci, vp, vp, vp, vp, vp]
+        L._loss_ld_bound = True
+    return L
+
+
+def task_loss_and_output_gradient(task, uncertainty, prediction, num_task_channel, gt_labels, gt_poses=None,
+                                  pixel_grid=None, cam_mat=None, nodata_value=-1, min_depth=0.1, soft_clamp=100.0,
+                                  hard_clamp=1000.0, init_tolerance=50.0):
+    """The four losses of train_single_task.py:274-296 (reduction 'mean') in the form the training step uses: the kernels
+    read the network output `prediction` [B, num_task_channel (+1 uncertainty channel), H, W] in place - no torch.split
+    copies - and write d loss / d prediction into ONE tensor of its shape, ready for prediction.backward(grad) - no
+    autograd node of the loss, hence no gradient scaling or concatenation kernels.  Returns (loss, valid_rate, grad);
+    loss and valid_rate are 0-dim device tensors.  Same values and gradients as the functions above."""
+    mode = _mode(uncertainty)
+    p = prediction.detach()
+    if not p.is_cuda:
+        raise RuntimeError("crossloc_amd.loss runs on the GPU only (no CPU fallback)")
+    if p.dtype != torch.float32 or not p.is_contiguous():
+        raise RuntimeError("task_loss_and_output_gradient reads the network output in place: contiguous float32 expected")
+    B, C, Ho, Wo = p.shape
+    if C != num_task_channel + mode:
+        raise RuntimeError("expected %d channels (%d task + %d uncertainty), got %d" % (num_task_channel + mode,
+                                                                                        num_task_channel, mode, C))
+    if task == 'semantics' and mode:
+        raise NotImplementedError                              # semantics.py:78-81
+    dev, N = p.device, Ho * Wo
+    grad = torch.empty_like(p)                                 # every element is written by the kernel
+    L = _bind_ld()
+    ws = torch.empty(L.xl_loss_workspace_doubles(B, Ho, Wo), dtype=torch.float64, device=dev)
+    out = torch.empty(2 + B, dtype=torch.float32, device=dev)
+    unc = ctypes.c_void_p(p.data_ptr() + 4 * num_task_channel * N) if mode else None
+    dunc = ctypes.c_void_p(grad.data_ptr() + 4 * num_task_channel * N) if mode else None
+    pp, gp, wp, op = _ptr(p), _ptr(grad), _ptr(ws), _ptr(out)
+    with torch.cuda.device(dev):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if task == 'coord':
+            cm = cam_mat.detach().cpu()
+            pg = pixel_grid[:, 0, :2].detach().cpu()
+            poses = _prep(gt_poses).reshape(-1, 16)
+            gt = _prep(gt_labels)
+            rc = L.xl_loss_coord_ld(pp, unc, _ptr(poses), _ptr(gt), B, Ho, Wo, C, C, float(cm[0, 0]), float(cm[0, 2]),
+                                    float(cm[1, 2]), float(pg[0, 1] - pg[0, 0]), float(min_depth), float(soft_clamp),
+                                    float(hard_clamp), float(init_tolerance), float(nodata_value), mode, 0, gp, dunc, wp, op,
+                                    stream)
+        elif task == 'depth':
+            gt = _prep(gt_labels)
+            rc = L.xl_loss_depth_ld(pp, unc, _ptr(gt), B, Ho, Wo, C, C, float(min_depth), float(hard_clamp),
+                                    float(nodata_value), mode, 0, gp, dunc, wp, op, stream)
+        elif task == 'normal':
+            gt = _prep(gt_labels)
+            rc = L.xl_loss_normal_ld(pp, unc, _ptr(gt), B, Ho, Wo, C, C, float(hard_clamp), float(nodata_value), mode, 0,
+                                     gp, dunc, wp, op, stream)
+        elif task == 'semantics':
+            lab = gt_labels.detach().to(device=dev, dtype=torch.float32).reshape(B, Ho, Wo).contiguous()
+            rc = L.xl_loss_semantics(pp, _ptr(lab), B, C, Ho, Wo, 0, gp, wp, op, stream)
+        else:
+            raise NotImplementedError(task)
+    _lib.check(rc)
+    return out[0], out[1], grad

@@ -2347,6 +2347,26 @@ class _Plan:
         return [(p, buf[o:o + n]) for p, o, n in self.grad_slices]
 
 
+def gradient_buffer(net):
+    """The flat fp32 buffer that the `.grad` of every trainable parameter of `net` is a slice of after a backward pass
+    (run_backward hands the gradients out as views of one result buffer).  One in-place collective on it reduces every
+    gradient at once.  Raises when the gradients are not the ones the last backward produced (missing, accumulated into a
+    tensor of their own, or replaced).  The caller must not keep the buffer across steps: a live view pins it (_sole_owner)."""
+    params = [p for p in net._tensors()[0] if p.requires_grad]
+    if not params or params[0].grad is None:
+        raise RuntimeError("gradient_buffer: no gradients (call it between loss.backward() and optimizer.zero_grad())")
+    ptr = params[0].grad.untyped_storage().data_ptr()
+    for plan in net._plans.values():
+        for buf in getattr(plan, "grad_results", ()):
+            if buf is None or buf.data_ptr() != ptr:
+                continue
+            if len(plan.grad_slices) != len(params) or any(
+                    p.grad is None or p.grad.data_ptr() != ptr + 4 * o for p, o, _ in plan.grad_slices):
+                break
+            return buf
+    raise RuntimeError("gradient_buffer: the .grad tensors are not the slices of one backward result buffer")
+
+
 def _sole_owner(buf):
     """True when `buf` is the only tensor left on its storage (no view of it is alive anywhere): 2 = this tensor + the
     Python storage object the query itself creates.  Unknown (private API missing) counts as shared."""
@@ -2491,6 +2511,13 @@ class TransPoseNet(nn.Module):
         self._plans = {}
         self.__dict__.pop("_tensor_cache", None)
         return super()._apply(fn, *a, **k)
+
+    def drop_plans_except(self, B, H, W):
+        """Release the plans (activation buffers, packed operands) of every input shape but [B, *, H, W] - a training loop
+        whose augmentation changes the input size from batch to batch keeps one size's plans at a time.  Plans that hold
+        the activations of a graph not yet differentiated stay."""
+        for k in [k for k, p in self._plans.items() if tuple(k[:3]) != (B, H, W) and not getattr(p, "busy", False)]:
+            del self._plans[k]
 
     def load_state_dict(self, *a, **k):
         self._plans = {}

@@ -44,6 +44,23 @@ int xl_loss_normal(const float *logits, const float *unc, const float *gt_normal
                    float hard_clamp, float nodata, int mode, int per_image_scale,
                    float *dlogits, float *dunc, double *workspace, float *out, void *stream);
 
+/* The same three losses on buffers that hold more channels per image than the loss reads: pred / dpred advance by
+ * ld_pred*Ho*Wo floats per image, unc / dunc by ld_unc*Ho*Wo.  With unc = pred + n_task*Ho*Wo and ld_pred = ld_unc =
+ * n_task + 1, the kernels read the network's [B, n_task+1, Ho, Wo] output in place and write d loss / d output into one
+ * tensor of that shape (no split copies, no gradient concatenation).  The old entry points are ld_pred = n_task, ld_unc = 1. */
+int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                     int B, int Ho, int Wo, int ld_pred, int ld_unc, float focal, float cx, float cy, float subsample,
+                     float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
+                     int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream);
+
+int xl_loss_depth_ld(const float *pred, const float *unc, const float *gt_depth, int B, int Ho, int Wo, int ld_pred, int ld_unc,
+                     float min_depth, float hard_clamp, float nodata, int mode, int per_image_scale,
+                     float *dpred, float *dunc, double *workspace, float *out, void *stream);
+
+int xl_loss_normal_ld(const float *logits, const float *unc, const float *gt_normals, int B, int Ho, int Wo, int ld_pred,
+                      int ld_unc, float hard_clamp, float nodata, int mode, int per_image_scale,
+                      float *dlogits, float *dunc, double *workspace, float *out, void *stream);
+
 /* semantics_classification_loss with CrossEntropyLoss2d (loss/semantics.py:10-18, 44-91; no class weights, no
  * uncertainty): logits [B,C,H,W], labels [B,H,W] class ids stored as floats (what the loader yields); out[1] is the
  * share of pixels whose arg-max class equals the label; dlogits = (softmax - onehot) * scale. */
