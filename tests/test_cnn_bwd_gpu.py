@@ -26,23 +26,21 @@ pytestmark = pytest.mark.gpu
 MEAN = torch.tensor([-455.934, 417.50, 520.31])
 
 
-def _reference_grads(sd, x, wgt, enc_add, dec_add):
+def _reference_grads(sd, x, wgt, enc_add, dec_add, n_task=3, n_pos=1, in_ch=3):
     """Autograd in float64 on the CPU: the reference must not have ReLU-mask flips of its own (an fp32 CPU run
-    does, now and then, relative to fp64 — see the module docstring)."""
+    does, now and then, relative to fp64 — see the module docstring).  n_task / n_pos: the head's channels (coord 3 + 1, depth
+    1 + 1, normal 2 + 1, no uncertainty 3 + 0); in_ch: 3 (RGB) or 1 (grayscale)."""
+    assert x.shape[1] == in_ch == sd["encoder.conv1.weight"].shape[1] and wgt.shape[1] == n_task + n_pos
+    assert sd["decoder.fc3.weight"].shape[0] == n_task + n_pos
     sd = {k: (v.double().clone().requires_grad_(True) if v.dtype.is_floating_point and not k.endswith("mean")
               else (v.double() if v.dtype.is_floating_point else v)) for k, v in sd.items()}
     x, wgt = x.double(), wgt.double()
-
-    class _Id(dict):
-        pass
     leaves = {k: v for k, v in sd.items() if v.requires_grad}
-    # cnn_oracle detaches its inputs; re-implement the call with live tensors
-    orig = cnn_oracle.transposenet_forward
+    # cnn_oracle.transposenet_forward detaches its inputs; call its two halves with live tensors
     res = cnn_oracle.encoder_forward(sd, x, "encoder", enc_add, 32)
-    y = cnn_oracle.decoder_forward(sd, res, dec_add, 3, 1, 32)
+    y = cnn_oracle.decoder_forward(sd, res, dec_add, n_task, n_pos, 32)
     (y * wgt).sum().backward()
     return y.detach().float(), {k: v.grad.float() for k, v in leaves.items()}
-
 
 
 def _check_direct_form(worst, worst2):
@@ -67,24 +65,36 @@ def test_parameter_gradients_vs_autograd(B, H, W, enc_add, dec_add, tiny, form, 
     in the float64 reference: the max-norm criterion stays on the direct form, the Winograd form is held to a relative
     L2 error per tensor (a flipped mask moves a few elements; a wiring error moves the whole tensor).
     tiny (round 6): the 128-channel network of `--tiny` (networks.py:133-135, 194-198, 245-247)."""
+    _check_parameter_gradients(form, monkeypatch, B, H, W, enc_add, dec_add, tiny)
+
+
+def _out_size(n):
+    """Three stride-2 3x3 pad-1 convolutions: ceil division each time."""
+    for _ in range(3):
+        n = (n + 1) // 2
+    return n
+
+
+def _check_parameter_gradients(form, monkeypatch, B, H, W, enc_add, dec_add, tiny, n_task=3, n_pos=1, gray=False, mean=MEAN):
     if form == "direct":
         monkeypatch.setenv("XL_NO_WINOGRAD_TRAIN", "1")
-    net = networks.TransPoseNet(MEAN, tiny, False, enc_add, dec_add, 3, 1)
+    in_ch = 1 if gray else 3
+    net = networks.TransPoseNet(mean, tiny, gray, enc_add, dec_add, n_task, n_pos)
     net.load_state_dict(seeded_state_dict(net, seed=11))
     g = torch.Generator().manual_seed(B * 100 + H)
-    x = torch.rand(B, 3, H, W, generator=g)
-    Ho, Wo = H // 8, W // 8
-    wgt = torch.randn(B, 4, Ho, Wo, generator=g)
-    wgt[:, 3] *= 0.1
-    yref, gref = _reference_grads(net.state_dict(), x, wgt, enc_add, dec_add)
+    x = torch.rand(B, in_ch, H, W, generator=g)
+    Ho, Wo = _out_size(H), _out_size(W)
+    wgt = torch.randn(B, n_task + n_pos, Ho, Wo, generator=g)
+    wgt[:, n_task:] *= 0.1
+    yref, gref = _reference_grads(net.state_dict(), x, wgt, enc_add, dec_add, n_task, n_pos, in_ch)
 
     net = net.cuda().train()
     y = net(x.cuda())
-    assert y.requires_grad
+    assert y.requires_grad and tuple(y.shape) == (B, n_task + n_pos, Ho, Wo)
     (y * wgt.cuda()).sum().backward()
     torch.cuda.synchronize()
-    scale = max(1.0, (yref[:, :3] - MEAN[None, :, None, None]).abs().max().item())
-    assert (y.detach().cpu()[:, :3] - yref[:, :3]).abs().max().item() <= 1e-3 * scale
+    scale = max(1.0, (yref[:, :n_task] - mean[None, :, None, None]).abs().max().item())
+    assert (y.detach().cpu()[:, :n_task] - yref[:, :n_task]).abs().max().item() <= 1e-3 * scale
     worst, worst2 = [], []
     gmax = max(v.abs().max().item() for v in gref.values())
     for name, p in net.named_parameters():
@@ -108,6 +118,20 @@ def test_parameter_gradients_vs_autograd(B, H, W, enc_add, dec_add, tiny, form, 
     else:
         assert worst2[0][0] <= 1e-1 and worst[0][0] <= 0.5, (worst2[:5], worst[:5])
     assert net.encoder.conv1.bias.grad.abs().max().item() == 0.0
+
+
+@pytest.mark.parametrize("form", ["direct", "winograd"])
+@pytest.mark.parametrize("B,H,W,gray,n_task,n_pos,mean", [
+    (2, 57, 91, False, 3, 1, MEAN), (1, 75, 109, False, 3, 1, MEAN),            # odd sizes (the augmentation's frames)
+    (2, 57, 91, True, 3, 1, MEAN),                                              # --grayscale
+    (2, 64, 96, False, 1, 1, torch.tensor([241.47])), (2, 64, 96, False, 2, 1, torch.tensor([0.0, 0.0])),   # depth, normal
+    (2, 64, 96, False, 3, 0, MEAN)])                                            # --uncertainty None
+def test_parameter_gradients_in_the_training_driver_configurations(B, H, W, gray, n_task, n_pos, mean, form, monkeypatch):
+    """What train_single_task offers beyond the RGB coordinate network at multiples of 8: frames of int(480 s) x int(720 s)
+    (every stride-2 layer rounds up, the single-row tail of conv1's weight gradient, ragged Winograd tiles), one input
+    channel, the depth (1 + 1) and normal (2 + 1) heads and the head without a positive channel.  Criteria per form as in
+    test_parameter_gradients_vs_autograd, unchanged."""
+    _check_parameter_gradients(form, monkeypatch, B, H, W, 1, 1, False, n_task, n_pos, gray, mean)
 
 
 def test_gradients_accumulate_and_second_step_matches():
@@ -135,8 +159,19 @@ def test_training_forms_agree_at_full_size(monkeypatch):
     weight gradients, conv-epilogue statistics, coefficient tables) against the direct-convolution plan with separate
     statistics passes - two HIP lowerings, no CPU oracle in the loop.  Relative L2 per tensor: ReLU-mask flips between
     the two forward roundings move single elements (module docstring), not norms."""
-    x = torch.rand(2, 3, 480, 720, generator=torch.Generator().manual_seed(6)).cuda()
-    wgt = torch.randn(2, 4, 60, 90, generator=torch.Generator().manual_seed(7)).cuda()
+    _training_forms_agree(monkeypatch, 480, 720)
+
+
+def test_training_forms_agree_at_an_augmented_size(monkeypatch):
+    """The same at 323 x 485 = int(480 s) x int(720 s) for s = 0.674, a frame of the training augmentation: odd in both
+    directions, 41 x 61 cells (ragged Winograd tiles, ragged 128- and 256-row GEMM tiles, conv-epilogue statistics whose last
+    tile straddles the image boundary).  Criteria of test_training_forms_agree_at_full_size."""
+    _training_forms_agree(monkeypatch, 323, 485)
+
+
+def _training_forms_agree(monkeypatch, H, W):
+    x = torch.rand(2, 3, H, W, generator=torch.Generator().manual_seed(6)).cuda()
+    wgt = torch.randn(2, 4, _out_size(H), _out_size(W), generator=torch.Generator().manual_seed(7)).cuda()
 
     def run():
         net = networks.TransPoseNet(MEAN, False, False, 2, 2, 3, 1)
@@ -445,3 +480,94 @@ def test_stride2_data_gradient_on_the_split_pipe_vs_float64(CO, CI, B, H, W):
     assert torch.isfinite(got).all()
     err = (got - ref).abs().max().item() / ref.abs().max().item()
     assert err <= 2e-6, err
+
+
+def test_fill0_zeroes_exactly_the_bytes_it_is_given():
+    """XL_OP_FILL0 (the head of a backward op list zeroes the gradient-maximum slots with it): `Cin` bytes at `out`."""
+    buf = torch.full((64,), float("nan"), device="cuda")
+    op = networks.XlOp()
+    op.type, op.Cin, op.out = networks.XL_OP_FILL0, 4 * 24, buf.data_ptr() + 4 * 8
+    _run([op])
+    got = buf.cpu()
+    assert torch.isnan(got[:8]).all() and torch.isnan(got[32:]).all() and (got[8:32] == 0).all()
+
+
+def test_groupnorm_parameter_gradients_of_a_layer_list_in_one_launch():
+    """XL_OP_GNB_PARAMS_LIST: d gamma / d beta / d conv-bias of several layers in one launch from the sums their
+    XL_OP_GNB_FINAL ops wrote to buffers of their own (op.scale) - against autograd (5e-6 / 2e-5, as
+    test_groupnorm_backward_vs_autograd) and bitwise against XL_OP_GNB_PARAMS per layer.  Three layers of different widths,
+    sizes and batch counts, one of them without a convolution in front (dbias NULL)."""
+    import torch.nn.functional as F
+    layers = [(2, 9, 13, 64, 1), (1, 12, 16, 512, 7), (3, 5, 7, 256, 0)]
+    keep, items, results = [], [], []
+    for li, (B, H, W, C, flags) in enumerate(layers):
+        g = torch.Generator().manual_seed(C + flags)
+        x = (torch.randn(B, C, H, W, generator=g) * 2 + 0.5).requires_grad_(True)
+        aux = torch.randn(B, C, H, W, generator=g)
+        gamma = (1 + 0.2 * torch.randn(C, generator=g)).requires_grad_(True)
+        beta = (0.3 * torch.randn(C, generator=g)).requires_grad_(True)
+        o = F.group_norm(x, 32, gamma, beta, 1e-5)
+        if flags & 1:
+            o = F.relu(o)
+        if flags & 2:
+            o = o + aux
+        if flags & 4:
+            o = F.relu(o)
+        dout = torch.randn(o.shape, generator=g)
+        o.backward(dout)
+        HW = H * W
+        nch, nch2 = max(1, min(128, (HW + 255) // 256)), max(1, min(128, (HW + 63) // 64))
+        xd, ad, dd = _nhwc(x.detach()).cuda(), _nhwc(aux).cuda(), _nhwc(dout).cuda()
+        gd, bd = gamma.detach().cuda(), beta.detach().cuda()
+        stats = torch.zeros(B * nch * 32 * 2, dtype=torch.float64, device="cuda")
+        outf = torch.empty_like(xd)
+        table = torch.full((B * C * 4,), float("nan"), device="cuda")
+        scratch = torch.zeros(B * nch2 * C * 3 + B * C * 6 + (B * C * 3 + 1) // 2, dtype=torch.float64, device="cuda")
+        sums = torch.full((B * C * 6,), float("nan"), dtype=torch.float64, device="cuda")
+        per_layer = [torch.full((C,), float("nan"), device="cuda") for _ in range(3)]
+        listed = [torch.full((C,), float("nan"), device="cuda") for _ in range(3)]
+        no_bias = li == 2
+
+        def gn_op(typ):
+            op = networks.XlOp()
+            op.type = typ
+            op.B, op.Hi, op.Wi, op.Cin, op.groups, op.nchunks, op.nchunks2 = B, H, W, C, 32, nch, nch2
+            op.flags, op.eps = flags, 1e-5
+            op.ld_in, op.ld_aux, op.ld_out = C, C, C
+            op.in_, op.w, op.bias = xd.data_ptr(), gd.data_ptr(), bd.data_ptr()
+            return op
+        st, fin, ap = gn_op(networks.XL_OP_GN_STATS), gn_op(networks.XL_OP_GN_FINAL), gn_op(networks.XL_OP_GN_APPLY)
+        st.stats = fin.stats = ap.stats = stats.data_ptr()
+        fin.out, fin.out2 = table.data_ptr(), table.data_ptr() + 4 * B * C * 2
+        ap.aux, ap.aux2, ap.out = ad.data_ptr(), table.data_ptr(), outf.data_ptr()
+        ops = [st, fin, ap]
+        for typ, own in ((networks.XL_OP_GNB_STATS, False), (networks.XL_OP_GNB_FINAL, False), (networks.XL_OP_GNB_PARAMS, False),
+                         (networks.XL_OP_GNB_FINAL, True)):
+            op = gn_op(typ)
+            op.stats, op.aux, op.aux2, op.stats2 = table.data_ptr(), dd.data_ptr(), outf.data_ptr(), scratch.data_ptr()
+            if typ == networks.XL_OP_GNB_PARAMS:
+                op.out, op.out2, op.aux2 = per_layer[0].data_ptr(), per_layer[1].data_ptr(), per_layer[2].data_ptr()
+                if no_bias:
+                    op.flags = flags | networks.GN_NO_CONV_BIAS
+            if own:
+                op.scale = sums.data_ptr()
+            ops.append(op)
+        _run(ops)
+        items.append((sums.data_ptr(), gd.data_ptr(), listed[0].data_ptr(), listed[1].data_ptr(),
+                      0 if no_bias else listed[2].data_ptr(), B, C, 32, HW))
+        keep.append((xd, ad, dd, gd, bd, stats, outf, table, scratch, sums))
+        results.append((per_layer, listed, gamma.grad, beta.grad, x.grad.sum((0, 2, 3)), no_bias))
+    tab = torch.from_numpy(np.array(items, dtype=networks.GNB_PARAMS_ITEM_DTYPE).view(np.uint8).copy()).cuda()
+    op = networks.XlOp()
+    op.type, op.Cin, op.Cout, op.in_ = networks.XL_OP_GNB_PARAMS_LIST, len(items), max(i[6] for i in items), tab.data_ptr()
+    _run([op])
+
+    def rel(a, b):
+        return ((a - b).abs().max() / b.abs().max()).item()
+    for per_layer, listed, dg, db, dbias, no_bias in results:
+        assert rel(listed[0].cpu(), dg) < 5e-6 and rel(listed[1].cpu(), db) < 5e-6
+        assert torch.equal(listed[0], per_layer[0]) and torch.equal(listed[1], per_layer[1])
+        if no_bias:
+            assert torch.isnan(listed[2]).all() and torch.isnan(per_layer[2]).all()       # neither form writes it
+        else:
+            assert rel(listed[2].cpu(), dbias) < 2e-5 and torch.equal(listed[2], per_layer[2])

@@ -35,12 +35,13 @@ def test_semantics_network_matches_reference_golden(tag):
     assert torch.equal(torch.argmax(y.cpu(), 1)[clear], torch.argmax(ref, 1)[clear])
 
 
-@pytest.mark.parametrize("H,W", [(64, 96), (60, 92)])
+@pytest.mark.parametrize("H,W", [(64, 96), (60, 92), (57, 91), (64, 91)])
 def test_semantics_network_gradients_vs_autograd(monkeypatch, H, W):
     """Training the full-size head: cross-entropy loss, backward through fc3, the pixel shuffle (60x92: and the bilinear
     trim of networks.py:344-349, whose backward gathers onto the shuffled 64x96 grid), the DUC conv + GroupNorm(32 groups
     of 12 channels) and the rest of the network, against float64 autograd on the CPU restatement (criteria as in
-    tests/test_cnn_bwd_gpu.py: direct convolutions, max-norm)."""
+    tests/test_cnn_bwd_gpu.py: direct convolutions, max-norm).  57x91: odd in both directions (other trim ratios, conv1's
+    single-row tail); 64x91: the trim acts on the columns only."""
     from oracle import cnn_oracle
     monkeypatch.setenv("XL_NO_WINOGRAD_TRAIN", "1")
     B = 2
@@ -116,6 +117,28 @@ def test_semantics_loss_full_size_vs_oracle():
     assert torch.allclose(p.grad.cpu(), q.grad, rtol=2e-4, atol=1e-11)
     with pytest.raises(NotImplementedError):
         xl_loss.semantics_classification_loss('MLE', p, None, labels.cuda(), xl_loss.CrossEntropyLoss2d(), 'mean')
+
+
+@pytest.mark.parametrize("red", ["mean", None])
+@pytest.mark.parametrize("B,H,W", [(1, 1, 1), (1, 7, 9), (3, 61, 91), (70, 5, 7)])
+def test_semantics_loss_ragged_sizes_vs_oracle(B, H, W, red):
+    """Pixel counts that are no multiple of the 256-thread block (1, 63, 5551, 35) and 70 images: per-image results past
+    the 64 entries of finalize_kernel's LDS table come from its serial branch.  Tolerances of
+    test_semantics_loss_full_size_vs_oracle."""
+    g = torch.Generator().manual_seed(B * 1000 + H * W)
+    logits = torch.randn(B, 6, H, W, generator=g) * 3
+    labels = torch.randint(0, 6, (B, 1, H, W), generator=g).float()
+    wgt = torch.linspace(0.5, 1.5, B)
+    p = logits.cuda().requires_grad_(True)
+    loss, rate = xl_loss.semantics_classification_loss(None, p, None, labels.cuda(), xl_loss.CrossEntropyLoss2d(), red)
+    (loss * wgt.cuda()).sum().backward() if red is None else loss.backward()
+    q = logits.clone().requires_grad_(True)
+    lo, ro = loss_oracle.semantics_loss(q, labels, red)
+    (lo * wgt).sum().backward() if red is None else lo.backward()
+    assert tuple(loss.shape) == tuple(lo.shape)
+    assert torch.allclose(loss.detach().cpu(), lo.detach(), rtol=2e-6, atol=0.0)
+    assert float(rate) == pytest.approx(ro, abs=1e-6)
+    assert torch.allclose(p.grad.cpu(), q.grad, rtol=2e-4, atol=1e-11)
 
 
 def test_segmentation_metrics():
