@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import loss as xl_loss
-from . import networks, optim
+from . import networks, optim, switches
 
 TASK_CHANNELS = {'coord': 3, 'depth': 1, 'normal': 2, 'semantics': 6}     # learning.py:273-283
 SAMPLER_SEED = 2021
@@ -490,7 +490,8 @@ def run(opt, basename, encoders_in=None):
                                  getattr(opt, 'reuse_coord_encoder', False), getattr(opt, 'unfreeze_coord_encoder', False),
                                  network_in=network_in)
         network = network.to(dev).train()
-        workers = int(os.environ.get("XL_TRAIN_WORKERS", str(min(6, (os.cpu_count() or 2) // 2))))
+        workers = switches.live("XL_TRAIN_WORKERS")
+        workers = min(6, (os.cpu_count() or 2) // 2) if workers is None else int(workers)
         trainer = Trainer(network, dataset, opt.task, opt, output_dir, ckpt_dir, dev, rank, world, group,
                           host_reduce=shared, num_workers=workers)
         if resume_path:
