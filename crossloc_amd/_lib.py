@@ -63,6 +63,14 @@ def lib():
                                                  c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
                                                  c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32,
                                                  c_vp, c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
+        # include/crossloc_metrics.h
+        L.xl_metrics_workspace_bytes.restype = c_i64
+        L.xl_metrics_workspace_bytes.argtypes = [c_i32, c_i32]
+        for name in ("xl_metrics_depth", "xl_metrics_normal"):
+            getattr(L, name).restype = c_i32
+            getattr(L, name).argtypes = [c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_f, c_vp, c_vp, c_vp]
+        L.xl_metrics_semantics.restype = c_i32
+        L.xl_metrics_semantics.argtypes = [c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
         for name in ("xl_dsac_forward_rgbd", "xl_dsac_backward_rgbd"):
             getattr(L, name).restype = c_i32
         _lib = L

@@ -183,12 +183,14 @@ def _resized_shape(h, w, image_height):
     return image_height, int(image_height * w / h)
 
 
-def write_synthetic_scene(root, count, seed=2021, noise=0.5, outlier_ratio=0.0, semantics=False):
+def write_synthetic_scene(root, count, seed=2021, noise=0.5, outlier_ratio=0.0, semantics=False, depth=False, normal=False):
     """Write `count` synthetic frames in the on-disk format above (tests and demos; images are noise; `semantics`: also a
-    full-resolution map of RAW class ids per frame)."""
+    full-resolution map of RAW class ids per frame; `depth`: the z-buffer depth [Ho,Wo] of the ray-cast scene points in the
+    camera frame; `normal`: the terrain's unit surface normals [3,Ho,Wo] in the world frame; both -1 where a ray misses)."""
     from PIL import Image
     from . import synth
-    for sub in ("rgb", "poses", "calibration", "init") + (("semantics",) if semantics else ()):
+    extra = (("semantics",) if semantics else ()) + (("depth",) if depth else ()) + (("normal",) if normal else ())
+    for sub in ("rgb", "poses", "calibration", "init") + extra:
         os.makedirs(os.path.join(root, sub), exist_ok=True)
     rng = np.random.default_rng(seed)
     for i in range(count):
@@ -202,4 +204,19 @@ def write_synthetic_scene(root, count, seed=2021, noise=0.5, outlier_ratio=0.0, 
         if semantics:
             raw = np.array([0, 1, 2, 3, 6, 9, 17])[rng.integers(0, 7, size=(synth.IMAGE_H // 16, synth.IMAGE_W // 16))]
             np.save(os.path.join(root, "semantics", name + ".npy"), np.kron(raw, np.ones((16, 16), raw.dtype)))
+        if depth or normal:
+            gt = sc["gt_coords"].astype(np.float64)
+            hit = (gt != synth.NODATA).all(0)
+            if depth:
+                z = np.einsum("c,chw->hw", sc["pose"][:3, 2], gt - sc["pose"][:3, 3][:, None, None])   # third row of R^T (X - t)
+                torch.save(torch.from_numpy(np.where(hit, z, synth.NODATA).astype(np.float32)),
+                           os.path.join(root, "depth", name + ".dat"))
+            if normal:
+                e = 0.5
+                gx = (synth.terrain_height(gt[0] + e, gt[1]) - synth.terrain_height(gt[0] - e, gt[1])) / (2 * e)
+                gy = (synth.terrain_height(gt[0], gt[1] + e) - synth.terrain_height(gt[0], gt[1] - e)) / (2 * e)
+                nrm = np.stack([-gx, -gy, np.ones_like(gx)], 0)
+                nrm /= np.linalg.norm(nrm, axis=0, keepdims=True)
+                torch.save(torch.from_numpy(np.where(hit[None], nrm, synth.NODATA).astype(np.float32)),
+                           os.path.join(root, "normal", name + ".dat"))
     return root

@@ -285,3 +285,215 @@ class PipelinedLocalizer:
         for st in self.cnn:
             torch.cuda.current_stream().wait_stream(st)
         torch.cuda.current_stream().wait_stream(self.side)
+
+
+# ------------------------------------------------------------------- depth / normal / semantics: fused per-image metric rows
+
+TASK_CHANNELS = {'coord': 3, 'depth': 1, 'normal': 2, 'semantics': 6}    # utils/evaluation.py:86-95
+ROW_WIDTH = {'depth': 3, 'normal': 2, 'semantics': 36}
+_LABEL_CHANNELS = {'depth': 1, 'normal': 3, 'semantics': 1}
+
+
+def task_metric_rows(task, predictions, gt_label, nodata_value=-1, class_map=None, as_float=False):
+    """One row per image of the metric sums of `task`, on the device, from the HIP kernels of csrc/xl_metrics.hip
+    (include/crossloc_metrics.h): depth float64 [B,3] = {sum |d-g|/g, sum (d-g)^2, n_valid}; normal float64 [B,2] = {sum of
+    angles in degrees, n_valid}; semantics int64 [B,36] confusion counts (rows = ground truth), float64 with `as_float` (what
+    gather_errors pads with NaN; counts are exact below 2^53).
+
+    predictions [B,nt,H,W] float32 on the GPU: the task channels, sigma already split off - the strided `pred[:, :nt]` view
+    of the network output is read in place.  gt_label [B,1|3,H,W] (any float dtype / device; moved and made contiguous).
+    class_map: optional uint8 [B,H,W] on the device that receives the arg-max class (semantics).  No host synchronisation;
+    a frame's row does not depend on the batch or the slot it is in."""
+    import ctypes
+    from . import _lib
+    if task not in ROW_WIDTH:
+        raise NotImplementedError(task)
+    if not predictions.is_cuda:
+        raise RuntimeError("crossloc_amd.evaluation.task_metric_rows runs on the GPU only (no CPU fallback)")
+    nt = TASK_CHANNELS[task]
+    if predictions.dim() != 4 or predictions.shape[1] != nt:
+        raise RuntimeError("%s predictions must be [B,%d,H,W], got %s" % (task, nt, tuple(predictions.shape)))
+    B, _, H, W = predictions.shape
+    n = H * W
+    pred = predictions.detach()
+    if pred.dtype != torch.float32:
+        pred = pred.float()
+    if B > 0 and not pred[0, 0].is_contiguous():
+        pred = pred.contiguous()                                   # e.g. channels_last: cells of a channel must be contiguous
+    gt = gt_label.detach().to(device=pred.device, dtype=torch.float32).contiguous()
+    if tuple(gt.shape) != (B, _LABEL_CHANNELS[task], H, W):
+        raise RuntimeError("%s labels must be [%d,%d,%d,%d], got %s" % (task, B, _LABEL_CHANNELS[task], H, W, tuple(gt.shape)))
+    sem = task == 'semantics'
+    rows = torch.empty((B, ROW_WIDTH[task]), dtype=torch.int64 if sem else torch.float64, device=pred.device)
+    if B == 0:
+        return rows.double() if (sem and as_float) else rows
+    L = _lib.lib()
+    ws = torch.empty((int(L.xl_metrics_workspace_bytes(B, n)) + 7) // 8, dtype=torch.float64, device=pred.device)
+    vp = ctypes.c_void_p
+    stream = vp(torch.cuda.current_stream(pred.device).cuda_stream)
+    sb, sc = pred.stride(0), pred.stride(1)
+    with torch.cuda.device(pred.device):
+        if sem:
+            cm_ptr = None
+            if class_map is not None:
+                if (class_map.dtype != torch.uint8 or tuple(class_map.shape) != (B, H, W) or not class_map.is_contiguous()
+                        or class_map.device != pred.device):
+                    raise RuntimeError("class_map must be a contiguous uint8 [B,H,W] tensor on the predictions' device")
+                cm_ptr = vp(class_map.data_ptr())
+            st = L.xl_metrics_semantics(vp(pred.data_ptr()), sb, sc, nt, vp(gt.data_ptr()), B, n, vp(ws.data_ptr()),
+                                        vp(rows.data_ptr()), cm_ptr, stream)
+        else:
+            fn = L.xl_metrics_depth if task == 'depth' else L.xl_metrics_normal
+            st = fn(vp(pred.data_ptr()), sb, sc, vp(gt.data_ptr()), B, n, float(nodata_value), vp(ws.data_ptr()),
+                    vp(rows.data_ptr()), stream)
+    _lib.check(st)
+    return rows.double() if (sem and as_float) else rows
+
+
+def depth_eval(depth, gt_depth, nodata_value):
+    """utils/evaluation.py:247-267: (depth_abs_rel, depth_rms) over the has-data cells of the batch [B,1,H,W].  0-dim float64
+    tensors on the device (the reference returns fp32 CPU tensors; nothing synchronises here until the caller reads them)."""
+    s = task_metric_rows('depth', depth, gt_depth, nodata_value).sum(0)
+    return s[0] / s[2], torch.sqrt(s[1] / s[2])
+
+
+def normal_eval(normal_logits, gt_normals, nodata_value):
+    """utils/evaluation.py:294-316: mean angular error in degrees over the has-data cells of the batch (0-dim float64
+    tensor on the device)."""
+    s = task_metric_rows('normal', normal_logits, gt_normals, nodata_value).sum(0)
+    return s[0] / s[1]
+
+
+def semantic_eval_rows(semantic_logits, gt_label, mute=False):
+    """utils/evaluation.py:388-415 on the fused kernel: (class_prediction [B,H,W] int64 on the CPU, miou[B], fwiou[B], acc[B]),
+    the return values of `semantic_eval` - one launch and one read-back for the batch instead of a pass per image."""
+    B, _, H, W = semantic_logits.shape
+    cmap = torch.empty((B, H, W), dtype=torch.uint8, device=semantic_logits.device)
+    rows = task_metric_rows('semantics', semantic_logits, gt_label, class_map=cmap)
+    acc_ls, miou_ls, fwiou_ls = group_metrics('semantics', rows.cpu().numpy())
+    if not mute:
+        print("Metrics within the batch: mean accuracy: {:.2f}%, mean IoU: {:.2f}%, frequency weighted IoU: {:.2f}%".
+              format(acc_ls.mean() * 100, miou_ls.mean() * 100, fwiou_ls.mean() * 100))
+    # widened on the device, so the host does no pass of its own over B*H*W elements; the int64 copy dominates (DESIGN §8)
+    return cmap.to(torch.int64).cpu(), miou_ls, fwiou_ls, acc_ls
+
+
+def group_metrics(task, rows, group=4):
+    """Host: per-image rows [K,D] in dataset order -> the lists the reference's evaluation loop collects
+    (test_single_task.py:381-413).  The reference loader uses batch 4 for these tasks (utils/evaluation.py:69), so depth and
+    normal figures are per GROUP of `group` consecutive frames (a shorter last group): the rows of a group are summed, then
+    the formulas applied; a group without a valid cell gives NaN like the reference's 0/0.  Semantics is per image.
+      depth -> (abs_rel[G], rms[G]);  normal -> angular_err[G];  semantics -> (accuracy[K], mean_iou[K], fw_iou[K])."""
+    import warnings
+    rows = np.asarray(rows.cpu() if isinstance(rows, torch.Tensor) else rows, np.float64)
+    if rows.ndim != 2 or rows.shape[1] != ROW_WIDTH[task]:
+        raise ValueError("%s rows must be [K,%d], got %s" % (task, ROW_WIDTH[task], rows.shape))
+    if task == 'semantics':
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)        # an image without a labelled pixel: nanmean of all-NaN
+            m = [segmentation_metrics(r.reshape(6, 6)) for r in rows]
+        m = np.asarray(m, np.float64).reshape(-1, 3)
+        return m[:, 0], m[:, 1], m[:, 2]
+    sums = np.stack([rows[s:s + group].sum(0) for s in range(0, len(rows), group)]) if len(rows) else rows
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if task == 'depth':
+            return sums[:, 0] / sums[:, 2], np.sqrt(sums[:, 1] / sums[:, 2])
+        return sums[:, 0] / sums[:, 1]
+
+
+def _log_report(eval_str, testing_log, section, tail='\n'):
+    if testing_log:
+        with open(testing_log, 'a') as f:
+            f.write("{:s} Evaluation on section {:s} {:s}".format('=' * 20, section, '=' * 20) + '\n')
+            f.write(eval_str)
+            f.write(tail)
+
+
+def depth_printout(depth_abs_rel_ls, depth_rms_ls, testing_log=None, section="test"):
+    """utils/evaluation.py:270-291"""
+    depth_abs_rel_ls, depth_rms_ls = np.array(depth_abs_rel_ls), np.array(depth_rms_ls)
+    eval_str = "Depth accuracy:"
+    eval_str += "\nabsolute relative error, mean: {:.2f}%, median: {:.2f}%".format(
+        np.mean(depth_abs_rel_ls) * 100.0, np.median(depth_abs_rel_ls) * 100.0)
+    eval_str += "\nRMS error, mean: {:.2f}m, median: {:.2f}m".format(np.mean(depth_rms_ls), np.median(depth_rms_ls))
+    print(eval_str)
+    _log_report(eval_str, testing_log, section)
+    return eval_str
+
+
+def normal_printout(normal_angular_err_ls, testing_log=None, section="test"):
+    """utils/evaluation.py:319-336"""
+    normal_angular_err_ls = np.array(normal_angular_err_ls)
+    eval_str = "Surface normal accuracy:"
+    eval_str += "\nangular prediction error, mean: {:.1f} deg, median: {:.1f} deg".format(
+        np.mean(normal_angular_err_ls), np.median(normal_angular_err_ls))
+    print(eval_str)
+    _log_report(eval_str, testing_log, section)
+    return eval_str
+
+
+def semantic_printout(accuracy_ls, mean_iou_ls, fw_iou_ls, testing_log=None, section="test"):
+    """utils/evaluation.py:447-484; each argument is a list of per-batch arrays like the reference's, or one flat array."""
+    def flat(ls):
+        return np.concatenate([np.atleast_1d(np.asarray(a, np.float64)) for a in ls]) if len(ls) else np.zeros(0)
+    accuracy_ls, mean_iou_ls, fw_iou_ls = flat(accuracy_ls), flat(mean_iou_ls), flat(fw_iou_ls)
+    accuracy_str = "Pixel accuracy, mean: {:.2f}, median: {:.2f}".format(
+        np.mean(accuracy_ls) * 100, np.median(accuracy_ls) * 100)
+    print(accuracy_str)
+    mean_iou_str = "Mean IoU, mean: {:.2f}, median: {:.2f}".format(np.mean(mean_iou_ls) * 100, np.median(mean_iou_ls) * 100)
+    print(mean_iou_str)
+    fw_iou_str = "Frequency weighted IoU, mean: {:.2f}, median: {:.2f}".format(
+        np.mean(fw_iou_ls) * 100, np.median(fw_iou_ls) * 100)
+    print(fw_iou_str)
+    eval_str = accuracy_str + '\n' + mean_iou_str + '\n' + fw_iou_str
+    _log_report(eval_str, testing_log, section, tail='\n\n')                  # :479-484 ends the block with a blank line
+    return eval_str
+
+
+def config_network(task, tiny, grayscale, uncertainty, fullsize, network_in=None, num_enc=0):
+    """utils/evaluation.py:81-118 (TransPoseNet branch): the evaluation network of `task` on the GPU, in eval mode, with
+    per-image statistics passes (a frame's output must not depend on the batch it lands in).  `network_in`: a reference
+    state_dict loaded strictly; None -> the seeded generator's weights (tests and demos)."""
+    from . import networks
+    from .weights import seeded_state_dict
+    if task not in TASK_CHANNELS:
+        raise NotImplementedError(task)
+    if uncertainty not in (None, 'MLE'):
+        raise NotImplementedError(uncertainty)
+    if task == 'semantics' and uncertainty is not None:
+        raise NotImplementedError("semantics has no uncertainty channel")
+    if task == 'semantics' and not fullsize:
+        raise NotImplementedError("semantics needs fullsize")
+    nt = TASK_CHANNELS[task]
+    network = networks.TransPoseNet(torch.zeros(nt), tiny, grayscale, 2, 2, nt, 0 if uncertainty is None else 1, 32,
+                                    num_enc, 0, fullsize)
+    network.batch_invariant = True
+    if network_in:
+        network.load_state_dict(torch.load(network_in, map_location="cpu"), strict=True)
+    else:
+        network.load_state_dict(seeded_state_dict(network, seed=2021))
+    return network.cuda().eval()
+
+
+def evaluate_section(network, dataset, task, nodata_value=-1, batch=4, rank=0, world=1, process_group=None):
+    """The depth / normal / semantics loop of test_single_task.py:328-413 over one dataset section (a CamLocDataset built
+    with raw_image=True and the label of `task`): frame i goes to rank i % world; per batch the forward pass, the sigma
+    split and task_metric_rows - nothing is read back inside the loop; ONE gather_errors of the rows at the end.
+    Returns (rows [K,D] float64 numpy in dataset order, group_metrics(task, rows) on rank 0 / None elsewhere)."""
+    if task not in ROW_WIDTH:
+        raise NotImplementedError(task)
+    dev = next(network.parameters()).device
+    nt = network.num_task_channel
+    K = len(dataset)
+    mine = shard_indices(K, rank, world)
+    out = []
+    for s in range(0, len(mine), batch):
+        items = [dataset[i] for i in mine[s:s + batch]]
+        images = torch.stack([it[0] for it in items]).to(dev)
+        labels = torch.stack([it[2] for it in items]).to(dev)
+        with torch.no_grad():
+            pred = network(images)
+        out.append(task_metric_rows(task, pred[:, :nt], labels, nodata_value, as_float=True))   # sigma split: :351-356
+    local = torch.cat(out, 0) if out else torch.empty((0, ROW_WIDTH[task]), dtype=torch.float64, device=dev)
+    rows = gather_errors(local, K, rank, world, process_group).cpu().numpy()
+    return rows, (group_metrics(task, rows) if rank == 0 else None)
