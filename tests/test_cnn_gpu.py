@@ -345,7 +345,8 @@ def test_conv1_vs_torch(cin):
 
 
 @pytest.mark.parametrize("B,H,W,ppt", [(2, 24, 40, 5), (3, 37, 53, 2), (1, 64, 96, 1),
-                                       (2, 24, 40, 0), (3, 37, 53, 0), (1, 64, 96, 0), (2, 100, 203, 0), (1, 480, 720, 0)])
+                                       (2, 24, 40, 0), (3, 37, 53, 0), (1, 64, 96, 0), (2, 100, 203, 0), (1, 480, 720, 0),
+                                       (2, 17, 65, 0), (2, 31, 127, 0), (1, 33, 129, 0)])   # one row / column into, one short of, a 16 x 64 tile
 def test_conv1_inference_form_vs_torch(B, H, W, ppt):
     """XL_OP_CONV1 with `stats` (statistics-only evaluation), GN_FINAL, XL_OP_CONV1 with aux2 (second evaluation that
     writes relu(groupnorm(conv))) against torch conv2d -> group_norm(32 groups) -> relu; 37x53 leaves a ragged last
@@ -392,6 +393,7 @@ def test_conv1_inference_form_vs_torch(B, H, W, ppt):
     assert torch.allclose(st[..., 1], (raw64 * raw64).sum((2, 3)), rtol=1e-6, atol=2e-4)
     got = out.cpu().permute(0, 3, 1, 2).double()
     assert torch.isfinite(got).all()
+    print("conv1 inference form %dx%dx%d ppt %d: %.2e of max (bound 2e-5)" % (B, H, W, ppt, (got - ref).abs().max().item() / ref.abs().max().item()))
     _close(got, ref, 2e-5)
     bad = conv1()                                                        # too few workgroups for the image
     bad.stats, bad.nchunks = stats.data_ptr(), max(nch - 1, 0)
@@ -400,7 +402,9 @@ def test_conv1_inference_form_vs_torch(B, H, W, ppt):
 
 
 @pytest.mark.parametrize("C,H,W,flags", [(32, 24, 40, 1), (64, 12, 20, 1), (128, 6, 10, 1), (256, 9, 13, 7),
-                                          (512, 9, 13, 6), (512, 60, 90, 7), (1536, 8, 12, 0), (32, 480, 720, 1)])
+                                          (512, 9, 13, 6), (512, 60, 90, 7), (1536, 8, 12, 0), (32, 480, 720, 1)] +
+                         # 255, 256 and 257 pixels: one short of, exactly and one past a 256-pixel chunk of the statistics
+                         [(C, H, W, 7) for C in (64, 512) for H, W in ((15, 17), (16, 16), (1, 257))])
 def test_groupnorm_vs_torch(C, H, W, flags):
     g = torch.Generator().manual_seed(C + H)
     B = 2
@@ -431,7 +435,9 @@ def test_groupnorm_vs_torch(C, H, W, flags):
     ap.in_, ap.w, ap.bias, ap.aux, ap.stats, ap.out = (xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), ad.data_ptr(),
                                                        stats.data_ptr(), out.data_ptr())
     _run([st, ap])
-    _close(out.cpu().permute(0, 3, 1, 2), ref, 2e-5)
+    got = out.cpu().permute(0, 3, 1, 2)
+    print("groupnorm C %d %dx%d flags %d: %.2e of max (bound 2e-5)" % (C, H, W, flags, (got - ref).abs().max().item() / ref.abs().max().item()))
+    _close(got, ref, 2e-5)
 
 
 def test_head_vs_torch():
@@ -808,8 +814,13 @@ def test_winograd_input_transform_applies_deferred_groupnorm(relu, m):
         _run([bad])
 
 
-@pytest.mark.parametrize("m", [4, 6])
-@pytest.mark.parametrize("cin,cout,B,H,W", [(256, 256, 2, 8, 12), (512, 256, 1, 9, 13), (128, 64, 2, 12, 16)])
+# every (H mod m, W mod m) class of the partial tiles: two rows of tiles by three columns, the last of each from 1 to m pixels
+WINO_SWEEP = [(4, H, W) for H in range(5, 9) for W in range(9, 13)] + [(6, H, W) for H in range(7, 13) for W in range(13, 19)]
+
+
+@pytest.mark.parametrize("cin,cout,B,H,W,m", [(ci, co, B, H, W, m) for m in (4, 6)
+                                              for ci, co, B, H, W in ((256, 256, 2, 8, 12), (512, 256, 1, 9, 13), (128, 64, 2, 12, 16))] +
+                         [(128, 64, 2, H, W, m) for m, H, W in WINO_SWEEP if (m, H, W) != (6, 12, 16)])        # (12 x 16 is in the list above)
 def test_winograd_data_gradient_vs_autograd_and_accumulate(cin, cout, B, H, W, m):
     """dX of a stride-1 3x3 convolution as F(m x m,3x3) with the flipped, channel-swapped kernel; written into a channel
     slice of a wider gradient tensor, then accumulated a second time."""
@@ -824,6 +835,8 @@ def test_winograd_data_gradient_vs_autograd_and_accumulate(cin, cout, B, H, W, m
     U = _wino_weights(w, m, dgrad=True)
     _wino_conv(_nhwc(dy).cuda(), U, None, m, B, H, W, cout, cin, sl, cin + 64)
     got = sl.permute(0, 3, 1, 2).cpu().double()
+    print("winograd dgrad m %d %dx%d: %.2e of max (bound %g)" % (m, H, W, (got - ref).abs().max().item() / ref.abs().max().item(),
+                                                                 3e-5 if m == 4 else 6e-5))
     _close(got, ref, 3e-5 if m == 4 else 6e-5)
     assert float(wide[..., :32].abs().max()) == 0.0 and float(wide[..., 32 + cin:].abs().max()) == 0.0
     _wino_conv(_nhwc(dy).cuda(), U, None, m, B, H, W, cout, cin, sl, cin + 64, accumulate=True)
@@ -836,6 +849,24 @@ def test_winograd_data_gradient_vs_autograd_and_accumulate(cin, cout, B, H, W, m
 def test_winograd_weight_gradient_vs_autograd(m, cin, cout, B, H, W):
     """dW of a stride-1 3x3 layer through F(m x m,3x3): V = B^T x B, dM = A dY A^T, (m+2)^2 batched tile-GEMMs, G^T dU G;
     9x13 has partial tiles on both edges."""
+    _winograd_weight_gradient(m, cin, cout, B, H, W)
+
+
+@pytest.mark.parametrize("m,H,W", WINO_SWEEP)
+def test_winograd_weight_gradient_over_every_partial_tile_class(m, H, W):
+    """64 -> 128 channels over every (H mod m, W mod m) class.  Two frames of these maps are 12 tiles, and the tile-GEMM (the tiles are
+    its K dimension, 32 per step) refuses fewer than 32 by name - plans take the direct weight gradient below 64 tiles
+    (forms.wino_wgrad_ok).  So: the refusal at two frames, then six frames (36 tiles: one full K-step and a ragged one of 4) against
+    float64 at the bound above."""
+    from crossloc_amd import _lib
+    with pytest.raises(_lib.XlError) as e:
+        _winograd_weight_gradient(m, 64, 128, 2, H, W)
+    msg = str(e.value)
+    assert "op 2 refused" in msg and "type %d" % networks.XL_OP_WGRAD in msg and "64 -> 128 channels" in msg, msg
+    _winograd_weight_gradient(m, 64, 128, 6, H, W)
+
+
+def _winograd_weight_gradient(m, cin, cout, B, H, W):
     g = torch.Generator().manual_seed(cin * 3 + cout + H)
     x = torch.relu(torch.randn(B, cin, H, W, generator=g))
     dy = torch.randn(B, cout, H, W, generator=g)
@@ -870,7 +901,9 @@ def test_winograd_weight_gradient_vs_autograd(m, cin, cout, B, H, W):
     f.Cin, f.Cout = cin, cout
     f.in_, f.out = dU.data_ptr(), dw.data_ptr()
     _run([a, d, wg, f])
-    _close(dw.cpu().double(), ref, 1e-4)
+    got = dw.cpu().double()
+    print("winograd wgrad m %d %dx%dx%d: %.2e of max (bound 1e-4)" % (m, B, H, W, (got - ref).abs().max().item() / ref.abs().max().item()))
+    _close(got, ref, 1e-4)
 
 
 @pytest.mark.skipif(bool(os.environ.get("XL_NO_WINOGRAD")), reason="asserts the Winograd forms of the default plans (measurement switch set)")
@@ -932,7 +965,9 @@ def test_folded_groupnorm_apply_is_bitwise_the_separate_pass(monkeypatch):
     (128, 256, 2, 35, 49, True, True, 32),      # conv4, operands inside wider tensors
     (128, 256, 5, 120, 180, True, False, 0),    # conv4 at its real size: 106 tiles per... 27000 rows, several tiles per CU later
     (64, 128, 9, 96, 120, True, True, 0),       # 102 tiles on <= 256 workgroups with second tiles (stores in flight)
-    (32, 64, 40, 80, 96, True, True, 0)])       # 300 tiles: every workgroup past its first tile
+    (32, 64, 40, 80, 96, True, True, 0)] +      # 300 tiles: every workgroup past its first tile
+    # all four parity classes of every stem layer (even sizes: the far-edge taps are inside the image; odd: on the padding)
+    [(ci, co, 2, H, W, True, True, 0) for ci, co in ((32, 64), (64, 128), (128, 256)) for H in (33, 34) for W in (41, 42)])
 def test_stride2_stem_conv_on_the_split_bf16_pipe(cin, cout, B, H, W, norm, relu, pad):
     """XL_OP_CONV 3x3 stride 2 with XL_CONV_SPLIT_BF16 | XL_CONV_SPLIT_IL (csrc/xl_stem_split.hip): weights split on the host
     (K tap-major), fp32 activations gathered per tap, optionally normalised (the producer's GroupNorm + ReLU applied to
@@ -1005,6 +1040,7 @@ def test_stride2_stem_conv_on_the_split_bf16_pipe(cin, cout, B, H, W, norm, relu
     scale = ref.abs().max().item()
     e32 = (out32.cpu().permute(0, 3, 1, 2).double() - ref).abs().max().item() / scale
     esp = (got - ref).abs().max().item() / scale
+    print("six-pass stem %d -> %d %dx%dx%d: %.2e of max, fp32 MFMA %.2e (bound 2e-6 and 4 x + 2e-7)" % (cin, cout, B, H, W, esp, e32))
     assert esp < 2e-6 and esp < 4 * e32 + 2e-7, (esp, e32)
 
 
@@ -1163,7 +1199,8 @@ def test_tile_major_winograd_product_is_bitwise_the_plane_major_form(monkeypatch
 
 
 @pytest.mark.skipif(os.environ.get("XL_GEMM_SPLIT_BF16") in ("0", "1"), reason="these forms belong to the split-pipe plans (measurement switch set)")
-@pytest.mark.parametrize("B,H,W", [(2, 64, 96), (1, 70, 100), (3, 41, 57), (2, 480, 720)])
+@pytest.mark.parametrize("B,H,W", [(2, 64, 96), (1, 70, 100), (3, 41, 57), (2, 480, 720),
+                                   (2, 42, 57), (2, 41, 58), (2, 42, 58)])                 # H and W of opposite parity; both even off the tile
 def test_fused_stem_is_bitwise_the_two_kernel_path(B, H, W, monkeypatch):
     """Round 4: conv1 + GroupNorm + ReLU evaluated inside conv2's operand stage (XL_OP_STEM12, csrc/xl_stem_fused.hip) against the
     two-kernel path (conv1 writes its raw output, conv2 normalises and splits it on load; XL_NO_STEM12=1).  Same term pairs, same

@@ -60,7 +60,8 @@ def _results(dw, db, Cin):
 
 # (1, 41, 57): odd height - the last step of a workgroup is a single row; (3, 7, 5) / (1, 1, 1): frames smaller than a step
 # of 32 pixels; (1, 9, 1100): 4 staged rows of 1102 float4 = 70528 bytes of LDS, past the 64 KiB a kernel gets unasked
-SHAPES = [(2, 40, 56), (1, 41, 57), (3, 7, 5), (1, 1, 1), (1, 9, 1100)]
+# (2, 42, 57) / (2, 41, 58): height and width of opposite parity
+SHAPES = [(2, 40, 56), (1, 41, 57), (3, 7, 5), (1, 1, 1), (1, 9, 1100), (2, 42, 57), (2, 41, 58)]
 
 
 @pytest.mark.parametrize("rows", [0, 8, 3, "H"])

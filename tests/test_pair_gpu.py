@@ -160,7 +160,10 @@ def test_pair_gemm_vs_float64_and_the_fp32_mfma_kernel(Z, T, cin, cout, vmag, um
     (32, 512, 7, 64, 80, True, True, True, 0, 256),       # two K-steps per tile
     (512, 256, 1, 60, 90, True, True, True, 0, 128),      # single-frame forms
     (512, 512, 1, 60, 90, True, True, True, 0, 192),
-    (512, 512, 2, 60, 90, False, False, True, 0, 384)])
+    (512, 512, 2, 60, 90, False, False, True, 0, 384)] +
+    # 255, 256 and 257 pixels per image: one short of, exactly and one past a 256-row tile (and its statistics entry)
+    # (255 pixels are less than a 256-row tile: refused by name below, and run on the 128-row tiles)
+    [(512, 512, 3, H, W, True, True, True, 0, 256) for H, W in ((15, 17), (16, 16), (1, 257))] + [(512, 512, 3, 15, 17, True, True, True, 0, 128)])
 def test_pair_conv1x1_vs_float64_and_the_split_bf16_kernel(cin, cout, B, H, W, norm, relu, stats, pad, form):
     """pair_conv1x1_kernel: fp32 activations, (optionally) normalised and turned into pairs on their way into LDS; bias, the
     GroupNorm partial sums of the output, every tile form - against float64 and beside the six-pass bf16 kernel."""
@@ -207,10 +210,20 @@ def test_pair_conv1x1_vs_float64_and_the_split_bf16_kernel(cin, cout, B, H, W, n
         if pad:
             assert torch.isnan(o[..., cout:]).all()
         return o[..., :cout].permute(0, 3, 1, 2).double(), st.cpu()
+    if (norm or stats or form < 0) and H * W < rows:
+        # a row tile may touch two images at most (their coefficients, their statistics entries): an image smaller than a tile is
+        # refused by both kernels, by name (forms.py: plans take the fp32 kernel below 256 pixels)
+        from crossloc_amd import _lib
+        for pair in (True, False):
+            with pytest.raises(_lib.XlError) as e:
+                run(pair)
+            assert "op 0 refused" in str(e.value) and "%d -> %d channels" % (cin, cout) in str(e.value), str(e.value)
+        return
     got, st = run(True)
     six, _ = run(False)
     sc = ref.abs().max().item()
     esp, e6 = (got - ref).abs().max().item() / sc, (six - ref).abs().max().item() / sc
+    print("pair conv1x1 %d -> %d %dx%dx%d form %d: %.2e of max, six-pass %.2e (bound 2e-6 and 1.5 x + 1e-7)" % (cin, cout, B, H, W, form, esp, e6))
     assert esp < 2e-6 and esp <= 1.5 * e6 + 1e-7, (esp, e6)
     if stats:
         sums = st.view(B, nchunks, G, 2)
@@ -276,7 +289,9 @@ def test_pair_conv1x1_residual_on_load(cin, cout, B, H, W, pad, form):
 @pytest.mark.parametrize("cin,cout,B,H,W,norm,relu,pad", [
     (64, 128, 2, 60, 90, True, True, 0), (128, 256, 2, 60, 90, True, True, 0), (32, 64, 2, 40, 64, True, True, 0),
     (64, 128, 3, 37, 53, True, False, 32), (128, 256, 5, 33, 41, False, False, 0), (128, 256, 1, 120, 180, True, True, 0),
-    (32, 64, 1, 97, 131, False, False, 0)])
+    (32, 64, 1, 97, 131, False, False, 0)] +
+    # all four parity classes of every stem layer (even sizes: the far-edge taps are inside the image; odd: on the padding)
+    [(ci, co, 2, H, W, True, True, 0) for ci, co in ((32, 64), (64, 128), (128, 256)) for H in (33, 34) for W in (41, 42)])
 def test_stride2_stem_conv_as_fp16_pairs(cin, cout, B, H, W, norm, relu, pad):
     """pair_conv3x3s2_kernel (csrc/xl_stem_pair.hip): the stride-2 3x3 stem layers with three fp16 passes - against a float64
     convolution, beside the six-pass bf16 kernel, with the GroupNorm partial sums of the epilogue."""
@@ -330,6 +345,7 @@ def test_stride2_stem_conv_as_fp16_pairs(cin, cout, B, H, W, norm, relu, pad):
     six, _ = run(False)
     sc = ref.abs().max().item()
     esp, e6 = (got - ref).abs().max().item() / sc, (six - ref).abs().max().item() / sc
+    print("pair stem %d -> %d %dx%dx%d: %.2e of max, six-pass %.2e (bound 2e-6 and 1.5 x + 1e-7)" % (cin, cout, B, H, W, esp, e6))
     assert esp < 2e-6 and esp <= 1.5 * e6 + 1e-7, (esp, e6)
     grouped = got.reshape(B, 32, cout // 32, HWo)
     for n in range(B):
@@ -344,7 +360,18 @@ def test_stride2_stem_conv_as_fp16_pairs(cin, cout, B, H, W, norm, relu, pad):
 @pytest.mark.parametrize("defer", [0, 1, 2])
 def test_winograd_input_transform_writes_the_pairs_of_its_fp32_result(defer):
     """XL_OP_WINO_IN with XL_CONV_PAIR_F16: V as activation pairs = the split of the fp32 transform's V, to the bit."""
-    B, H, W, C = 2, 13, 20, 128
+    _input_transform_pairs(defer, 13, 20)
+
+
+@pytest.mark.parametrize("H,W", [(7, 18), (8, 17), (9, 16), (10, 15), (11, 14), (12, 13)])
+@pytest.mark.parametrize("defer", [0, 1, 2])
+def test_winograd_input_transform_pairs_with_every_partial_last_tile(defer, H, W):
+    """The same with last tiles of 1 to 6 rows against last tiles of 6 to 1 columns."""
+    _input_transform_pairs(defer, H, W)
+
+
+def _input_transform_pairs(defer, H, W):
+    B, C = 2, 128
     g = torch.Generator().manual_seed(defer)
     x = (torch.randn(B, H, W, C, generator=g) * 2.0).cuda()
     coef = torch.stack([torch.rand(B, C, generator=g) + 0.5, torch.randn(B, C, generator=g)], 2).contiguous().cuda()
@@ -370,6 +397,114 @@ def test_winograd_input_transform_writes_the_pairs_of_its_fp32_result(defer):
     networks._check(networks._bind().xl_cnn_pair_activation(outs[0].data_ptr(), want.data_ptr(), 64 * T, C, scale.data_ptr(), None))
     torch.cuda.synchronize()
     assert torch.equal(outs[1].view(torch.int16), want)
+
+
+# every (H mod m, W mod m) class of the partial tiles: two rows of tiles by three columns, the last of each from 1 to m pixels
+WINO_CHAIN = [(6, H, W) for H in range(7, 13) for W in range(13, 19)] + [(4, H, W) for H in range(5, 9) for W in range(9, 13)]
+
+
+def _wino_chain(form, x, coef, defer, w, bias, m, B, H, W, cin, cout, scale=None):
+    """Input transform (deferred GroupNorm: 0 none, 1 apply, 2 apply + ReLU) -> (m+2)^2 batched GEMMs -> output transform with
+    bias and GroupNorm partial sums, the GEMM operands in `form`:
+      fp32: V and U in fp32, the fp32-MFMA kernel (the accuracy yardstick);
+      pair: V written as fp16 pairs by the transform, U as pairs, pair_gemm_kernel - what inference plans run for F(6x6,3x3);
+      six : V in fp32, split into three bf16 terms by the GEMM (XL_CONV_SPLIT_ACT), U as interleaved bf16 planes - what training
+            plans run for F(4x4,3x3) (and for F(6x6,3x3) without the pair switch).
+    Returns (result as float64 NCHW, statistics [B, chunks, 32, 2], the transform's V)."""
+    Th, Tw = -(-H // m), -(-W // m)
+    T, nf, G = B * Th * Tw, (m + 2) ** 2, 32
+    V = torch.zeros(nf * T * cin, device="cuda")
+    Mb = torch.full((nf * T * cout,), float("nan"), device="cuda")
+    out = torch.full((B, H, W, cout), float("nan"), device="cuda")
+    a = networks.XlOp()
+    a.type, a.ksize = networks.XL_OP_WINO_IN, m
+    a.B, a.Hi, a.Wi, a.Cin, a.Ho, a.Wo, a.ld_in = B, H, W, cin, Th, Tw, cin
+    a.in_, a.out = x.data_ptr(), V.data_ptr()
+    if defer:
+        a.aux2 = coef.data_ptr()
+        a.flags = networks.GN_RELU_IN if defer == 2 else 0
+    gm = networks.XlOp()
+    gm.type = networks.XL_OP_CONV
+    gm.B, gm.Hi, gm.Wi, gm.Cin, gm.Ho, gm.Wo, gm.Cout = B, Th, Tw, cin, Th, Tw, cout
+    gm.ksize, gm.stride, gm.ld_in, gm.ld_out, gm.nchunks2 = 1, 1, cin, cout, nf
+    gm.in_, gm.out = V.data_ptr(), Mb.data_ptr()
+    if form == "pair":
+        U = torch.zeros(2 * nf * cout * cin + 4 * nf, dtype=torch.int16, device="cuda")
+        networks._check(networks._bind().xl_cnn_pack_wino_weight_pair(w.data_ptr(), U.data_ptr(), cout, cin, m, 0, None))
+        a.flags |= networks.CONV_PAIR_F16
+        gm.flags = PAIR
+        a.scale = gm.scale = scale.data_ptr()
+    else:
+        plan = networks._Plan.__new__(networks._Plan)                   # [(m+2)^2][Cout][Cin] exactly as a plan packs it
+        plan.device = torch.device("cuda")
+        U = torch.empty(nf * cout * cin, dtype=torch.float32, device="cuda")
+        plan._pack(U, w, "wino%d" % m)
+        if form == "six":
+            U = networks._Plan.split_bf16_interleaved(U.view(nf, cout, cin), cin)
+            gm.flags = networks.CONV_SPLIT_BF16 | networks.CONV_SPLIT_IL | networks.CONV_SPLIT_ACT
+            gm.reserved_i = 256
+    gm.w = U.data_ptr()
+    tpb = 16
+    nch = -(-(Th * Tw) // tpb)
+    stats = torch.full((B, nch, G, 2), float("nan"), dtype=torch.float64, device="cuda")
+    o = networks.XlOp()
+    o.type, o.ksize = networks.XL_OP_WINO_OUT, m
+    o.B, o.Hi, o.Wi, o.Cin, o.ld_out, o.groups, o.nchunks, o.reserved_i = B, H, W, cout, cout, G, nch, tpb
+    o.in_, o.out, o.bias, o.stats = Mb.data_ptr(), out.data_ptr(), bias.data_ptr(), stats.data_ptr()
+    _run([a, gm, o])
+    return out.permute(0, 3, 1, 2).cpu().double(), stats.cpu(), V
+
+
+@pytest.mark.parametrize("m,H,W", WINO_CHAIN)
+def test_winograd_chain_in_the_forms_the_plans_run_vs_float64(m, H, W):
+    """The Winograd layer as plans run it, over every partial-tile class, two frames, against a float64 convolution of the input with
+    the deferred GroupNorm applied (none / apply / apply + ReLU in rotation).  F(6x6,3x3): the pair form of inference plans.
+    F(4x4,3x3): no transform writes pairs for it - training plans keep V in fp32 and the GEMM splits it into three bf16 terms; that
+    form.  128 input channels; 256 output channels, because both GEMM kernels tile 256 columns and refuse 128 (asserted by name - a
+    plan takes the fp32 GEMM for such a layer).  Bounds: the caps of test_winograd_conv_with_statistics_vs_float64 (6e-5 / 3e-5 of
+    max |reference|), and no worse than 1.5 x the same chain with the fp32-MFMA GEMM on the same data (+ 1e-7), the bar of every
+    pair kernel in this file; the GroupNorm sums of the epilogue as in that test."""
+    from crossloc_amd import _lib
+    B, cin, cout = 2, 128, 256
+    form = "pair" if m == 6 else "six"
+    defer = WINO_CHAIN.index((m, H, W)) % 3
+    g = torch.Generator().manual_seed(m * 10000 + H * 100 + W)
+    x = torch.randn(B, H, W, cin, generator=g) * 2.0
+    coef = torch.stack([torch.rand(B, cin, generator=g) + 0.5, torch.randn(B, cin, generator=g)], 2).contiguous()
+    w = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+    b = torch.randn(cout, generator=g)
+    xn = x.double()
+    if defer:
+        xn = xn * coef[:, None, None, :, 0].double() + coef[:, None, None, :, 1].double()
+        if defer == 2:
+            xn = xn.clamp(min=0)
+    ref = F.conv2d(xn.permute(0, 3, 1, 2), w.double(), b.double(), padding=1)
+    xd, cd, wd, bd = x.cuda(), coef.cuda(), w.cuda().contiguous(), b.cuda()
+    y32, _, V32 = _wino_chain("fp32", xd, cd, defer, wd, bd, m, B, H, W, cin, cout)
+    scale = _scale_for(V32.abs().max().item(), 2)
+    got, stats, _ = _wino_chain(form, xd, cd, defer, wd, bd, m, B, H, W, cin, cout, scale)
+    assert torch.isfinite(got).all()
+    sc = ref.abs().max().item()
+    e, e32 = (got - ref).abs().max().item() / sc, (y32 - ref).abs().max().item() / sc
+    cap = 6e-5 if m == 6 else 3e-5
+    print("winograd chain m %d %s %dx%d defer %d: %.2e of max, fp32 GEMM %.2e (bound %g and 1.5 x + 1e-7)" % (m, form, H, W, defer, e, e32, cap))
+    assert e <= cap and e <= 1.5 * e32 + 1e-7, (e, e32)
+    st = stats.sum(1)                                           # [B, 32, 2]
+    y = got.reshape(B, 32, cout // 32, H * W)
+    assert torch.allclose(st[..., 0], y.sum((2, 3)), rtol=1e-5, atol=2e-3)
+    assert torch.allclose(st[..., 1], (y * y).sum((2, 3)), rtol=1e-5, atol=2e-3)
+    # 128 -> 128: the GEMM of this form has no 128-column tile
+    bad = networks.XlOp()
+    bad.type = networks.XL_OP_CONV
+    bad.B, bad.Hi, bad.Wi, bad.Cin, bad.Ho, bad.Wo, bad.Cout = B, 2, 3, cin, 2, 3, 128
+    bad.ksize, bad.stride, bad.ld_in, bad.ld_out, bad.nchunks2 = 1, 1, cin, 128, (m + 2) ** 2
+    bad.flags = PAIR if m == 6 else (networks.CONV_SPLIT_BF16 | networks.CONV_SPLIT_IL | networks.CONV_SPLIT_ACT)
+    bad.in_ = bad.w = bad.out = V32.data_ptr()
+    bad.scale = scale.data_ptr()
+    with pytest.raises(_lib.XlError) as err:
+        _run([bad])
+    msg = str(err.value)
+    assert "op 0 refused" in msg and "type %d" % networks.XL_OP_CONV in msg and "128 -> 128 channels" in msg, msg
 
 
 def test_pair_scales_follow_the_groupnorm_bound():
