@@ -22,8 +22,13 @@
 //   write      inverse rigid transform as float 4x4 (pose2trans, dsacstar_util.h:759-770)
 //
 // Arithmetic contract: compiled with -ffp-contract=off; every transcendental is a fixed polynomial in
-// + - * / sqrt; reductions use a fixed order.  tests/test_dsac_gpu.py checks sampled cells, tries,
-// scores, winner and refined pose against oracle/dsac_oracle.c bit for bit.
+// + - * / sqrt; reductions use a fixed order.  What one lane computes on its own (the polynomials, the RNG, projection,
+// quartic, P3P, the Cholesky step, the backward pass's derivatives) lives in xl_dsac_math.h, which the CPU oracle compiles
+// too; this file keeps what is parallel: LDS staging, ballots, wave and block reductions, the LM state machine, the
+// kernels and the host entry points.  tests/test_dsac_gpu.py checks sampled cells, tries, scores, winner and refined pose
+// against oracle/dsac_oracle.c bit for bit - a check of that parallel part and of gcc == hipcc, not of the shared
+// formulas (those: tests/indep_dsac.py and tests/test_oracle_dsac_pin.py).  The oracle includes the header; nothing here
+// includes the oracle.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -42,136 +47,30 @@ constexpr int kMaxCells = kThreads * kMaxCellsPerThread;     // 16384
 constexpr int kLmMaxIter = 20;                               // cv::solvePnP ITERATIVE term criteria
 constexpr double kFltEps = 1.1920928955078125e-07;
 
-struct Pose { double R[9]; double t[3]; };                   // world -> camera
+// Pose, Cam, V3 and every function one lane evaluates on its own (deterministic exp / sincos / atan2, RNG, projection,
+// quartic, P3P, Cholesky step, the backward pass's derivatives): shared with the CPU oracle, written once
+#include "xl_dsac_math.h"
 
-// ------------------------------------------------------------------------------ deterministic math
-
-__device__ __forceinline__ double pow2i(int k)
-{
-    return __longlong_as_double((long long)(k + 1023) << 52);
-}
-
-__device__ __forceinline__ double det_exp(double x)
-{
-    if (x != x) return x;
-    if (x > 709.0) return __longlong_as_double(0x7ff0000000000000LL);
-    if (x < -708.0) return 0.0;
-    const double INV_LN2 = 0x1.71547652b82fep+0;
-    const double LN2_HI = 0x1.62e42f8000000p-1;
-    const double LN2_LO = 0x1.be8e7bcd5e4f2p-27;
-    double kf = floor(x * INV_LN2 + 0.5);
-    double r = (x - kf * LN2_HI) - kf * LN2_LO;
-    double p = 1.0 / 87178291200.0;
-    p = p * r + 1.0 / 6227020800.0;
-    p = p * r + 1.0 / 479001600.0;
-    p = p * r + 1.0 / 39916800.0;
-    p = p * r + 1.0 / 3628800.0;
-    p = p * r + 1.0 / 362880.0;
-    p = p * r + 1.0 / 40320.0;
-    p = p * r + 1.0 / 5040.0;
-    p = p * r + 1.0 / 720.0;
-    p = p * r + 1.0 / 120.0;
-    p = p * r + 1.0 / 24.0;
-    p = p * r + 1.0 / 6.0;
-    p = p * r + 0.5;
-    p = p * r + 1.0;
-    p = p * r + 1.0;
-    return p * pow2i((int)kf);
-}
-
-__device__ __forceinline__ void det_sincos(double x, double &s, double &c)
-{
-    const double TWO_OVER_PI = 0x1.45f306dc9c883p-1;
-    const double PIO2_HI = 0x1.921fb50000000p+0;
-    const double PIO2_LO = 0x1.110b4611a6263p-26;
-    double kf = floor(x * TWO_OVER_PI + 0.5);
-    double r = (x - kf * PIO2_HI) - kf * PIO2_LO;
-    double r2 = r * r;
-    double ps = -1.0 / 355687428096000.0;
-    ps = ps * r2 + 1.0 / 1307674368000.0;
-    ps = ps * r2 - 1.0 / 6227020800.0;
-    ps = ps * r2 + 1.0 / 39916800.0;
-    ps = ps * r2 - 1.0 / 362880.0;
-    ps = ps * r2 + 1.0 / 5040.0;
-    ps = ps * r2 - 1.0 / 120.0;
-    ps = ps * r2 + 1.0 / 6.0;
-    double sr = r - r * r2 * ps;
-    double pc = -1.0 / 6402373705728000.0;
-    pc = pc * r2 + 1.0 / 20922789888000.0;
-    pc = pc * r2 - 1.0 / 87178291200.0;
-    pc = pc * r2 + 1.0 / 479001600.0;
-    pc = pc * r2 - 1.0 / 3628800.0;
-    pc = pc * r2 + 1.0 / 40320.0;
-    pc = pc * r2 - 1.0 / 720.0;
-    pc = pc * r2 + 1.0 / 24.0;
-    double cr = 1.0 - r2 * (0.5 - r2 * pc);
-    double q = kf - 4.0 * floor(kf * 0.25);
-    int qi = (int)q;
-    if (qi == 0) { s = sr; c = cr; }
-    else if (qi == 1) { s = cr; c = -sr; }
-    else if (qi == 2) { s = -sr; c = -cr; }
-    else { s = -cr; c = sr; }
-}
-
-// ------------------------------------------------------------------------------ counter-based RNG
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t try_state(uint64_t imageKey, uint32_t hyp, uint32_t t)
-{
-    return mix64(imageKey ^ (((uint64_t)hyp << 32) | (uint64_t)t));
-}
-
-__device__ __forceinline__ int draw(uint64_t state, int j, int n)
-{
-    uint64_t r = mix64(state + 0x9e3779b97f4a7c15ULL * (uint64_t)(j + 1));
-    uint32_t hi = (uint32_t)(r >> 32);
-    return (int)(((uint64_t)hi * (uint64_t)(uint32_t)n) >> 32);
-}
-
-// ------------------------------------------------------------------------------ camera + coordinates
-
-struct Cam { double f, cx, cy; float thr, alpha, maxReproj; int sub, Ho, Wo, N; };
-
-// scene coordinates of the image: SoA planes in LDS
+// scene coordinates of the image: SoA planes in LDS (cell i = y * Wo + x)
 struct Coords {
     const float *sx, *sy, *sz;
     __device__ __forceinline__ void fetch(int i, double &X, double &Y, double &Z) const
     {
         X = (double)sx[i]; Y = (double)sy[i]; Z = (double)sz[i];
     }
+    // clamped reprojection error of cell i, whose row / column the caller divides out or carries along (CellWalk)
+    __device__ __forceinline__ float err(const Pose &p, int i, int y, int x, const Cam &cam) const
+    {
+        double X, Y, Z;
+        fetch(i, X, Y, Z);
+        return cell_err(&p, X, Y, Z, y, x, &cam);
+    }
+    __device__ __forceinline__ float err(const Pose &p, int i, const Cam &cam) const
+    {
+        int y = i / cam.Wo, x = i - y * cam.Wo;
+        return err(p, i, y, x, cam);
+    }
 };
-
-__device__ __forceinline__ void project(const Pose &p, double X, double Y, double Z, const Cam &cam,
-                                        float &u, float &v)
-{
-    double xc = p.R[0] * X + p.R[1] * Y + p.R[2] * Z + p.t[0];
-    double yc = p.R[3] * X + p.R[4] * Y + p.R[5] * Z + p.t[1];
-    double zc = p.R[6] * X + p.R[7] * Y + p.R[8] * Z + p.t[2];
-    double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-    double x = xc * z, y = yc * z;
-    u = (float)(x * cam.f + cam.cx);
-    v = (float)(y * cam.f + cam.cy);
-}
-
-// (cell i = y * Wo + x; the loops that walk the cells at a fixed stride carry (y, x) along instead of dividing: CellWalk)
-__device__ __forceinline__ float cell_err_at(const Pose &p, const Coords &co, int i, int y, int x, const Cam &cam)
-{
-    double X, Y, Z;
-    co.fetch(i, X, Y, Z);
-    float u, v;
-    project(p, X, Y, Z, cam, u, v);
-    float px = (float)(x * cam.sub + cam.sub / 2), py = (float)(y * cam.sub + cam.sub / 2);
-    float dx = px - u, dy = py - v;
-    double n = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
-    float a = (float)n;
-    return (cam.maxReproj < a) ? cam.maxReproj : a;
-}
 
 // row / column of a cell index that advances by a constant stride: one division at the start, then adds and compares (an integer
 // division by the run-time grid width is ~25 of a cell's ~160 instructions in the scoring loop)
@@ -180,229 +79,6 @@ struct CellWalk {
     __device__ __forceinline__ CellWalk(int i0, int stride, int wo) : y(i0 / wo), x(i0 - (i0 / wo) * wo), sy(stride / wo), sx(stride - (stride / wo) * wo), Wo(wo) {}
     __device__ __forceinline__ void step() { y += sy; x += sx; if (x >= Wo) { x -= Wo; ++y; } }
 };
-
-__device__ __forceinline__ float cell_err(const Pose &p, const Coords &co, int i, const Cam &cam)
-{
-    int y = i / cam.Wo, x = i - y * cam.Wo;
-    double X, Y, Z;
-    co.fetch(i, X, Y, Z);
-    float u, v;
-    project(p, X, Y, Z, cam, u, v);
-    float px = (float)(x * cam.sub + cam.sub / 2), py = (float)(y * cam.sub + cam.sub / 2);
-    float dx = px - u, dy = py - v;
-    double n = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
-    float a = (float)n;
-    return (cam.maxReproj < a) ? cam.maxReproj : a;
-}
-
-// ------------------------------------------------------------------------------ quartic (Ferrari)
-
-__device__ __forceinline__ double cubic_pos_root(double c2, double c1, double c0)
-{
-    double m = fabs(c2);
-    if (fabs(c1) > m) m = fabs(c1);
-    if (fabs(c0) > m) m = fabs(c0);
-    double lo = 0.0, hi = 1.0 + m;
-    double z = hi;
-    for (int it = 0; it < 128; ++it) {
-        double g = ((z + c2) * z + c1) * z + c0;
-        double dg = (3.0 * z + 2.0 * c2) * z + c1;
-        if (g > 0.0) hi = z; else lo = z;
-        if (g == 0.0) break;
-        double zn = z - g / dg;
-        if (!(zn > lo && zn < hi)) zn = 0.5 * (lo + hi);
-        if (zn == z || !(hi > lo)) break;
-        z = zn;
-    }
-    return z;
-}
-
-__device__ __forceinline__ bool quadratic(double b, double c, double &r0, double &r1)
-{
-    double disc = b * b - 4.0 * c;
-    if (!(disc >= 0.0)) return false;
-    double sq = sqrt(disc);
-    double q = (b >= 0.0) ? -0.5 * (b + sq) : -0.5 * (b - sq);
-    if (q != 0.0) { r0 = q; r1 = c / q; }
-    else { r0 = 0.0; r1 = 0.0; }
-    return true;
-}
-
-// roots land in four fixed slots (valid mask bit i) in the order the oracle appends them
-__device__ __forceinline__ unsigned quartic(double A4, double A3, double A2, double A1, double A0,
-                                            double &x0, double &x1, double &x2, double &x3)
-{
-    double a = A3 / A4, b = A2 / A4, c = A1 / A4, d = A0 / A4;
-    double a2 = a * a;
-    double p = b - 0.375 * a2;
-    double q = c - 0.5 * a * b + 0.125 * a2 * a;
-    double r = d - 0.25 * a * c + 0.0625 * a2 * b - (3.0 / 256.0) * a2 * a2;
-    double shift = -0.25 * a;
-    unsigned mask = 0;
-    x0 = x1 = x2 = x3 = 0.0;
-    double z0 = cubic_pos_root(2.0 * p, p * p - 4.0 * r, -(q * q));
-    if (z0 > 0.0) {
-        double s = sqrt(z0);
-        double h = 0.5 * (p + z0);
-        double g = 0.5 * q / s;
-        double r0, r1;
-        if (quadratic(s, h - g, r0, r1)) { x0 = r0 + shift; x1 = r1 + shift; mask |= 3u; }
-        if (quadratic(-s, h + g, r0, r1)) { x2 = r0 + shift; x3 = r1 + shift; mask |= 12u; }
-    } else {
-        double w0, w1;
-        if (quadratic(p, r, w0, w1)) {
-            if (w0 >= 0.0) { double y = sqrt(w0); x0 = y + shift; x1 = -y + shift; mask |= 3u; }
-            if (w1 >= 0.0) { double y = sqrt(w1); x2 = y + shift; x3 = -y + shift; mask |= 12u; }
-        }
-    }
-    return mask;
-}
-
-// ------------------------------------------------------------------------------ P3P + 4th point
-
-struct V3 { double x, y, z; };
-
-__device__ __forceinline__ V3 cross3(V3 a, V3 b)
-{
-    return V3{ a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x };
-}
-
-struct Frame { V3 e1, e2, e3; };
-
-__device__ __forceinline__ bool frame_of(V3 A, V3 B, V3 C, Frame &F)
-{
-    V3 ab{ B.x - A.x, B.y - A.y, B.z - A.z };
-    V3 ac{ C.x - A.x, C.y - A.y, C.z - A.z };
-    double n1 = sqrt(ab.x * ab.x + ab.y * ab.y + ab.z * ab.z);
-    if (!(n1 > 0.0)) return false;
-    F.e1 = V3{ ab.x / n1, ab.y / n1, ab.z / n1 };
-    V3 nn = cross3(ab, ac);
-    double n3 = sqrt(nn.x * nn.x + nn.y * nn.y + nn.z * nn.z);
-    if (!(n3 > 0.0)) return false;
-    F.e3 = V3{ nn.x / n3, nn.y / n3, nn.z / n3 };
-    F.e2 = cross3(F.e3, F.e1);
-    return true;
-}
-
-__device__ __forceinline__ V3 bearing(double u, double v, const Cam &cam)
-{
-    double mx = (u - cam.cx) / cam.f, my = (v - cam.cy) / cam.f;
-    double nrm = sqrt(mx * mx + my * my + 1.0);
-    return V3{ mx / nrm, my / nrm, 1.0 / nrm };
-}
-
-// one candidate root of the quartic -> pose + 4th-point error; false if the root is rejected
-__device__ __forceinline__ bool p3p_candidate(double v, double pq, double ca, double cb, double cg,
-                                              double a2, double b2, double c2,
-                                              V3 f0, V3 f1, V3 f2, V3 P0, V3 P1, V3 P2, V3 P3,
-                                              double u3, double v3, const Frame &E, const Cam &cam,
-                                              Pose &cand, double &err)
-{
-    if (!(v > 0.0)) return false;
-    double den = cg - v * ca;
-    if (!(den != 0.0)) return false;
-    double u = ((pq - 1.0) * v * v - 2.0 * pq * cb * v + 1.0 + pq) / (2.0 * den);
-    if (!(u > 0.0)) return false;
-    double w = 1.0 + v * v - 2.0 * v * cb;
-    if (!(w > 0.0)) return false;
-    double s1 = sqrt(b2 / w), s2 = u * s1, s3 = v * s1;
-    for (int it = 0; it < 2; ++it) {
-        double F1 = s2 * s2 + s3 * s3 - 2.0 * s2 * s3 * ca - a2;
-        double F2 = s1 * s1 + s3 * s3 - 2.0 * s1 * s3 * cb - b2;
-        double F3 = s1 * s1 + s2 * s2 - 2.0 * s1 * s2 * cg - c2;
-        double j12 = 2.0 * s2 - 2.0 * s3 * ca, j13 = 2.0 * s3 - 2.0 * s2 * ca;
-        double j21 = 2.0 * s1 - 2.0 * s3 * cb, j23 = 2.0 * s3 - 2.0 * s1 * cb;
-        double j31 = 2.0 * s1 - 2.0 * s2 * cg, j32 = 2.0 * s2 - 2.0 * s1 * cg;
-        double det = j12 * j23 * j31 + j13 * j21 * j32;
-        if (!(det != 0.0)) break;
-        double dx1 = (F1 * (-(j23 * j32)) - j12 * (-(j23 * F3)) + j13 * (F2 * j32)) / det;
-        double dx2 = (-(F1 * (-(j23 * j31))) + j13 * (j21 * F3 - F2 * j31)) / det;
-        double dx3 = (-(j12 * (j21 * F3 - F2 * j31)) + F1 * (j21 * j32)) / det;
-        s1 -= dx1; s2 -= dx2; s3 -= dx3;
-    }
-    if (!(s1 > 0.0) || !(s2 > 0.0) || !(s3 > 0.0)) return false;
-    V3 C0{ s1 * f0.x, s1 * f0.y, s1 * f0.z };
-    V3 C1{ s2 * f1.x, s2 * f1.y, s2 * f1.z };
-    V3 C2{ s3 * f2.x, s3 * f2.y, s3 * f2.z };
-    Frame D;
-    if (!frame_of(C0, C1, C2, D)) return false;
-    // R[i][j] = d1[i] e1[j] + d2[i] e2[j] + d3[i] e3[j]
-    cand.R[0] = D.e1.x * E.e1.x + D.e2.x * E.e2.x + D.e3.x * E.e3.x;
-    cand.R[1] = D.e1.x * E.e1.y + D.e2.x * E.e2.y + D.e3.x * E.e3.y;
-    cand.R[2] = D.e1.x * E.e1.z + D.e2.x * E.e2.z + D.e3.x * E.e3.z;
-    cand.R[3] = D.e1.y * E.e1.x + D.e2.y * E.e2.x + D.e3.y * E.e3.x;
-    cand.R[4] = D.e1.y * E.e1.y + D.e2.y * E.e2.y + D.e3.y * E.e3.y;
-    cand.R[5] = D.e1.y * E.e1.z + D.e2.y * E.e2.z + D.e3.y * E.e3.z;
-    cand.R[6] = D.e1.z * E.e1.x + D.e2.z * E.e2.x + D.e3.z * E.e3.x;
-    cand.R[7] = D.e1.z * E.e1.y + D.e2.z * E.e2.y + D.e3.z * E.e3.y;
-    cand.R[8] = D.e1.z * E.e1.z + D.e2.z * E.e2.z + D.e3.z * E.e3.z;
-    double pwx = (P0.x + P1.x + P2.x) / 3.0, pwy = (P0.y + P1.y + P2.y) / 3.0, pwz = (P0.z + P1.z + P2.z) / 3.0;
-    double pcx = (C0.x + C1.x + C2.x) / 3.0, pcy = (C0.y + C1.y + C2.y) / 3.0, pcz = (C0.z + C1.z + C2.z) / 3.0;
-    cand.t[0] = pcx - (cand.R[0] * pwx + cand.R[1] * pwy + cand.R[2] * pwz);
-    cand.t[1] = pcy - (cand.R[3] * pwx + cand.R[4] * pwy + cand.R[5] * pwz);
-    cand.t[2] = pcz - (cand.R[6] * pwx + cand.R[7] * pwy + cand.R[8] * pwz);
-    double xc = cand.R[0] * P3.x + cand.R[1] * P3.y + cand.R[2] * P3.z + cand.t[0];
-    double yc = cand.R[3] * P3.x + cand.R[4] * P3.y + cand.R[5] * P3.z + cand.t[1];
-    double zc = cand.R[6] * P3.x + cand.R[7] * P3.y + cand.R[8] * P3.z + cand.t[2];
-    double up = cam.cx + cam.f * xc / zc, vp = cam.cy + cam.f * yc / zc;
-    err = (up - u3) * (up - u3) + (vp - v3) * (vp - v3);
-    return true;
-}
-
-__device__ __forceinline__ void pose_identity(Pose &p)
-{
-    p.R[0] = 1.0; p.R[1] = 0.0; p.R[2] = 0.0;
-    p.R[3] = 0.0; p.R[4] = 1.0; p.R[5] = 0.0;
-    p.R[6] = 0.0; p.R[7] = 0.0; p.R[8] = 1.0;
-    p.t[0] = 0.0; p.t[1] = 0.0; p.t[2] = 0.0;
-}
-
-// cv::solvePnP(SOLVEPNP_P3P) call-site contract (dsacstar_util.h:185-193): 3 points solve, 4th selects
-__device__ bool p3p(V3 P0, V3 P1, V3 P2, V3 P3, const double (&uv)[4][2], const Cam &cam, Pose &out)
-{
-    V3 f0 = bearing(uv[0][0], uv[0][1], cam);
-    V3 f1 = bearing(uv[1][0], uv[1][1], cam);
-    V3 f2 = bearing(uv[2][0], uv[2][1], cam);
-    double ca = f1.x * f2.x + f1.y * f2.y + f1.z * f2.z;
-    double cb = f0.x * f2.x + f0.y * f2.y + f0.z * f2.z;
-    double cg = f0.x * f1.x + f0.y * f1.y + f0.z * f1.z;
-    double d0, d1, d2;
-    d0 = P1.x - P2.x; d1 = P1.y - P2.y; d2 = P1.z - P2.z;
-    double a2 = d0 * d0 + d1 * d1 + d2 * d2;
-    d0 = P0.x - P2.x; d1 = P0.y - P2.y; d2 = P0.z - P2.z;
-    double b2 = d0 * d0 + d1 * d1 + d2 * d2;
-    d0 = P0.x - P1.x; d1 = P0.y - P1.y; d2 = P0.z - P1.z;
-    double c2 = d0 * d0 + d1 * d1 + d2 * d2;
-    if (!(a2 > 0.0) || !(b2 > 0.0) || !(c2 > 0.0)) return false;
-    Frame E;
-    if (!frame_of(P0, P1, P2, E)) return false;
-
-    double pq = (a2 - c2) / b2, qq = (a2 + c2) / b2;
-    double c2b = c2 / b2, a2b = a2 / b2;
-    double A4 = (pq - 1.0) * (pq - 1.0) - 4.0 * c2b * ca * ca;
-    double A3 = 4.0 * (pq * (1.0 - pq) * cb - (1.0 - qq) * ca * cg + 2.0 * c2b * ca * ca * cb);
-    double A2 = 2.0 * (pq * pq - 1.0 + 2.0 * pq * pq * cb * cb + 2.0 * ((b2 - c2) / b2) * ca * ca
-                       - 4.0 * qq * ca * cb * cg + 2.0 * ((b2 - a2) / b2) * cg * cg);
-    double A1 = 4.0 * (-pq * (1.0 + pq) * cb + 2.0 * a2b * cg * cg * cb - (1.0 - qq) * ca * cg);
-    double A0 = (1.0 + pq) * (1.0 + pq) - 4.0 * a2b * cg * cg;
-    if (!(A4 != 0.0) || A4 != A4) return false;
-
-    double x0, x1, x2, x3;
-    unsigned mask = quartic(A4, A3, A2, A1, A0, x0, x1, x2, x3);
-    bool found = false;
-    double best = 0.0;
-#pragma unroll 1
-    for (int ri = 0; ri < 4; ++ri) {
-        if (!((mask >> ri) & 1u)) continue;
-        double v = (ri == 0) ? x0 : (ri == 1) ? x1 : (ri == 2) ? x2 : x3;
-        Pose cand;
-        double e;
-        if (!p3p_candidate(v, pq, ca, cb, cg, a2, b2, c2, f0, f1, f2, P0, P1, P2, P3,
-                           uv[3][0], uv[3][1], E, cam, cand, e)) continue;
-        if (!found || e < best) { best = e; out = cand; found = true; }
-    }
-    return found;
-}
 
 // one sampling try (dsacstar_util.h:159-219); returns accept flag, pose = try result (identity if P3P failed)
 __device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, uint32_t hyp, uint32_t t,
@@ -422,15 +98,15 @@ __device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, 
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
         co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
     }
-    if (!p3p(P[0], P[1], P[2], P[3], uv, cam, pose)) {
-        pose_identity(pose);
+    if (!p3p(P[0], P[1], P[2], P[3], uv, &cam, &pose)) {
+        pose_identity(&pose);
         return false;
     }
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float u, v;
-        project(pose, P[j].x, P[j].y, P[j].z, cam, u, v);
+        project(&pose, P[j].x, P[j].y, P[j].z, &cam, &u, &v);
         float dx = px[j] - u, dy = py[j] - v;
         double n = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
         if (ok && !(n < (double)cam.thr)) ok = false;
@@ -517,106 +193,6 @@ __device__ __forceinline__ void block_reduce28(double (&a)[28], double *red, int
     }
 }
 
-__device__ __forceinline__ bool solve6(const double (&ne)[28], double lambda, double (&d)[6])
-{
-    double A[6][6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r)
-#pragma unroll
-            for (int c = r; c < 6; ++c) { A[r][c] = ne[k]; A[c][r] = ne[k]; ++k; }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; ++r) A[r][r] = A[r][r] * (1.0 + lambda);
-    double L[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) L[i][j] = 0.0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double s = A[j][j];
-#pragma unroll
-        for (int m = 0; m < j; ++m) s -= L[j][m] * L[j][m];
-        if (!(s > 0.0)) ok = false;
-        double ljj = sqrt(s);
-        L[j][j] = ljj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i][j];
-#pragma unroll
-            for (int m = 0; m < j; ++m) v -= L[i][m] * L[j][m];
-            L[i][j] = v / ljj;
-        }
-    }
-    if (!ok) return false;
-    double yv[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = ne[21 + i];
-#pragma unroll
-        for (int m = 0; m < i; ++m) v -= L[i][m] * yv[m];
-        yv[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = yv[i];
-#pragma unroll
-        for (int m = i + 1; m < 6; ++m) v -= L[m][i] * d[m];
-        d[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (!(d[i] == d[i]) || fabs(d[i]) > 1.0e300) ok = false;
-    return ok;
-}
-
-__device__ __forceinline__ void apply_step(const Pose &prev, const double (&d)[6], Pose &out)
-{
-    double wx = -d[0], wy = -d[1], wz = -d[2];
-    double th2 = wx * wx + wy * wy + wz * wz;
-    double th = sqrt(th2);
-    double E[9];
-    if (!(th > 1.0e-300)) {
-        E[0] = 1.0; E[1] = -wz; E[2] = wy;
-        E[3] = wz;  E[4] = 1.0; E[5] = -wx;
-        E[6] = -wy; E[7] = wx;  E[8] = 1.0;
-    } else {
-        double s, c;
-        det_sincos(th, s, c);
-        double kx = wx / th, ky = wy / th, kz = wz / th;
-        double c1 = 1.0 - c;
-        E[0] = c + c1 * kx * kx;      E[1] = c1 * kx * ky - s * kz; E[2] = c1 * kx * kz + s * ky;
-        E[3] = c1 * kx * ky + s * kz; E[4] = c + c1 * ky * ky;      E[5] = c1 * ky * kz - s * kx;
-        E[6] = c1 * kx * kz - s * ky; E[7] = c1 * ky * kz + s * kx; E[8] = c + c1 * kz * kz;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            out.R[3 * i + j] = E[3 * i] * prev.R[j] + E[3 * i + 1] * prev.R[3 + j] + E[3 * i + 2] * prev.R[6 + j];
-    out.t[0] = prev.t[0] - d[3];
-    out.t[1] = prev.t[1] - d[4];
-    out.t[2] = prev.t[2] - d[5];
-}
-
-__device__ __forceinline__ double lambda_of(int lg)
-{
-    // 10^lg for lg in [-16, 16]; decimal literals, identical constants on host and device
-    switch (lg) {
-        case -16: return 1e-16; case -15: return 1e-15; case -14: return 1e-14; case -13: return 1e-13;
-        case -12: return 1e-12; case -11: return 1e-11; case -10: return 1e-10; case -9: return 1e-9;
-        case -8: return 1e-8; case -7: return 1e-7; case -6: return 1e-6; case -5: return 1e-5;
-        case -4: return 1e-4; case -3: return 1e-3; case -2: return 1e-2; case -1: return 1e-1;
-        case 0: return 1e0; case 1: return 1e1; case 2: return 1e2; case 3: return 1e3; case 4: return 1e4;
-        case 5: return 1e5; case 6: return 1e6; case 7: return 1e7; case 8: return 1e8; case 9: return 1e9;
-        case 10: return 1e10; case 11: return 1e11; case 12: return 1e12; case 13: return 1e13;
-        case 14: return 1e14; case 15: return 1e15; default: return 1e16;
-    }
-}
-
 struct Params {
     const float *coords; int64_t sb, sc, sy, sx;
     float *outPoses;
@@ -663,7 +239,7 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
         {
             int j = 0;
             for (int i = tid; i < N; i += kThreads, ++j) {
-                float e = cell_err(pose, co, i, cam);
+                float e = co.err(pose, i, cam);
                 if (e < cam.thr) inl |= (1ull << j);
             }
         }
@@ -688,14 +264,14 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
             double d[6];
             prev = cur;
             if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
-            apply_step(prev, d, cur);
+            apply_step(&prev, d, &cur);
             double prevErr = ne[27];
             normal_eq_thread(co, cam, cur, inl, tid, neNew);
             block_reduce28(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
             while (neNew[27] > prevErr) {
                 if (++lg <= 16) {
                     if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
-                    apply_step(prev, d, cur);
+                    apply_step(&prev, d, &cur);
                     normal_eq_thread(co, cam, cur, inl, tid, neNew);
                     block_reduce28(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
                 } else break;
@@ -767,7 +343,7 @@ void xl_dsac_forward_kernel(Params P)
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
 
     const uint64_t imageIdx = P.image0 + (uint64_t)b * P.imageStride;
-    const uint64_t imageKey = mix64(P.seed + 0x9e3779b97f4a7c15ULL * (imageIdx + 1));
+    const uint64_t imageKey = image_key(P.seed, imageIdx);
 
     // ---- sample + score: this wave's hypotheses
     double bestScore = 0.0;
@@ -787,7 +363,7 @@ void xl_dsac_forward_kernel(Params P)
             int cc[4] = { 0, 0, 0, 0 };
             bool ok = false;
             if (t < P.maxTries) ok = sample_try(co, cam, imageKey, (uint32_t)h, t, p, cc);
-            else pose_identity(p);
+            else pose_identity(&p);
             unsigned long long m = __ballot(ok);
             int src;
             if (m != 0ull) { src = __ffsll((long long)m) - 1; triesUsed = (int)t0 + src + 1; }
@@ -809,10 +385,10 @@ void xl_dsac_forward_kernel(Params P)
         for (; i + 64 < N; i += 128) {
             float e0, e1;
             if (P.cellWalk) {
-                e0 = cell_err_at(pose, co, i, w0.y, w0.x, cam); e1 = cell_err_at(pose, co, i + 64, w1.y, w1.x, cam);
+                e0 = co.err(pose, i, w0.y, w0.x, cam); e1 = co.err(pose, i + 64, w1.y, w1.x, cam);
                 w0.step(); w1.step();
             } else {
-                e0 = cell_err(pose, co, i, cam); e1 = cell_err(pose, co, i + 64, cam);
+                e0 = co.err(pose, i, cam); e1 = co.err(pose, i + 64, cam);
             }
             double st0 = (double)(beta * (e0 - cam.thr)), st1 = (double)(beta * (e1 - cam.thr));
             st0 = 1.0 / (1.0 + det_exp(-st0));
@@ -821,7 +397,7 @@ void xl_dsac_forward_kernel(Params P)
             acc += 1.0 - st1;
         }
         for (; i < N; i += 64) {
-            float e = cell_err(pose, co, i, cam);
+            float e = co.err(pose, i, cam);
             float stf = beta * (e - cam.thr);
             double st = (double)stf;
             st = 1.0 / (1.0 + det_exp(-st));
@@ -943,288 +519,8 @@ void xl_dsac_forward_kernel(Params P)
 // ============================================================================== backward_rgb
 // dsacstar_rgb_backward (dsacstar.cpp:200-483): expected pose loss over the soft-max distribution of the hypotheses
 // and its gradient w.r.t. the scene coordinates (path I through the refined poses, path II through the scores).
-// Every device function below mirrors oracle/dsac_bwd_oracle.c operation for operation (same order, no contraction),
-// so the two produce identical bits; reference line numbers are given there.
-
-constexpr double kProbThresh = 0.001;          // dsacstar_derivative.h:36
-constexpr double kEps = 0.00000001;            // dsacstar_util.h:45
-constexpr double kMaxLoss = 10000000.0;        // dsacstar_loss.h:35
-constexpr double kPiRef = 3.1415926;           // dsacstar_util.h:46
-constexpr double kCvPi = 3.1415926535897932384626433832795;
-constexpr double kDblEps = 2.2204460492503131e-16;
-
-__device__ double det_atan2(double y, double x)
-{
-    if (x == 0.0 && y == 0.0) return 0.0;
-    double n = sqrt(x * x + y * y);
-    double cn = x / n, sn = y / n;
-    double ax = fabs(x), ay = fabs(y);
-    double t;
-    if (ay <= ax) { double a = ay / ax; t = a / (1.0 + 0.28 * a * a); }
-    else { double a = ax / ay; t = 1.5707963267948966 - a / (1.0 + 0.28 * a * a); }
-    if (x < 0.0) t = 3.141592653589793 - t;
-    if (y < 0.0) t = -t;
-    for (int it = 0; it < 3; ++it) {
-        double s, c;
-        det_sincos(t, s, c);
-        double d = sn * c - cn * s;
-        double d2 = d * d;
-        t = t + d * (1.0 + d2 * (1.0 / 6.0 + d2 * (3.0 / 40.0)));
-    }
-    return t;
-}
-
-__device__ double det_acos(double v) { return det_atan2(sqrt((1.0 - v) * (1.0 + v)), v); }
-
-__device__ void log_so3(const double *R, double *r)
-{
-    double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    double c = (R[0] + R[4] + R[8] - 1.0) * 0.5;
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    double theta = det_atan2(s, c);
-    if (s < 1e-5) {
-        if (c > 0.0) { r[0] = 0.0; r[1] = 0.0; r[2] = 0.0; return; }
-        double t;
-        t = (R[0] + 1.0) * 0.5; rx = sqrt(t > 0.0 ? t : 0.0);
-        t = (R[4] + 1.0) * 0.5; ry = sqrt(t > 0.0 ? t : 0.0) * (R[1] < 0.0 ? -1.0 : 1.0);
-        t = (R[8] + 1.0) * 0.5; rz = sqrt(t > 0.0 ? t : 0.0) * (R[2] < 0.0 ? -1.0 : 1.0);
-        if (fabs(rx) < fabs(ry) && fabs(rx) < fabs(rz) && ((R[5] > 0.0) != (ry * rz > 0.0))) rz = -rz;
-        theta = theta / sqrt(rx * rx + ry * ry + rz * rz);
-        r[0] = rx * theta; r[1] = ry * theta; r[2] = rz * theta;
-        return;
-    }
-    double vth = (1.0 / (2.0 * s)) * theta;
-    r[0] = rx * vth; r[1] = ry * vth; r[2] = rz * vth;
-}
-
-__device__ void exp_so3(const double *r, double *R)
-{
-    double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (th < kDblEps) {
-        for (int i = 0; i < 9; ++i) R[i] = 0.0;
-        R[0] = 1.0; R[4] = 1.0; R[8] = 1.0;
-        return;
-    }
-    double s, c;
-    det_sincos(th, s, c);
-    double c1 = 1.0 - c, ith = 1.0 / th;
-    double kx = r[0] * ith, ky = r[1] * ith, kz = r[2] * ith;
-    R[0] = c + c1 * kx * kx;      R[1] = c1 * kx * ky - s * kz; R[2] = c1 * kx * kz + s * ky;
-    R[3] = c1 * kx * ky + s * kz; R[4] = c + c1 * ky * ky;      R[5] = c1 * ky * kz - s * kx;
-    R[6] = c1 * kx * kz - s * ky; R[7] = c1 * ky * kz + s * kx; R[8] = c + c1 * kz * kz;
-}
-
-// dR[(3a+b)*3 + c] = d R[a][b] / d r_c
-__device__ void rodrigues_jac(const double *r, double *dR)
-{
-    double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    for (int i = 0; i < 27; ++i) dR[i] = 0.0;
-    if (th < kDblEps) {
-        dR[5 * 3 + 0] = -1.0; dR[7 * 3 + 0] = 1.0;
-        dR[2 * 3 + 1] = 1.0;  dR[6 * 3 + 1] = -1.0;
-        dR[1 * 3 + 2] = -1.0; dR[3 * 3 + 2] = 1.0;
-        return;
-    }
-    double s, c;
-    det_sincos(th, s, c);
-    double c1 = 1.0 - c, ith = 1.0 / th;
-    double k[3] = { r[0] * ith, r[1] * ith, r[2] * ith };
-    for (int i = 0; i < 3; ++i) {
-        double dk[3];
-        for (int j = 0; j < 3; ++j) dk[j] = ((i == j ? 1.0 : 0.0) - k[i] * k[j]) * ith;
-        double ski = s * k[i], cki = c * k[i];
-        double K[9] = { 0.0, -k[2], k[1], k[2], 0.0, -k[0], -k[1], k[0], 0.0 };
-        double dK[9] = { 0.0, -dk[2], dk[1], dk[2], 0.0, -dk[0], -dk[1], dk[0], 0.0 };
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                double v = ski * (k[a] * k[b]) + c1 * (dk[a] * k[b] + k[a] * dk[b]) + cki * K[3 * a + b] + s * dK[3 * a + b];
-                if (a == b) v -= ski;
-                dR[(3 * a + b) * 3 + i] = v;
-            }
-    }
-}
-
-// row of d max(|proj - pt|, EPS) / d (rvec, tvec), zero above maxReproj; returns the error
-__device__ double resid_row(const Pose &p, const double *dR, double X, double Y, double Z, float px, float py,
-                            const Cam &cam, double (&J6)[6])
-{
-    double qx = p.R[0] * X + p.R[1] * Y + p.R[2] * Z;
-    double qy = p.R[3] * X + p.R[4] * Y + p.R[5] * Z;
-    double qz = p.R[6] * X + p.R[7] * Y + p.R[8] * Z;
-    double xc = qx + p.t[0], yc = qy + p.t[1], zc = qz + p.t[2];
-    double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-    double xn = xc * z, yn = yc * z;
-    float uf = (float)(xn * cam.f + cam.cx), vf = (float)(yn * cam.f + cam.cy);
-    float dxf = uf - px, dyf = vf - py;
-    double err = sqrt((double)dxf * (double)dxf + (double)dyf * (double)dyf);
-    if (err < kEps) err = kEps;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) J6[i] = 0.0;
-    if (err > (double)cam.maxReproj) return err;
-    double nx = 1.0 / err * (double)dxf, ny = 1.0 / err * (double)dyf;
-    double fa = cam.f * z;
-    double fc = -(fa * xn);
-    double fd = -(fa * yn);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double dX = dR[0 * 3 + c] * X + dR[1 * 3 + c] * Y + dR[2 * 3 + c] * Z;
-        double dY = dR[3 * 3 + c] * X + dR[4 * 3 + c] * Y + dR[5 * 3 + c] * Z;
-        double dZ = dR[6 * 3 + c] * X + dR[7 * 3 + c] * Y + dR[8 * 3 + c] * Z;
-        double ju = fa * dX + fc * dZ, jv = fa * dY + fd * dZ;
-        J6[c] = nx * ju + ny * jv;
-    }
-    J6[3] = nx * fa;
-    J6[4] = ny * fa;
-    J6[5] = nx * fc + ny * fd;
-    return err;
-}
-
-// dProjectdObj, dsacstar_derivative.h:51-106
-__device__ void dproject_dobj(const Pose &p, double X, double Y, double Z, float ptx, float pty, const Cam &cam,
-                              double (&out)[3])
-{
-    out[0] = 0.0; out[1] = 0.0; out[2] = 0.0;
-    double ox = p.R[0] * X + p.R[1] * Y + p.R[2] * Z + p.t[0];
-    double oy = p.R[3] * X + p.R[4] * Y + p.R[5] * Z + p.t[1];
-    double oz = p.R[6] * X + p.R[7] * Y + p.R[8] * Z + p.t[2];
-    if (fabs(oz) < kEps) return;
-    double px = cam.f * ox / oz + cam.cx;
-    double py = cam.f * oy / oz + cam.cy;
-    double ex = (double)ptx - px, ey = (double)pty - py;
-    double err = sqrt(ex * ex + ey * ey);
-    if (err > (double)cam.maxReproj) return;
-    err += kEps;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        double pxd = cam.f * p.R[k] / oz - cam.f * ox / oz / oz * p.R[6 + k];
-        double pyd = cam.f * p.R[3 + k] / oz - cam.f * oy / oz / oz * p.R[6 + k];
-        out[k] = 0.5 / err * (2.0 * ex * -pxd + 2.0 * ey * -pyd);
-    }
-}
-
-// pseudo-inverse of a symmetric PSD 6x6: cyclic Jacobi, 12 sweeps, eigenvalues <= 2 eps sum|w| dropped
-__device__ void pinv6(const double *A_, double *Ainv)
-{
-    double A[6][6], V[6][6];
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) { A[i][j] = A_[6 * i + j]; V[i][j] = (i == j) ? 1.0 : 0.0; }
-    for (int sweep = 0; sweep < 12; ++sweep)
-        for (int p = 0; p < 5; ++p)
-            for (int q = p + 1; q < 6; ++q) {
-                double apq = A[p][q];
-                if (apq == 0.0) continue;
-                double tau = (A[q][q] - A[p][p]) / (2.0 * apq);
-                double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-                for (int k = 0; k < 6; ++k) {
-                    double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < 6; ++k) {
-                    double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < 6; ++k) {
-                    double vkp = V[k][p], vkq = V[k][q];
-                    V[k][p] = c * vkp - s * vkq;
-                    V[k][q] = s * vkp + c * vkq;
-                }
-            }
-    double sum = 0.0;
-    for (int i = 0; i < 6; ++i) sum += fabs(A[i][i]);
-    double thr = sum * (2.0 * kDblEps);
-    double wi[6];
-    for (int i = 0; i < 6; ++i) wi[i] = (fabs(A[i][i]) > thr) ? 1.0 / A[i][i] : 0.0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double v = 0.0;
-            for (int k = 0; k < 6; ++k) v += V[i][k] * wi[k] * V[j][k];
-            Ainv[6 * i + j] = v;
-        }
-}
-
-struct Gt { double Rc2w[9]; double C[3]; double R2[9]; double t2[3]; };
-
-__device__ void gt_from_pose16(const float *gt16, Gt &g)
-{
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) g.Rc2w[3 * i + j] = (double)gt16[4 * i + j];
-        g.C[i] = (double)gt16[4 * i + 3];
-    }
-    double Rt[9], r2[3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) Rt[3 * i + j] = g.Rc2w[3 * j + i];
-    log_so3(Rt, r2);
-    exp_so3(r2, g.R2);
-    for (int i = 0; i < 3; ++i)
-        g.t2[i] = -(g.R2[3 * i] * g.C[0] + g.R2[3 * i + 1] * g.C[1] + g.R2[3 * i + 2] * g.C[2]);
-}
-
-__device__ double pose_loss(const Pose &est, const Gt &g, double wRot, double wTrans, double cut)
-{
-    double trace = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k) trace += g.Rc2w[3 * i + k] * est.R[3 * k + i];
-    trace = trace > 3.0 ? 3.0 : (trace < -1.0 ? -1.0 : trace);
-    double rotErr = 180.0 * det_acos((trace - 1.0) / 2.0) / kPiRef;
-    double d2 = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        double c1 = -(est.R[i] * est.t[0] + est.R[3 + i] * est.t[1] + est.R[6 + i] * est.t[2]);
-        double d = c1 - g.C[i];
-        d2 += d * d;
-    }
-    double tErr = sqrt(d2);
-    double loss = wRot * rotErr + wTrans * tErr;
-    if (loss > cut) loss = sqrt(cut * loss);
-    return loss < kMaxLoss ? loss : kMaxLoss;
-}
-
-__device__ void dloss(const Pose &est, const double *dR, const Gt &g, double wRot, double wTrans, double cut,
-                      double (&jac)[6])
-{
-    for (int i = 0; i < 6; ++i) jac[i] = 0.0;
-    const double *R1 = est.R, *R2 = g.R2;
-    double trace = 0.0;
-    for (int a = 0; a < 3; ++a)
-        for (int k = 0; k < 3; ++k) trace += R1[3 * a + k] * R2[3 * a + k];
-    trace = trace > 3.0 ? 3.0 : (trace < -1.0 ? -1.0 : trace);
-    double rotErr = 180.0 * det_acos((trace - 1.0) / 2.0) / kCvPi;
-    double invT1[3], invT2[3], diff[3];
-    for (int i = 0; i < 3; ++i) {
-        invT1[i] = R1[i] * est.t[0] + R1[3 + i] * est.t[1] + R1[6 + i] * est.t[2];
-        invT2[i] = R2[i] * g.t2[0] + R2[3 + i] * g.t2[1] + R2[6 + i] * g.t2[2];
-        diff[i] = invT1[i] - invT2[i];
-    }
-    double tErr = sqrt(diff[0] * diff[0] + diff[1] * diff[1] + diff[2] * diff[2]);
-    double loss = wRot * rotErr + wTrans * tErr;
-    int cutLoss = 0;
-    if (loss > cut) { loss = sqrt(loss); cutLoss = 1; }
-    if (loss > kMaxLoss) return;
-    if ((tErr + rotErr) < kEps) return;
-    double dD[3];
-    for (int i = 0; i < 3; ++i) dD[i] = diff[i] / tErr;
-    for (int j = 0; j < 3; ++j)
-        jac[3 + j] += (dD[0] * R1[j * 3 + 0] + dD[1] * R1[j * 3 + 1] + dD[2] * R1[j * 3 + 2]) * wTrans;
-    for (int c = 0; c < 3; ++c) {
-        double v = 0.0;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) v += dD[i] * est.t[j] * dR[(3 * j + i) * 3 + c];
-        jac[c] += v * wTrans;
-    }
-    double fac = 180.0 / kCvPi * -1.0 / sqrt(3.0 - trace * trace + 2.0 * trace);
-    for (int c = 0; c < 3; ++c) {
-        double v = 0.0;
-        for (int m = 0; m < 9; ++m) v += R2[m] * dR[m * 3 + c];
-        jac[c] += fac * v * wRot;
-    }
-    if (cutLoss)
-        for (int i = 0; i < 6; ++i) jac[i] *= 0.5 / loss;
-    for (int i = 0; i < 6; ++i)
-        if (!(jac[i] == jac[i]) || fabs(jac[i]) > 1.0e300) { for (int k = 0; k < 6; ++k) jac[k] = 0.0; return; }
-}
+// The per-cell and per-hypothesis derivatives are in xl_dsac_math.h (reference line numbers there); the kernels below
+// keep the order of oracle/dsac_bwd_oracle.c's reductions, so the two produce identical bits.
 
 // per-hypothesis record in global memory (doubles); the first 53 entries are the oracle's debug record
 constexpr int kRec = XL_DSAC_BWD_REC;
@@ -1290,7 +586,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     for (int i = 0; i < P.nHyp; ++i) if (i == 0 || sc[i] > maxScore) maxScore = sc[i];
     for (int i = 0; i < P.nHyp; ++i) sum += det_exp(sc[i] - maxScore);
     const double prob = det_exp(sc[h] - maxScore) / sum;
-    const bool active = !(prob < kProbThresh);
+    const bool active = !(prob < XLM_PROB_THRESH);
 
     Pose init, pose;
     load_pose(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, init);
@@ -1305,8 +601,8 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
         refine_pose(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel);
     }
     Gt gt;
-    gt_from_pose16(P.gt + (int64_t)b * 16, gt);
-    const double loss = pose_loss(pose, gt, (double)P.wRot, (double)P.wTrans, (double)P.softClamp);
+    gt_from_pose16(P.gt + (int64_t)b * 16, &gt);
+    const double loss = pose_loss(&pose, &gt, (double)P.wRot, (double)P.wTrans, (double)P.softClamp);
 
     double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
     double dLossH[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, wv[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
@@ -1318,7 +614,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
         rodrigues_jac(r0, dRi);
         log_so3(pose.R, rv);
         rodrigues_jac(rv, dRr);
-        dloss(pose, dRr, gt, (double)P.wRot, (double)P.wTrans, (double)P.softClamp, dLossH);
+        dloss(&pose, dRr, &gt, (double)P.wRot, (double)P.wTrans, (double)P.softClamp, dLossH);
         if (tid == 0)
             for (int i = 0; i < 27; ++i) { rec[kRecDRinit + i] = dRi[i]; rec[kRecDRref + i] = dRr[i]; }
         if (ro.finalInl >= 4) {
@@ -1331,7 +627,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
                 int y = i / cam.Wo, x = i - y * cam.Wo;
                 double X, Y, Z, J6[6];
                 co.fetch(i, X, Y, Z);
-                resid_row(pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), cam, J6);
+                resid_row(&pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
                 int k = 0;
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
@@ -1353,7 +649,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
                 int y = i / cam.Wo, x = i - y * cam.Wo;
                 double X, Y, Z, J6[6];
                 co.fetch(i, X, Y, Z);
-                resid_row(pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), cam, J6);
+                resid_row(&pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
                 for (int r = 0; r < 6; ++r) {
                     double u = 0.0;
                     for (int c = 0; c < 6; ++c) u += Ainv[6 * r + c] * J6[c];
@@ -1403,7 +699,7 @@ void xl_dsac_bwd_expect_kernel(BwdParams P)
     }
     for (int i = tid; i < P.nHyp; i += kThreads) {
         const double pi = rec[(int64_t)i * kRec];
-        if (pi < kProbThresh) continue;
+        if (pi < XLM_PROB_THRESH) continue;
         double g = pi * rec[(int64_t)i * kRec + 1];
         for (int j = 0; j < P.nHyp; ++j) g -= pi * rec[(int64_t)j * kRec] * rec[(int64_t)j * kRec + 1];
         rec[(int64_t)i * kRec + 5] = g;
@@ -1422,7 +718,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
     double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
-    if (rec[0] < kProbThresh) return;
+    if (rec[0] < XLM_PROB_THRESH) return;
     Cam cam;
     bwd_cam(P, b, cam);
     const int N = cam.N;
@@ -1444,12 +740,12 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
         int y = i / cam.Wo, x = i - y * cam.Wo;
         double X, Y, Z, J6[6];
         co.fetch(i, X, Y, Z);
-        float e = cell_err(init, co, i, cam);
+        float e = co.err(init, i, y, x, cam);
         float stf = beta * (e - cam.thr);
         double st = 1.0 / (1.0 + det_exp(-(double)stf));
         double dRep = -st * (1.0 - st) * (double)beta * sog;
         dRep *= (double)facf;
-        resid_row(init, dRi, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), cam, J6);
+        resid_row(&init, dRi, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
 #pragma unroll
         for (int k = 0; k < 6; ++k) a[k] += dRep * J6[k];
     }
@@ -1480,7 +776,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
         Pose sp;
         V3 Q[4];
         for (int q = 0; q < 4; ++q) { Q[q].x = (double)pts[q][0]; Q[q].y = (double)pts[q][1]; Q[q].z = (double)pts[q][2]; }
-        const bool ok = p3p(Q[0], Q[1], Q[2], Q[3], uv, cam, sp);
+        const bool ok = p3p(Q[0], Q[1], Q[2], Q[3], uv, &cam, &sp);
         double r[3] = { 0.0, 0.0, 0.0 };
         if (ok) log_so3(sp.R, r);
         double *o = sol + tid * 7;
@@ -1537,12 +833,10 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
     const float beta = 5.0f / cam.thr;
     const float facf = cam.alpha / (float)cam.Wo / (float)cam.Ho;
     const int mt = i % kThreads, mj = i / kThreads;
-    // one cell's coordinates as a 1-cell "plane" for cell_err()
-    const float cX = q[0], cY = q[P.sc], cZ = q[2 * P.sc];
     for (int h = 0; h < P.nHyp; ++h) {
         const double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
         const double prob = rec[0];
-        if (prob < kProbThresh) continue;
+        if (prob < XLM_PROB_THRESH) continue;
         Pose init, ref;
         load_pose(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, init);
         load_pose(rec + 6, ref);
@@ -1550,29 +844,20 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
         const unsigned long long m = P.masks[((int64_t)b * P.nHyp + h) * kThreads + mt];
         if (rec[3] >= 4.0 && rec[4] == 0.0 && ((m >> mj) & 1ull)) {
             double J6[6], dNdO[3];
-            resid_row(ref, rec + kRecDRref, X, Y, Z, px, py, cam, J6);
+            resid_row(&ref, rec + kRecDRref, X, Y, Z, px, py, &cam, J6);
             double s = 0.0;
             for (int k = 0; k < 6; ++k) s += J6[k] * rec[24 + k];
             s = -s;
-            dproject_dobj(ref, X, Y, Z, px, py, cam, dNdO);
+            dproject_dobj(&ref, X, Y, Z, px, py, &cam, dNdO);
             for (int k = 0; k < 3; ++k) gI[k] = s * dNdO[k];
         }
-        // clamped float error of the cell under the unrefined hypothesis (same arithmetic as cell_err)
-        float e;
-        {
-            float u, v;
-            project(init, (double)cX, (double)cY, (double)cZ, cam, u, v);
-            float dx = px - u, dy = py - v;
-            double n = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
-            float af = (float)n;
-            e = (cam.maxReproj < af) ? cam.maxReproj : af;
-        }
+        float e = cell_err(&init, X, Y, Z, y, x, &cam);            // clamped float error under the unrefined hypothesis
         float stf = beta * (e - cam.thr);
         double st = 1.0 / (1.0 + det_exp(-(double)stf));
         double dRep = -st * (1.0 - st) * (double)beta * rec[5];
         dRep *= (double)facf;
         double dPdO[3];
-        dproject_dobj(init, X, Y, Z, px, py, cam, dPdO);
+        dproject_dobj(&init, X, Y, Z, px, py, &cam, dPdO);
         double jac[3] = { dPdO[0] * dRep, dPdO[1] * dRep, dPdO[2] * dRep };
         const int32_t *cells = P.cells + ((int64_t)b * P.nHyp + h) * 4;
         for (int j = 0; j < 4; ++j)
