@@ -133,6 +133,46 @@ def forward_rgb(sceneCoordinates, outPose, ransacHypotheses, inlierThreshold, fo
     return None
 
 
+QUALITY_DOUBLES = 64                     # XL_DSAC_QUALITY_DOUBLES: doubles per row of pose_quality_batch
+# field name -> column (or columns) of a pose_quality_batch row; layout and meaning: include/crossloc_dsac.h
+QUALITY_FIELDS = {
+    "n_cells": 0, "n_inliers": 1, "soft_score": 2, "sum_err": 3, "sum_err2": 4, "sse": 5, "status": 6,
+    "sigma_px": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
+    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58), "reserved": slice(58, 64),
+}
+
+
+def pose_quality_batch(sceneCoordinates, poses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha, maxReproj,
+                       subSampling, focals=None):
+    """How far the poses of B images can be trusted: inlier statistics, JtJ of the reprojection residuals over the inliers
+    and the pose covariance, at the given pose of each image (usually what forward_rgb_batch wrote; enqueue this behind it
+    on the same stream).  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, any grid size), poses [B,4,4] float32 CUDA
+    contiguous cam->world; the other arguments as in forward_rgb_batch.  Returns a float64 CUDA tensor [B,64]
+    (QUALITY_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    _check_coords(sceneCoordinates, True)
+    if not sceneCoordinates.is_cuda or not isinstance(poses, torch.Tensor) or not poses.is_cuda:
+        raise RuntimeError("pose_quality_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
+        raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
+    dev = sceneCoordinates.device
+    if poses.device != dev:
+        raise RuntimeError("poses must be on the device of sceneCoordinates")
+    if focals is not None:
+        focals = focals.to(device=dev, dtype=torch.float32).contiguous()
+        assert focals.numel() == B
+    rows = torch.empty((B, QUALITY_DOUBLES), dtype=torch.float64, device=dev)      # (the kernel writes all 64 of every row)
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_pose_quality_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(poses), float(inlierThreshold), float(focalLength),
+            float(ppointX), float(ppointY), float(inlierAlpha), float(maxReproj), int(subSampling), _ptr(focals),
+            _ptr(rows), ctypes.c_void_p(stream))
+    _lib.check(rc)
+    return rows
+
+
 BWD_REC = 128                            # XL_DSAC_BWD_REC: doubles per hypothesis in the debug record
 
 

@@ -89,6 +89,40 @@ def accuracy_report(t_err_ls, r_err_ls, coords_error_ls=None):
     return stats, s
 
 
+def selective_accuracy(t_err, r_err, sigma_pos, keep=(1.0, 0.9, 0.75, 0.5)):
+    """Accuracy of the frames the solver itself trusts most: frames sorted by ascending predicted position uncertainty
+    `sigma_pos` (column `sigma_pos_m` of dsacstar.pose_quality_batch; NaN - no covariance - last, ties by index), and for
+    each fraction in `keep` the statistics of accuracy_report over the first ceil(keep * K) frames.  Pure numpy.
+    Returns a list of (fraction, frames kept, stats dict), one per fraction."""
+    t = np.asarray(t_err, np.float64)
+    r = np.asarray(r_err, np.float64)
+    s = np.asarray(sigma_pos, np.float64)
+    K = len(t)
+    order = np.lexsort((np.arange(K), np.where(np.isnan(s), np.inf, s), np.isnan(s)))
+    out = []
+    for frac in keep:
+        n = min(K, int(np.ceil(frac * K)))
+        idx = order[:n]
+        if n == 0:
+            out.append((float(frac), 0, None))
+            continue
+        out.append((float(frac), n, accuracy_report(t[idx], r[idx])[0]))
+    return out
+
+
+def selective_accuracy_table(t_err, r_err, sigma_pos, keep=(1.0, 0.9, 0.75, 0.5)):
+    """The text crossloc_amd.pose_quality_single_task prints under the usual report."""
+    s = "\nSelective accuracy (frames kept by ascending sigma_pos_m):"
+    s += "\n  keep  frames  median_t[m]  median_r[deg]  5m5deg  3m3deg"
+    for frac, n, st in selective_accuracy(t_err, r_err, sigma_pos, keep):
+        if st is None:
+            s += "\n  %4.0f%%  %6d  (no frames)" % (frac * 100, n)
+        else:
+            s += "\n  %4.0f%%  %6d  %11.3f  %13.3f  %5.1f%%  %5.1f%%" % (
+                frac * 100, n, st["median_t"], st["median_r"], st["5m5deg"], st["3m3deg"])
+    return s
+
+
 def scene_coords_printout(t_err_ls, r_err_ls, est_xyz_ls, coords_error_ls, testing_log=None, section="test"):
     """utils/evaluation.py:193-244 without the numpy pose dumps: prints (and appends to testing_log)."""
     coords = np.concatenate([np.asarray(c, np.float64).ravel() for c in coords_error_ls]) if len(coords_error_ls) else None
@@ -191,9 +225,12 @@ def _focal_args(focal, n):
 
 
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
-                   threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None):
+                   threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
+                   quality=False):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
     (:354), HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda, predictions [B,4,Ho,Wo]).
+    `quality=True`: the pose-quality pass (dsacstar.pose_quality_batch) is enqueued directly behind the solver on the
+    solver's stream and its rows [B,64] float64 are returned as a third value.
     `focal`: a number, or one focal length per frame.
     `scene_coords` overrides the solver input (synthetic scenes: untrained weights do not predict a scene).
     `plant` [B,3,Ho,Wo]: written into the coordinate channels of the network output after the head; the solver then
@@ -210,6 +247,10 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
                                inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
                                image0=image0, image_stride=image_stride, focals=focals)
+    if quality:
+        rows = dsacstar.pose_quality_batch(coords, poses, threshold, f0, float(image_w / 2), float(image_h / 2),
+                                           inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE, focals=focals)
+        return poses, pred, rows
     return poses, pred
 
 
@@ -262,9 +303,10 @@ class PipelinedLocalizer:
             o.record_stream(self.cnn[0])
         return pred, [ev]
 
-    def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None):
+    def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
-        synchronising the side stream)."""
+        synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
+        side stream and its rows [B,64] float64 are returned as a third value."""
         import dsacstar
         pred, events = self.forward_cnn(images, plant)
         coords = pred[:, :self.net.num_task_channel] if scene_coords is None else scene_coords
@@ -276,8 +318,14 @@ class PipelinedLocalizer:
             dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                        float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
                                        image0=image0, image_stride=image_stride)
+            if quality:
+                rows = dsacstar.pose_quality_batch(coords, poses, self.thr, self.focal, float(self.w / 2), float(self.h / 2),
+                                                   self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE)
         pred.record_stream(self.side)
         poses.record_stream(self.side)
+        if quality:
+            rows.record_stream(torch.cuda.current_stream())  # allocated on the side stream, read by the caller's after finish()
+            return poses, pred, rows
         return poses, pred
 
     def finish(self):

@@ -107,6 +107,44 @@ int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                uint32_t max_tries, void *stream, double *rec_dev);
 
+/*
+ * Per-frame pose quality (no reference counterpart): how far the pose of an image can be trusted.  A stand-alone pass over
+ * the scene coordinates at ONE given pose per image - usually the one xl_dsac_forward_rgb_batch wrote, enqueued behind it
+ * on the same stream.  One workgroup per image; coordinates are read in place through the strides, so any grid size is
+ * accepted (also those the solver refuses with XL_ERR_GRID).  Asynchronous on `stream`: no host synchronisation, no
+ * allocation.  A null pointer or a non-positive size returns XL_ERR_ARG before any HIP call.
+ *
+ *   coords_dev     [B,3,Ho,Wo] float32, strides (sb, sc, sy, sx) in elements
+ *   poses_dev      [B,16] float32 cam->world 4x4, row-major; read as the backward pass reads its ground truth (rotation
+ *                  made exactly orthonormal, then inverted to world->camera {R, t})
+ *   thr, focal, ppx, ppy, alpha, max_reproj, sub, focals_dev   as in xl_dsac_forward_rgb_batch
+ *   rows_dev       [B,XL_DSAC_QUALITY_DOUBLES] float64, one row per image:
+ *
+ *     [0]      n_cells = Ho*Wo
+ *     [1]      n_inliers: cells whose clamped float reprojection error e is < thr (the refinement's comparison)
+ *     [2]      soft-inlier score at this pose: (alpha / Wo / Ho in float) * sum over all cells of 1 - sigmoid(5/thr (e - thr))
+ *     [3],[4]  sum e, sum e^2 over the inliers
+ *     [5]      SSE = sum (ru^2 + rv^2) over the inliers, double residuals in pixels
+ *     [6]      status: 0 ok; 1 fewer than 4 inliers; 2 JtJ not positive definite; 3 a pose entry (rows 0..2) is not finite
+ *     [7]      sigma_px = sqrt(SSE / (2 n_inliers - 6))
+ *     [8]      sigma_pos_m = sqrt(trace Sigma_C)
+ *     [9]      sigma_rot_deg = sqrt(Sigma_00 + Sigma_11 + Sigma_22) * 180/pi
+ *     [10..30] JtJ over the inliers, upper triangle row-major
+ *     [31..51] Sigma = sigma_px^2 (JtJ)^-1, upper triangle row-major
+ *     [52..57] Sigma_C = A Sigma A^T, upper triangle: covariance of the camera centre C = -R^T t in world coordinates,
+ *              A = [ -R^T [t]x , -R^T ] (3x6)
+ *     [58..63] 0.0 (reserved)
+ *
+ *   Parameters of JtJ and Sigma: (wx, wy, wz, tx, ty, tz) with R' = Exp(w) R, t' = t + d on the world->camera pose, the
+ *   increment of the Levenberg-Marquardt refinement.  With status 1 or 2, [7..9] and [31..57] are NaN and the rest is valid;
+ *   with status 3 every field except [0] and [6] is NaN.
+ */
+#define XL_DSAC_QUALITY_DOUBLES 64
+int xl_dsac_pose_quality_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                               int B, int Ho, int Wo, const float *poses_dev /* [B,16] cam->world */,
+                               float thr, float focal, float ppx, float ppy, float alpha, float max_reproj, int sub,
+                               const float *focals_dev, double *rows_dev /* [B,64] */, void *stream);
+
 /* Exported for symmetry with the reference module (dsacstar.cpp:889-891); not on CrossLoc's
  * path (no call site in the reference).  They return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);

@@ -1,0 +1,142 @@
+/*
+ * tests/pose_quality_ref.c — CPU restatement of the pose-quality pass (crossloc_amd/csrc/xl_dsac_quality.hip).
+ *
+ * TEST INFRASTRUCTURE ONLY.  The per-cell and per-image arithmetic is the product's xl_dsac_quality_math.h, compiled here
+ * by gcc as C99 with -ffp-contract=off.  This file restates serially what the kernel does in parallel around it: the
+ * walk of 256 virtual threads over the cells (thread t: cells t, t + 256, ... in ascending order), the xor butterfly of
+ * each 64-lane wave and the waves added in order 0, 1, 2, 3 - the way oracle/dsac_oracle.c restates the solver's block
+ * reductions (xo_reduce28).  Bitwise GPU == this file therefore checks the kernel's orchestration and that gcc and hipcc
+ * agree on the same IEEE operations; the formulas themselves are checked by tests/test_pose_quality_cpu.py (numeric
+ * Jacobians, Monte-Carlo calibration, the oracle's score and per-cell error).
+ */
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "xl_dsac_quality_math.h"     /* crossloc_amd/csrc: shared with the kernel */
+
+#define XQ_T 256                      /* threads of the kernel's workgroup: 4 waves of 64 */
+
+static double xq_butterfly64(double p[64])
+{
+    double q[64];
+    for (int off = 32; off >= 1; off >>= 1) {
+        for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ off];
+        memcpy(p, q, sizeof(q));
+    }
+    return p[0];
+}
+
+static Cam xq_cam(int Ho, int Wo, float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub)
+{
+    Cam cam;
+    cam.f = (double)focal; cam.cx = (double)ppx; cam.cy = (double)ppy;
+    cam.thr = thr; cam.alpha = alpha; cam.maxReproj = maxReproj;
+    cam.sub = sub; cam.Ho = Ho; cam.Wo = Wo; cam.N = Ho * Wo;
+    return cam;
+}
+
+/* the kernel from its pose on: per-thread partials, canonical reduction, final step */
+static void xq_sums(const float *coords, int64_t sc, int64_t sy, int64_t sx, const Cam *cam, const Pose *pose, bool poseOk,
+                    double *s)
+{
+    double (*part)[XLQ_SUMS] = (double (*)[XLQ_SUMS])malloc(sizeof(double) * XQ_T * XLQ_SUMS);
+    const float beta = 5.0f / cam->thr;
+    for (int tid = 0; tid < XQ_T; ++tid) {
+        double *a = part[tid];
+        for (int k = 0; k < XLQ_SUMS; ++k) a[k] = 0.0;
+        if (!poseOk) continue;
+        for (int i = tid; i < cam->N; i += XQ_T) {
+            const int y = i / cam->Wo, x = i - y * cam->Wo;
+            const float *q = coords + (int64_t)y * sy + (int64_t)x * sx;
+            quality_cell(pose, (double)q[0], (double)q[sc], (double)q[2 * sc], y, x, cam, beta, a);
+        }
+    }
+    for (int k = 0; k < XLQ_SUMS; ++k) {
+        double tot = 0.0;
+        for (int w = 0; w < XQ_T / 64; ++w) {
+            double p[64];
+            for (int l = 0; l < 64; ++l) p[l] = part[w * 64 + l][k];
+            const double ws = xq_butterfly64(p);
+            tot = (w == 0) ? ws : tot + ws;
+        }
+        s[k] = tot;
+    }
+    free(part);
+}
+
+static void xq_row(const float *coords, int64_t sc, int64_t sy, int64_t sx, const Cam *cam, const Pose *pose, bool poseOk,
+                   double *row)
+{
+    double s[XLQ_SUMS];
+    xq_sums(coords, sc, sy, sx, cam, pose, poseOk, s);
+    quality_row(s, pose, cam, poseOk, row);
+}
+
+/* the row the kernel must produce for one image: float32 cam->world 4x4 in, 64 doubles out */
+int xq_pose_quality(const float *coords, int64_t sc, int64_t sy, int64_t sx, int Ho, int Wo, const float *pose16,
+                    float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *row)
+{
+    if (!coords || !pose16 || !row || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
+    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    const bool poseOk = quality_pose16_finite(pose16);
+    Pose pose;
+    if (poseOk) quality_pose_from16(pose16, &pose);
+    else pose_identity(&pose);
+    xq_row(coords, sc, sy, sx, &cam, &pose, poseOk, row);
+    return 0;
+}
+
+/* the same at a double world -> camera pose (R row-major, t): for cross-checks against the oracle's score and its
+ * refined pose (`pose1` of the debug record) */
+int xq_pose_quality_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx, int Ho, int Wo, const double *Rt12,
+                        float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *row)
+{
+    if (!coords || !Rt12 || !row || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
+    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    Pose pose;
+    for (int i = 0; i < 9; ++i) pose.R[i] = Rt12[i];
+    for (int i = 0; i < 3; ++i) pose.t[i] = Rt12[9 + i];
+    const bool poseOk = quality_pose_finite(&pose);
+    if (!poseOk) pose_identity(&pose);
+    xq_row(coords, sc, sy, sx, &cam, &pose, poseOk, row);
+    return 0;
+}
+
+/* the 32 reduced sums themselves at a double world -> camera pose (the row keeps 22 of the 28 normal-equation sums) */
+int xq_test_sums_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx, int Ho, int Wo, const double *Rt12,
+                     float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *sums32)
+{
+    if (!coords || !Rt12 || !sums32 || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
+    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    Pose pose;
+    for (int i = 0; i < 9; ++i) pose.R[i] = Rt12[i];
+    for (int i = 0; i < 3; ++i) pose.t[i] = Rt12[9 + i];
+    xq_sums(coords, sc, sy, sx, &cam, &pose, true, sums32);
+    return 0;
+}
+
+/* --- hooks for the formula tests: thin calls into the shared headers --- */
+
+/* the world -> camera pose the kernel derives from a float cam->world 4x4 */
+void xq_test_pose_from16(const float *pose16, double *Rt12)
+{
+    Pose p;
+    quality_pose_from16(pose16, &p);
+    for (int i = 0; i < 9; ++i) Rt12[i] = p.R[i];
+    for (int i = 0; i < 3; ++i) Rt12[9 + i] = p.t[i];
+}
+
+/* apply_step: out = prev (-) d, i.e. R = Exp(-d_w) R_prev, t = t_prev - d_t */
+void xq_test_apply_step(const double *Rt12, const double *d6, double *out12)
+{
+    Pose prev, out;
+    for (int i = 0; i < 9; ++i) prev.R[i] = Rt12[i];
+    for (int i = 0; i < 3; ++i) prev.t[i] = Rt12[9 + i];
+    apply_step(&prev, d6, &out);
+    for (int i = 0; i < 9; ++i) out12[i] = out.R[i];
+    for (int i = 0; i < 3; ++i) out12[9 + i] = out.t[i];
+}
+
+int xq_test_inv6(const double *ut21, double *inv36) { return quality_inv6(ut21, inv36) ? 1 : 0; }
