@@ -31,6 +31,7 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 int xl_run_bwd_op(const xl_op &op, hipStream_t st);   // xl_cnn_bwd.hip
 int xl_run_split_gemm(const xl_op &op, hipStream_t st);   // xl_gemm_split.hip
@@ -40,10 +41,6 @@ int xl_run_stem12(const xl_op &op, hipStream_t st);       // xl_stem_fused.hip
 int xl_run_s2_dgrad(const xl_op &op, hipStream_t st);     // xl_stem_dgrad.hip
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------- conv1
 
@@ -220,29 +217,12 @@ void conv1_fused_kernel(const float *__restrict__ in, const float *__restrict__ 
 // the 3 x 3 window: 16 slots = 4 pixels (x-1, x, x+1 and a fourth with zero weights) x {R, G, B, 0}; a lane's 8 values are
 // two neighbouring pixel words = one ds_read2_b64, no gather.  32 pixels of a row x 32 channels = 3 K-steps x 6 term
 // pairs = 18 MFMAs; the weight fragments (9 x 4 registers) are built once per wave.
-typedef __bf16 c1_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int c1_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int c1_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int kC1TH = 16, kC1TW = 64, kC1HH = kC1TH + 2, kC1HW = kC1TW + 4;   // 66 halo columns + 2 of zeros (slot dx = 3 of the last pixels)
 constexpr int kC1Halo = 3 * kC1HH * kC1HW * 8;                 // bytes: [plane][row][col] of 8-byte pixel words
 
-__device__ __forceinline__ unsigned c1_bf16_rn(float x)
-{
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void c1_split3(float a, unsigned &h1, unsigned &h2, unsigned &h3)
-{
-    h1 = c1_bf16_rn(a);
-    const float r1 = a - __builtin_bit_cast(float, h1 << 16);
-    h2 = c1_bf16_rn(r1);
-    h3 = c1_bf16_rn(r1 - __builtin_bit_cast(float, h2 << 16));
-}
-
 template <int PASS>
 __global__ __launch_bounds__(256)
-void conv1_mfma_kernel(const float *__restrict__ in, const c1_u32x4 *__restrict__ wfrag, const float *__restrict__ bias,
+void conv1_mfma_kernel(const float *__restrict__ in, const u32x4 *__restrict__ wfrag, const float *__restrict__ bias,
                        const float *__restrict__ coeff, float *__restrict__ out, double *__restrict__ stats,
                        int H, int W, int tilesX, int relu)
 {
@@ -260,7 +240,7 @@ void conv1_mfma_kernel(const float *__restrict__ in, const c1_u32x4 *__restrict_
     const float *img = in + (long long)n * 3 * HW;
 
     // ---- halo -> LDS, split
-    c1_u32x2 *sH = reinterpret_cast<c1_u32x2 *>(smem);
+    u32x2 *sH = reinterpret_cast<u32x2 *>(smem);
     for (int i = tid; i < kC1HH * kC1HW; i += 256) {
         const int r = i / kC1HW, c = i - r * kC1HW;
         const int y = y0 - 1 + r, x = x0 - 1 + c;
@@ -270,19 +250,19 @@ void conv1_mfma_kernel(const float *__restrict__ in, const c1_u32x4 *__restrict_
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const float v = inb ? img[ch * HW + off] : 0.f;
-            c1_split3(v, h[0][ch], h[1][ch], h[2][ch]);
+            xl_bf16_split3(v, h[0][ch], h[1][ch], h[2][ch]);
         }
 #pragma unroll
-        for (int p = 0; p < 3; ++p) sH[p * (kC1HH * kC1HW) + i] = c1_u32x2{ h[p][0] | (h[p][1] << 16), h[p][2] };
+        for (int p = 0; p < 3; ++p) sH[p * (kC1HH * kC1HW) + i] = u32x2{ h[p][0] | (h[p][1] << 16), h[p][2] };
     }
     // ---- weight fragments: lane -> (channel lane & 31, K half lane >> 5); slot j of a K-step = (dx = j >> 2, c = j & 3),
     // zero for c = 3 and dx = 3.  Split and packed once per plan on the host side: wfrag[plane][dy][lane], 16 bytes each.
     const int kh = lane >> 5;
-    c1_bf16x8 wf[3][3];                                              // [plane][dy]
+    bf16x8 wf[3][3];                                                 // [plane][dy]
 #pragma unroll
     for (int p = 0; p < 3; ++p)
 #pragma unroll
-        for (int dy = 0; dy < 3; ++dy) wf[p][dy] = __builtin_bit_cast(c1_bf16x8, wfrag[(p * 3 + dy) * 64 + lane]);
+        for (int dy = 0; dy < 3; ++dy) wf[p][dy] = __builtin_bit_cast(bf16x8, wfrag[(p * 3 + dy) * 64 + lane]);
     // accumulator element r of a lane: pixel lane & 31, channel 8 (r >> 2) + 4 kh + (r & 3)
     float b16[16], sc[16], sh[16];
 #pragma unroll
@@ -303,14 +283,14 @@ void conv1_mfma_kernel(const float *__restrict__ in, const c1_u32x4 *__restrict_
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = b16[r];
-        c1_bf16x8 pf[3][3];                                          // [plane][dy]
+        bf16x8 pf[3][3];                                             // [plane][dy]
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
-                const c1_u32x2 *src = sH + p * (kC1HH * kC1HW) + (ly + dy) * kC1HW + lx + 2 * kh;
-                const c1_u32x2 a = src[0], b = src[1];
-                pf[p][dy] = __builtin_bit_cast(c1_bf16x8, c1_u32x4{ a[0], a[1], b[0], b[1] });
+                const u32x2 *src = sH + p * (kC1HH * kC1HW) + (ly + dy) * kC1HW + lx + 2 * kh;
+                const u32x2 a = src[0], b = src[1];
+                pf[p][dy] = __builtin_bit_cast(bf16x8, u32x4{ a[0], a[1], b[0], b[1] });
             }
         constexpr int PW[6] = { 2, 1, 0, 1, 0, 0 }, PP[6] = { 0, 1, 2, 0, 1, 0 };   // smallest terms first
 #pragma unroll
@@ -407,14 +387,6 @@ struct ConvArgs {
     // coef = {scale, shift} pairs [B][Cin][2] from GN_FINAL, x -> max(x*scale + shift, normLo), normLo = 0 (ReLU) or -inf
     const float *coef; float normLo;
 };
-
-// bijective XCD remap: block b runs on XCD b%8; give each XCD a contiguous run of tiles
-__device__ __forceinline__ int xcd_remap(int b, int nwg)
-{
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = b & 7, local = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-}
 
 // Tiles go global -> LDS directly (buffer_load ... lds through buffer descriptors): no register staging and no
 // ds_write phase.  A padding tap gets an out-of-range offset and the hardware writes zeros (no branch, no select on
@@ -603,7 +575,6 @@ void igemm_conv_kernel(ConvArgs a)
     if constexpr (MODE == 0 && ZB == 0) {
         // forward: the accumulators start at the bias (a null bias reads as zeros through the bounds check)
         const __amdgpu_buffer_rsrc_t srdBias = __builtin_amdgcn_make_buffer_rsrc((void *)a.bias, 0, a.bias ? a.Cout * 4 : 0, 0x00020000);
-        typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
@@ -761,7 +732,6 @@ void igemm_conv_kernel(ConvArgs a)
     // loads return 0); with branches the compiler must assume a load pending at every block entry and emits vmcnt(0)
     // before each store.  The accumulate switch is a compile-time tag for the same reason.
     const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc((void *)a.out, 0, (int)a.outBytes, 0x00020000);
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     unsigned pixOff[TI];
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
@@ -1198,22 +1168,6 @@ __device__ __forceinline__ void wino6_at(const V (&m)[8], V (&o)[6])
     o[5] = d12 + 32.f * d34 + d56 + m[7];
 }
 
-// fp32 -> bf16 (round to nearest even) and back; a = h1 + h2 + h3 splits 24 mantissa bits exactly
-__device__ __forceinline__ unsigned bf16_rn(float x)
-{
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ float bf16_f(unsigned h) { return __builtin_bit_cast(float, h << 16); }
-__device__ __forceinline__ void bf16_split3(float a, unsigned &h1, unsigned &h2, unsigned &h3)
-{
-    h1 = bf16_rn(a);
-    const float r1 = a - bf16_f(h1);
-    h2 = bf16_rn(r1);
-    h3 = bf16_rn(r1 - bf16_f(h2));
-}
-
 // one tile x 2 channels per thread; DEFER as in wino4_in_kernel.  SPLIT: V is written as three bf16 planes
 // ([plane][64][tiles][C], the operand form of csrc/xl_gemm_split.hip) instead of fp32.
 // The interleaved-plane forms are held to 168 VGPRs = three waves per SIMD (the deferred one would take 178 and runs 20 %
@@ -1320,11 +1274,10 @@ void wino6_in_kernel(const float *__restrict__ in, float *__restrict__ V, int B,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     unsigned a1, a2, a3, b1, b2, b3;
-                    bf16_split3(o[j][0], a1, a2, a3);
-                    bf16_split3(o[j][1], b1, b2, b3);
+                    xl_bf16_split3(o[j][0], a1, a2, a3);
+                    xl_bf16_split3(o[j][1], b1, b2, b3);
                     unsigned *row = sX[wv][j & 1];
                     row[wr] = a1 | (b1 << 16); row[wr + 8] = a2 | (b2 << 16); row[wr + 16] = a3 | (b3 << 16);
-                    typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
                     const u32x3 v3 = u32x3{ row[3 * lane], row[3 * lane + 1], row[3 * lane + 2] };
                     *reinterpret_cast<u32x3 *>(op + (8 * i + j) * zw) = v3;
                 }
@@ -1340,8 +1293,6 @@ void wino6_in_kernel(const float *__restrict__ in, float *__restrict__ V, int B,
             // the lo' pair), then lanes 1 and 2 swap - so that lane q stores bytes 8 q .. 8 q + 7: the same dwordx2 store, at the
             // same address, as the fp32 form.  (Through a wave-private LDS row instead: 0.60 / 1.07 ms per 512-channel launch at 95
             // frames, plain / fold form, against 0.51 / 0.83 for fp32.)
-            typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-            typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             const float sc = pairScale[0];
             const bool odd = (threadIdx.x & 1) != 0, mid = ((threadIdx.x + 1) & 2) != 0;      // lanes 1 and 2 of a quad
             unsigned *op = reinterpret_cast<unsigned *>(V) + t * C + 2 * c2;
@@ -1351,9 +1302,8 @@ void wino6_in_kernel(const float *__restrict__ in, float *__restrict__ V, int B,
                 wino6_bt(w[i], o);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const f32x2 x = o[j] * sc;
-                    const f16x2 h = __builtin_convertvector(x, f16x2);
-                    const f16x2 l = __builtin_convertvector((x - __builtin_convertvector(h, f32x2)) * 2048.f, f16x2);
+                    f16x2 h, l;
+                    xl_f16_pair_scaled_pk(o[j] * sc, h, l);
                     const int H = __builtin_bit_cast(int, h), L = __builtin_bit_cast(int, l);
                     const int recv = __builtin_amdgcn_update_dpp(0, odd ? H : L, 0xB1, 0xF, 0xF, false);      // quad_perm [1,0,3,2]
                     int p0 = odd ? recv : H, p1 = odd ? L : recv;                 // even lanes: (hi, hi'), odd lanes: (lo', lo'')
@@ -1375,8 +1325,8 @@ void wino6_in_kernel(const float *__restrict__ in, float *__restrict__ V, int B,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     unsigned a1, a2, a3, b1, b2, b3;
-                    bf16_split3(o[j][0], a1, a2, a3);
-                    bf16_split3(o[j][1], b1, b2, b3);
+                    xl_bf16_split3(o[j][0], a1, a2, a3);
+                    xl_bf16_split3(o[j][1], b1, b2, b3);
                     unsigned *q = op + (((8 * i + j) * zs) >> 1);
                     q[0] = a1 | (b1 << 16); q[plane] = a2 | (b2 << 16); q[2 * plane] = a3 | (b3 << 16);
                 }
@@ -1432,7 +1382,6 @@ void wino6_out_kernel(const float *__restrict__ M, const float *__restrict__ bia
     // VW = 2: the first frequency column of a tile is fetched while the tile BEFORE it is still being reduced and stored (round
     // 4): without that every tile started with an empty memory pipeline - 8 loads issued, one full HBM latency waited - and the
     // 36 stores of a tile went out with no read in flight behind them.
-    typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
     const unsigned zsB = (unsigned)(zs * 4);
     auto tile_off = [&](int tl) { return (unsigned)(((long long)n * Timg + tl) * ts + cch) * 4u; };
     auto ldp = [&](unsigned vo, int plane) {
@@ -1659,7 +1608,6 @@ void wino6_out_dma_kernel(const float *__restrict__ M, const float *__restrict__
                 const bool live = (oy < H) & (ox < W);
                 const f32x2 v = y[pI][qI];
                 const unsigned off = live ? (unsigned)(((((long long)n * H + oy) * W + ox) * ldOut + cch) * 4) : OOB;
-                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), srdO, (int)off, 0, 0);
                 if (live) { s1 += v; s2 += v * v; }
             }
@@ -1753,7 +1701,6 @@ void gn_final_kernel(const double *__restrict__ stats, const float *__restrict__
             if (k1 > valid) k1 = valid;
             // four interleaved partial sums (k % 4), added in order: the loads of four entries are in flight together - as
             // one dependent chain a slice of 19 entries (a single frame: 150 one-tile chunks) took ~8 us of L2 latency
-            typedef double f64x2 __attribute__((ext_vector_type(2)));
             const f64x2 *st = reinterpret_cast<const f64x2 *>(stats) + ((long long)n * nchunks * G + g);
             double pa[4] = { 0.0, 0.0, 0.0, 0.0 }, pb[4] = { 0.0, 0.0, 0.0, 0.0 };
             int k = k0;
@@ -2335,15 +2282,15 @@ int run_op(const xl_op &op, hipStream_t st)
                     if (op.nchunks != tilesX * tilesY || (op.stats && op.groups != 32)) return XL_ERR_ARG;
                     if (op.stats && op.out)
                         hipLaunchKernelGGL(conv1_mfma_kernel<2>, dim3(op.nchunks, op.B), dim3(256), 0, st, (const float *)op.in,
-                                           (const c1_u32x4 *)op.w, (const float *)op.bias, (const float *)nullptr, (float *)op.out,
+                                           (const u32x4 *)op.w, (const float *)op.bias, (const float *)nullptr, (float *)op.out,
                                            (double *)op.stats, op.Hi, op.Wi, tilesX, 0);
                     else if (op.stats)
                         hipLaunchKernelGGL(conv1_mfma_kernel<0>, dim3(op.nchunks, op.B), dim3(256), 0, st, (const float *)op.in,
-                                           (const c1_u32x4 *)op.w, (const float *)op.bias, (const float *)nullptr, (float *)nullptr,
+                                           (const u32x4 *)op.w, (const float *)op.bias, (const float *)nullptr, (float *)nullptr,
                                            (double *)op.stats, op.Hi, op.Wi, tilesX, 0);
                     else
                         hipLaunchKernelGGL(conv1_mfma_kernel<1>, dim3(op.nchunks, op.B), dim3(256), 0, st, (const float *)op.in,
-                                           (const c1_u32x4 *)op.w, (const float *)op.bias, (const float *)op.aux2, (float *)op.out,
+                                           (const u32x4 *)op.w, (const float *)op.bias, (const float *)op.aux2, (float *)op.out,
                                            (double *)nullptr, op.Hi, op.Wi, tilesX, (op.flags & XL_GN_RELU_IN) ? 1 : 0);
                     return XL_OK;
                 }

@@ -18,15 +18,12 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 int xl_run_wgrad_split(const xl_op &op, hipStream_t st);   // xl_wgrad_split.hip
 int xl_run_wgrad_pair(const xl_op &op, hipStream_t st);    // xl_wgrad_pair.hip
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff)
 {
@@ -35,14 +32,6 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned
 }
 
 // ---------------------------------------------------------------------------------------------- wgrad
-
-// bijective XCD remap: block b runs on XCD b%8; give each XCD a contiguous run of work items
-__device__ __forceinline__ int xcd_remap(int b, int nwg)
-{
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = b & 7, local = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-}
 
 struct WgradArgs {
     const float *x; const float *dy; float *partial;
@@ -65,7 +54,7 @@ struct WgradArgs {
 // forward kernel's: double-buffered, one barrier per K-step placed before its last chunk, the first fragments of
 // the next step prefetched across the step boundary, DMA issue in the shadow of the last chunk's MFMAs.
 template <int N> struct FragT { typedef float type; };
-template <> struct FragT<2> { typedef float type __attribute__((ext_vector_type(2))); };
+template <> struct FragT<2> { typedef f32x2 type; };
 template <int N> __device__ __forceinline__ float frag_elem(const typename FragT<N>::type &v, int i);
 template <> __device__ __forceinline__ float frag_elem<1>(const float &v, int) { return v; }
 template <> __device__ __forceinline__ float frag_elem<2>(const FragT<2>::type &v, int i) { return v[i]; }
@@ -261,7 +250,6 @@ void wgrad_kernel(WgradArgs a)
             const int c = c0 + wc * (BC / WC) + TJ * col;
             float *dst = P + (long long)o * a.Cin + c;
             if constexpr (TJ == 2) {
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
                 *reinterpret_cast<f32x2 *>(dst) = f32x2{ acc[i][0][r], acc[i][1][r] };
             } else {
                 *dst = acc[i][0][r];
@@ -320,8 +308,6 @@ int launch_wgrad(const xl_op &op, hipStream_t st)
 // Weight gradient of a stride-1 3x3 layer through F(4x4,3x3): with V = B^T x B (wino4_in_kernel) and dM = A dY A^T per
 // 4x4 output tile, dU[xi][co][ci] = sum_tiles dM[xi][t][co] V[xi][t][ci] is 36 GEMMs with the TILES as the K dimension
 // (the batched wgrad_kernel above, 4x fewer multiplies than the 9-tap form), and dg = G^T dU G.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 template <typename V>
 __device__ __forceinline__ void wino4_a(const V (&d)[4], V (&o)[6])      // A = (A^T)^T, 6x4
 {

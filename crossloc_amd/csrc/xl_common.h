@@ -25,6 +25,30 @@ struct XlLdsLimit {
     }
 };
 
+// bijective XCD remap: block b runs on XCD b%8; give each XCD a contiguous run of tiles / work items
+__device__ __forceinline__ int xcd_remap(int b, int nwg)
+{
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = b & 7, local = b >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
+}
+
+// The LDS slot swizzle of the fp16-pair operands (xl_gemm_pair.hip, xl_stem_pair.hip, xl_wgrad_pair.hip).  LDS rows of both
+// operands are 4 slots of 16 bytes (hi k0-7, hi k8-15, lo k0-7, lo k8-15), slot s of row r at physical slot s ^ swz(r).
+// ds_read_b128 is serviced in four groups of 16 lanes ({0-3, 12-15, 20-27}, ...); the 16 rows of a group must hit 16 different
+// 16-byte columns of the 256-byte bank row: (4 r + slot) mod 16, i.e. rows equal mod 4 need different swz - bits 2-3 of the
+// row.  Bit 1 is folded into the upper slot bit for the converting kernels' ds_write_b128 (groups of 8 consecutive lanes = 4
+// rows x 2 halves over 128 bytes of banks: rows r and r + 2 would collide).
+__device__ __forceinline__ int swz(int row) { return ((row >> 2) & 3) ^ (((row >> 1) & 1) << 1); }
+
+// Sum of a double over the 64 lanes of a wave, every lane gets it: xor butterfly, a fixed order (the solver's canonical one)
+__device__ __forceinline__ double wave_butterfly(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
+    return v;
+}
+
 // Sum over the 32 lanes of a half wave (lanes 0-31 / 32-63) as a fixed fp32 tree on the DPP path, one v_add_f32 per level, no
 // LDS traffic: pairs, quads (quad_perm), half rows (row_half_mirror), rows (row_mirror), then lane 15 of rows 0 / 2 broadcast
 // into rows 1 / 3 (row_bcast:15).  The total is valid in the UPPER 16 lanes of the half only (lanes 16-31 / 48-63).

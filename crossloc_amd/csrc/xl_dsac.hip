@@ -116,13 +116,6 @@ __device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, 
 
 // ------------------------------------------------------------------------------ wave / block reductions
 
-__device__ __forceinline__ double wave_butterfly(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
-
 __device__ __forceinline__ Pose wave_bcast_pose(const Pose &p, int src)
 {
     Pose o;

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "../../include/crossloc_dsac.h"
+#include "xl_common.h"
 
 namespace {
 
@@ -38,13 +39,6 @@ struct QualityParams {
     int Ho, Wo, sub;
     float thr, focal, ppx, ppy, alpha, maxReproj;
 };
-
-__device__ __forceinline__ double wave_butterfly(double v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_quality_kernel(QualityParams P)

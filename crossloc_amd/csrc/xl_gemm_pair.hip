@@ -41,26 +41,13 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kPA = 64;                                  // bytes per activation row and K-step: {hi, lo'} x 16 fp16
 constexpr int kPB = 64;                                  // bytes per weight row and K-step: {hi, lo} x 16 fp16
 constexpr unsigned OOB = 0x80000000u;
-
-// LDS rows of both operands are 4 slots of 16 bytes (hi k0-7, hi k8-15, lo k0-7, lo k8-15), slot s of row r at
-// physical slot s ^ swz(r).  ds_read_b128 is serviced in four groups of 16 lanes ({0-3, 12-15, 20-27}, ...); the 16 rows of a
-// group must hit 16 different 16-byte columns of the 256-byte bank row: (4 r + slot) mod 16, i.e. rows equal mod 4 need
-// different swz - bits 2-3 of the row.  Bit 1 is folded into the upper slot bit for the converting kernel's ds_write_b128
-// (groups of 8 consecutive lanes = 4 rows x 2 halves over 128 bytes of banks: rows r and r + 2 would collide).
-__device__ __forceinline__ int swz(int row) { return ((row >> 2) & 3) ^ (((row >> 1) & 1) << 1); }
 
 struct PairArgs {
     const unsigned char *v, *u;  // [Z][T][C/16][2][16] fp16, [Z][N][C/16][2][16] fp16
@@ -91,8 +78,6 @@ __device__ __forceinline__ void lane_pair_exchange(const f32x16 &c, bool odd, f3
         o1[e] = odd ? x1 : recv;
     }
 }
-
-__device__ __forceinline__ f16x8 scale_hs(f16x8 hi) { return hi * (_Float16)0.00048828125f; }      // hi * 2^-11: 4 x v_pk_mul_f16
 
 // vmcnt bookkeeping (in order, per wave): a wave issues 4 DMA instructions per K-step (2 per operand), all in front of the step's
 // barrier, into the stage that was multiplied in the step before.  At the barrier of step s the operands of step s + 1 must
@@ -243,7 +228,7 @@ void pair_gemm_kernel(PairArgs a)
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) { fb[0][j] = fbN[j]; fbs[j] = scale_hs(fbN[j]); }
+            for (int j = 0; j < 2; ++j) { fb[0][j] = fbN[j]; fbs[j] = xl_f16_hs(fbN[j]); }
 #pragma unroll
             for (int i = 0; i < 4; ++i) fa[1][i] = faN[i];
 #pragma unroll
@@ -527,8 +512,8 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const f32x2 v = f32x2{ x[2 * e], x[2 * e + 1] };
-                const f16x2 hi = __builtin_convertvector(v, f16x2);
-                const f16x2 lo = __builtin_convertvector((v - __builtin_convertvector(hi, f32x2)) * 2048.f, f16x2);
+                f16x2 hi, lo;
+                xl_f16_pair_scaled_pk(v, hi, lo);
                 w[0][2 * h + e] = __builtin_bit_cast(unsigned, hi);
                 w[1][2 * h + e] = __builtin_bit_cast(unsigned, lo);
             }
@@ -658,9 +643,9 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
         for (int j = 0; j < 2; ++j) fb[1][j] = ldB(sc, 1, j);
 #pragma unroll
         for (int i = 0; i < RI; ++i) fa[0][i] = ldA(sa, 0, i);
-        fbs[0] = scale_hs(fb[0][0]);
+        fbs[0] = xl_f16_hs(fb[0][0]);
         mma_col(fbs[0], fa[1], 0);                                     // hs x lo'
-        fbs[1] = scale_hs(fb[0][1]);
+        fbs[1] = xl_f16_hs(fb[0][1]);
         mma_col(fbs[1], fa[1], 1);
         load_a(parTag);                                               // step kk + 2: two steps until its conversion
         advance_a();

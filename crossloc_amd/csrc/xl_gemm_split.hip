@@ -24,13 +24,9 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct SplitArgs {
     const uint16_t *v, *u;      // plane 0 of the activations / weights
@@ -39,13 +35,6 @@ struct SplitArgs {
     int T, C, N, Z, nbm, nbn;
     unsigned vBytes, uBytes, outBytes;     // extents of one plane / of the output for the buffer descriptors
 };
-
-__device__ __forceinline__ int xcd_remap(int b, int nwg)
-{
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = b & 7, local = b >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
-}
 
 constexpr int kBM = 128, kBN = 128, kBK = 32;           // tile; K-step in channels
 constexpr int kRowB = kBK * 2;                          // bytes per LDS row (64)
@@ -638,25 +627,6 @@ struct SplitConvArgs {
                                                      // producer's whole GroupNorm(+ReLU, +residual, +ReLU) epilogue applied on load
 };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_bf16(float x, float y)        // {bf16(x), bf16(y)} round to nearest even
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ x, y }, bf16x2));
-}
-__device__ __forceinline__ float hi_f(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float lo_f(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-// x = t1 + t2 + t3 exactly, for two values at a time (one 32-bit word per term)
-// (two values at a time as a float pair: v_pk_add_f32 for the residuals)
-__device__ __forceinline__ void split_pair(f32x2 v, unsigned &w1, unsigned &w2, unsigned &w3)
-{
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-    const f32x2 r = v - f32x2{ lo_f(w1), hi_f(w1) };
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-    const f32x2 r2 = r - f32x2{ lo_f(w2), hi_f(w2) };
-    w3 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-}
-
 // NW = waves per workgroup: 8 -> tiles of 256 x 256 (2 x 4 waves of 128 x 64), the throughput form; 4 -> tiles of 128 x 128
 // (2 x 2 waves of 64 x 64) for launches whose 256 x 256 tiles would leave most of the 256 CUs idle (a single frame: 44 tiles).
 // Every output element accumulates its K-steps and term pairs in the same order in both forms: bitwise the same result.
@@ -821,8 +791,8 @@ __device__ __forceinline__ void split_conv1x1_body(const SplitConvArgs &a)
                     x = f32x4{ fmaxf(x[0] + r[0], 0.f), fmaxf(x[1] + r[1], 0.f), fmaxf(x[2] + r[2], 0.f), fmaxf(x[3] + r[3], 0.f) };
                 }
             }
-            split_pair(f32x2{ x[0], x[1] }, w[0][2 * h], w[1][2 * h], w[2][2 * h]);
-            split_pair(f32x2{ x[2], x[3] }, w[0][2 * h + 1], w[1][2 * h + 1], w[2][2 * h + 1]);
+            xl_bf16_split3_pk(f32x2{ x[0], x[1] }, w[0][2 * h], w[1][2 * h], w[2][2 * h]);
+            xl_bf16_split3_pk(f32x2{ x[2], x[3] }, w[0][2 * h + 1], w[1][2 * h + 1], w[2][2 * h + 1]);
         }
 #pragma unroll
         for (int p = 0; p < 3; ++p)

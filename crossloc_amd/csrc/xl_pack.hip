@@ -7,22 +7,9 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned bf16_rn(float x)
-{
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void split3(float a, unsigned &h1, unsigned &h2, unsigned &h3)
-{
-    h1 = bf16_rn(a);
-    const float r1 = a - __builtin_bit_cast(float, h1 << 16);
-    h2 = bf16_rn(r1);
-    h3 = bf16_rn(r1 - __builtin_bit_cast(float, h2 << 16));
-}
 
 // G of F(m x m, 3x3): [(m+2)][3], the matrices of crossloc_amd/networks.py::_Plan._WINO_G
 template <int M> struct WinoG;
@@ -66,7 +53,7 @@ void wino_weight_kernel(const float *__restrict__ w, void *__restrict__ dst, int
                 if (form == 0) reinterpret_cast<float *>(dst)[e] = u;
                 else {
                     unsigned h1, h2, h3;
-                    split3(u, h1, h2, h3);
+                    xl_bf16_split3(u, h1, h2, h3);
                     uint16_t *d = reinterpret_cast<uint16_t *>(dst);
                     if (form == 1) { d[e] = (uint16_t)h1; d[plane + e] = (uint16_t)h2; d[2 * plane + e] = (uint16_t)h3; }
                     else {
@@ -90,7 +77,7 @@ void split_weight_kernel(const float *__restrict__ src, uint16_t *__restrict__ d
         else if (taps == 0) v = src[(long long)k * rows + r];                      // transposed source [K][rows]
         else { const int tap = k / Cin, c = k - tap * Cin; v = src[((long long)r * Cin + c) * taps + tap]; }
         unsigned h1, h2, h3;
-        split3(v, h1, h2, h3);
+        xl_bf16_split3(v, h1, h2, h3);
         const long long b0 = ((long long)r * (K >> 4) + (k >> 4)) * 48 + (k & 15);
         dst[b0] = (uint16_t)h1; dst[b0 + 16] = (uint16_t)h2; dst[b0 + 32] = (uint16_t)h3;
     }
@@ -101,22 +88,7 @@ void split_weight_kernel(const float *__restrict__ src, uint16_t *__restrict__ d
 // XL_CONV_PAIR_F16 (csrc/xl_gemm_pair.hip): a weight w, scaled by the power of two 2^e of its matrix (max|w| 2^e in [2^14, 2^15)),
 // is stored as {hi = fp16(x), lo = fp16(x - hi)}; layout [Z][rows][K/16][2][16] fp16, then 2 Z floats:
 // the maxima of the matrices as float bits (pass 1, atomicMax on the bits of |w| - non-negative floats order like their bits)
-// and the inverse scales 2^-e (pass 2).
-__device__ __forceinline__ float pair_scale_of_max(unsigned maxBits)
-{
-    if (maxBits == 0u || (maxBits >> 23) == 0u) return 1.f;                       // all zero (or subnormal): no scaling
-    const int E = (int)(maxBits >> 23) - 127;                                    // floor(log2(max))
-    int e = 14 - E;
-    if (e > 100) e = 100;
-    if (e < -100) e = -100;
-    return __builtin_bit_cast(float, (unsigned)(e + 127) << 23);
-}
-__device__ __forceinline__ void pair_hi_lo(float x, uint16_t &hi, uint16_t &lo)
-{
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)(x - (float)h);
-    hi = __builtin_bit_cast(uint16_t, h); lo = __builtin_bit_cast(uint16_t, l);
-}
+// and the inverse scales 2^-e (pass 2).  Scale and pair: xl_pair_scale_of_max and xl_f16_pair (xl_operand_math.h).
 
 template <int M>
 __device__ __forceinline__ void wino_u_of(const float *__restrict__ w, int Cin, int o, int c, int dgrad, float (&u)[(M + 2) * (M + 2)])
@@ -178,9 +150,9 @@ void wino_weight_pair_kernel(const PairItem *__restrict__ items, PairItem one)
         } else {
 #pragma unroll
             for (int z = 0; z < Z; ++z) {
-                const float sc = pair_scale_of_max(maxBits[z]);
+                const float sc = xl_pair_scale_of_max(maxBits[z]);
                 uint16_t hi, lo;
-                pair_hi_lo(u[z] * sc, hi, lo);
+                xl_f16_pair(u[z] * sc, hi, lo);
                 const long long b0 = (((long long)z * rows + r) * (K >> 4) + (k >> 4)) * 32 + (k & 15);
                 dst[b0] = hi; dst[b0 + 16] = lo;
                 if (i == 0) invScale[z] = 1.f / sc;
@@ -220,7 +192,7 @@ void pair_weight_kernel(const PairItem *__restrict__ items, PairItem one)
     float *__restrict__ invScale = reinterpret_cast<float *>(maxBits + 1);
     const int Cin = taps > 0 ? K / taps : K;
     unsigned m = 0u;
-    const float sc = PASS ? pair_scale_of_max(maxBits[0]) : 1.f;
+    const float sc = PASS ? xl_pair_scale_of_max(maxBits[0]) : 1.f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         if (PASS == 0) {                                               // (the maximum does not care about the order: a linear read)
             const unsigned b = __builtin_bit_cast(unsigned, fabsf(src[i]));
@@ -233,7 +205,7 @@ void pair_weight_kernel(const PairItem *__restrict__ items, PairItem one)
         else if (taps == 0) v = src[(long long)k * rows + r];
         else { const int tap = k / Cin, c = k - tap * Cin; v = src[((long long)r * Cin + c) * taps + tap]; }
         uint16_t hi, lo;
-        pair_hi_lo(v * sc, hi, lo);
+        xl_f16_pair(v * sc, hi, lo);
         const long long b0 = ((long long)r * (K >> 4) + (k >> 4)) * 32 + (k & 15);
         dst[b0] = hi; dst[b0 + 16] = lo;
         if (i == 0) invScale[0] = 1.f / sc;
@@ -250,11 +222,10 @@ void pair_activation_kernel(const float *__restrict__ src, uint16_t *__restrict_
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const long long r = i / K;
         const int k = (int)(i - r * K);
-        const float x = src[i] * sc;
-        const _Float16 h = (_Float16)x;
-        const _Float16 l = (_Float16)((x - (float)h) * 2048.f);
+        uint16_t hi, lo;
+        xl_f16_pair_scaled(src[i] * sc, hi, lo);
         const long long b0 = (r * (K >> 3) + (k >> 3)) * 16 + (k & 7);
-        dst[b0] = __builtin_bit_cast(uint16_t, h); dst[b0 + 8] = __builtin_bit_cast(uint16_t, l);
+        dst[b0] = hi; dst[b0 + 8] = lo;
     }
 }
 

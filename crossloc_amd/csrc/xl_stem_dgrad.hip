@@ -20,30 +20,12 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kTY = 16, kTX = 32;                      // result pixels per tile
 constexpr int kPR = kTY / 2 + 1, kPC = kTX / 2 + 1;    // dY patch: 9 x 17
-
-__device__ __forceinline__ float sd_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float sd_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ void sd_split_pair(f32x2 v, unsigned &w1, unsigned &w2, unsigned &w3)
-{
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-    const f32x2 r = v - f32x2{ sd_lo(w1), sd_hi(w1) };
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-    const f32x2 r2 = r - f32x2{ sd_lo(w2), sd_hi(w2) };
-    w3 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-}
 
 struct S2DgradArgs {
     const float *dy;             // [B][Ho][Wo][CO], pixel stride ldDy
@@ -114,8 +96,8 @@ void s2_dgrad_kernel(S2DgradArgs a)
             if (i < PIECES) {
                 const int pix = i / (CO / 4), c4 = i - pix * (CO / 4);
                 unsigned wa[3], wb[3];
-                sd_split_pair(f32x2{ pre[e][0], pre[e][1] }, wa[0], wa[1], wa[2]);
-                sd_split_pair(f32x2{ pre[e][2], pre[e][3] }, wb[0], wb[1], wb[2]);
+                xl_bf16_split3_pk(f32x2{ pre[e][0], pre[e][1] }, wa[0], wa[1], wa[2]);
+                xl_bf16_split3_pk(f32x2{ pre[e][2], pre[e][3] }, wb[0], wb[1], wb[2]);
 #pragma unroll
                 for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2 *>(sP + pix * kPix + p * (CO * 2) + c4 * 8) = u32x2{ wa[p], wb[p] };
             }

@@ -30,18 +30,9 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTW = 16;                                // conv2 output columns per tile (rows: the template parameter TH)
 constexpr int kPW = 2 * kTW + 1;                       // conv1 output columns the tile needs: 33
@@ -67,31 +58,8 @@ template <int TH, bool PAIR = false> struct S12 {
     static constexpr int kPB = TH / 2;                               // 32-pixel blocks per tile (4 waves: kPB x 4 / kPB column blocks)
 };
 
-// the split of conv1_mfma_kernel (integer round-to-nearest-even) - the image halo must be split exactly as there
-__device__ __forceinline__ unsigned s12_bf16_rn(float x)
-{
-    unsigned u = __builtin_bit_cast(unsigned, x);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-__device__ __forceinline__ void s12_split3(float a, unsigned &h1, unsigned &h2, unsigned &h3)
-{
-    h1 = s12_bf16_rn(a);
-    const float r1 = a - __builtin_bit_cast(float, h1 << 16);
-    h2 = s12_bf16_rn(r1);
-    h3 = s12_bf16_rn(r1 - __builtin_bit_cast(float, h2 << 16));
-}
-// the split of split_conv3x3s2_kernel (v_cvt_pk_bf16_f32, exact residuals): the normalised activations, two at a time
-__device__ __forceinline__ float s12_hi(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float s12_lo(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ void s12_split_pair(f32x2 v, unsigned &w1, unsigned &w2, unsigned &w3)
-{
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-    const f32x2 r = v - f32x2{ s12_lo(w1), s12_hi(w1) };
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-    const f32x2 r2 = r - f32x2{ s12_lo(w2), s12_hi(w2) };
-    w3 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-}
+// The image halo is split as in conv1_mfma_kernel (xl_bf16_split3, the integer form), the normalised activations as in
+// split_conv3x3s2_kernel (xl_bf16_split3_pk, two at a time): both exactly as there.
 
 struct Stem12Args {
     const float *img;            // [B][3][H][W]
@@ -204,7 +172,7 @@ void stem12_kernel(Stem12Args a)
             if (i < kHaloPix) {
                 unsigned h[3][3];
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) s12_split3(pre[e][ch], h[0][ch], h[1][ch], h[2][ch]);
+                for (int ch = 0; ch < 3; ++ch) xl_bf16_split3(pre[e][ch], h[0][ch], h[1][ch], h[2][ch]);
 #pragma unroll
                 for (int p = 0; p < 3; ++p) sH[p * kHaloPix + i] = u32x2{ h[p][0] | (h[p][1] << 16), h[p][2] };
             }
@@ -297,14 +265,16 @@ void stem12_kernel(Stem12Args a)
                 for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(fmaf(acc[4 * q + e], sc4[e], sh4[e]), lo, hi);
                 unsigned wa[3], wb[3];
                 if constexpr (PAIR) {
+                    // xl_f16_pair_scaled_pk written out for both halves at once (both hi first): through two calls the compiler
+                    // schedules this conversion differently, and the kernel's code is kept as it was measured
                     const f32x2 va = f32x2{ v[0], v[1] }, vb = f32x2{ v[2], v[3] };
                     const f16x2 ha = __builtin_convertvector(va, f16x2), hb = __builtin_convertvector(vb, f16x2);
                     wa[0] = __builtin_bit_cast(unsigned, ha); wb[0] = __builtin_bit_cast(unsigned, hb);
-                    wa[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((va - __builtin_convertvector(ha, f32x2)) * 2048.f, f16x2));
-                    wb[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((vb - __builtin_convertvector(hb, f32x2)) * 2048.f, f16x2));
+                    wa[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((va - __builtin_convertvector(ha, f32x2)) * kXlPairLoScale, f16x2));
+                    wb[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((vb - __builtin_convertvector(hb, f32x2)) * kXlPairLoScale, f16x2));
                 } else {
-                    s12_split_pair(f32x2{ v[0], v[1] }, wa[0], wa[1], wa[2]);
-                    s12_split_pair(f32x2{ v[2], v[3] }, wb[0], wb[1], wb[2]);
+                    xl_bf16_split3_pk(f32x2{ v[0], v[1] }, wa[0], wa[1], wa[2]);
+                    xl_bf16_split3_pk(f32x2{ v[2], v[3] }, wb[0], wb[1], wb[2]);
                 }
                 if (valid) {
 #pragma unroll
@@ -353,7 +323,7 @@ void stem12_kernel(Stem12Args a)
                 // hs x lo', lo x hi, hi x hi: pair_conv3x3s2_kernel's terms and order
 #pragma unroll
                 for (int j = 0; j < kNJ; ++j) {
-                    const f16x8 hs = __builtin_bit_cast(f16x8, fbr[slot][0][j]) * (_Float16)0.00048828125f;
+                    const f16x8 hs = xl_f16_hs(__builtin_bit_cast(f16x8, fbr[slot][0][j]));
                     acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hs, fa[1], acc2[j], 0, 0, 0);
                 }
 #pragma unroll
@@ -391,7 +361,6 @@ void stem12_kernel(Stem12Args a)
             // (u & 1); fp32 over the pair, the fp32 tree of xl_half_wave_sum over the 32 pixels, one fp64 entry per (tile, block)
             const bool live = oy < a.Ho && ox < a.Wo;
             double *o = a.stats + ((long long)n * a.nchunks + tt * kPB + pxb) * 64;
-            typedef double f64x2 __attribute__((ext_vector_type(2)));
             // (all the trees first - DPP only, no LDS traffic - then ONE predicated block of stores by a lane that holds the totals)
             float s1[kNJ][8], s2[kNJ][8];
 #pragma unroll

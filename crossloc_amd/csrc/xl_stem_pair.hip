@@ -18,19 +18,11 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kUnit = 64;                               // bytes per row and K-step, both operands: 2 planes x 16 fp16
-__device__ __forceinline__ int swz(int row) { return ((row >> 2) & 3) ^ (((row >> 1) & 1) << 1); }      // (csrc/xl_gemm_pair.hip)
-__device__ __forceinline__ f16x8 scale_hs(f16x8 hi) { return hi * (_Float16)0.00048828125f; }            // hi * 2^-11
 
 struct PairStemArgs {
     const float *in; const unsigned char *u; const float *bias; float *out;
@@ -206,8 +198,8 @@ void pair_conv3x3s2_kernel(PairStemArgs a)
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const f32x2 v = f32x2{ x[2 * e], x[2 * e + 1] };
-                const f16x2 vh = __builtin_convertvector(v, f16x2);
-                const f16x2 vl = __builtin_convertvector((v - __builtin_convertvector(vh, f32x2)) * 2048.f, f16x2);
+                f16x2 vh, vl;
+                xl_f16_pair_scaled_pk(v, vh, vl);
                 w[0][2 * h + e] = __builtin_bit_cast(unsigned, vh);
                 w[1][2 * h + e] = __builtin_bit_cast(unsigned, vl);
             }
@@ -307,7 +299,7 @@ void pair_conv3x3s2_kernel(PairStemArgs a)
 #pragma unroll
         for (int i = 0; i < RI; ++i) fa[0][i] = ldA(sa, 0, i);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) fbs[j] = scale_hs(fb[0][j]);
+        for (int j = 0; j < 2; ++j) fbs[j] = xl_f16_hs(fb[0][j]);
         mma(fbs, fa[1]); dma_instr(0, sd);                             // hs x lo'
         __builtin_amdgcn_sched_barrier(0);
         // lo x hi with the conversion of step kk + 1 threaded through it
@@ -394,7 +386,6 @@ void pair_conv3x3s2_kernel(PairStemArgs a)
             const int kT = m0 / BM - (int)(((long long)nLo * HWo) / BM);
             double *oLo = a.stats + ((long long)nLo * a.nchunks + kT * WM + wm) * a.G * 2;
             double *oHi = a.stats + ((long long)(nLo + 1) * a.nchunks + wm) * a.G * 2;
-            typedef double f64x2 __attribute__((ext_vector_type(2)));
             auto sums = [&](auto cpgTag) __attribute__((always_inline)) {
                 constexpr int CPG = decltype(cpgTag)::value;
                 constexpr int NR = CPG >= 16 ? 8 : (CPG >= 4 ? 4 : 2);   // accumulator registers per group and lane

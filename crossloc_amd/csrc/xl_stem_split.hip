@@ -31,33 +31,11 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kUnit = 96;                               // bytes per row and K-step: 3 planes x 16 bf16
-
-__device__ __forceinline__ unsigned pk_bf16(float x, float y)        // {bf16(x), bf16(y)} round to nearest even
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ x, y }, bf16x2));
-}
-__device__ __forceinline__ float hi_f(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float lo_f(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-// (two values at a time as a float pair: v_pk_add_f32 for the residuals)
-__device__ __forceinline__ void split_pair(f32x2 v, unsigned &w1, unsigned &w2, unsigned &w3)
-{
-    w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-    const f32x2 r = v - f32x2{ lo_f(w1), hi_f(w1) };
-    w2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-    const f32x2 r2 = r - f32x2{ lo_f(w2), hi_f(w2) };
-    w3 = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
-}
 
 struct StemArgs {
     const float *in; const uint16_t *u; const float *bias; float *out;
@@ -234,8 +212,8 @@ void split_conv3x3s2_kernel(StemArgs a)
                 x = f32x4{ __builtin_amdgcn_fmed3f(lo[0], clampLo, clampHi), __builtin_amdgcn_fmed3f(lo[1], clampLo, clampHi),
                            __builtin_amdgcn_fmed3f(hi[0], clampLo, clampHi), __builtin_amdgcn_fmed3f(hi[1], clampLo, clampHi) };
             }
-            split_pair(f32x2{ x[0], x[1] }, w[0][2 * h], w[1][2 * h], w[2][2 * h]);
-            split_pair(f32x2{ x[2], x[3] }, w[0][2 * h + 1], w[1][2 * h + 1], w[2][2 * h + 1]);
+            xl_bf16_split3_pk(f32x2{ x[0], x[1] }, w[0][2 * h], w[1][2 * h], w[2][2 * h]);
+            xl_bf16_split3_pk(f32x2{ x[2], x[3] }, w[0][2 * h + 1], w[1][2 * h + 1], w[2][2 * h + 1]);
         }
 #pragma unroll
         for (int p = 0; p < 3; ++p)
@@ -425,7 +403,6 @@ void split_conv3x3s2_kernel(StemArgs a)
             const int kT = m0 / BM - (int)(((long long)nLo * HWo) / BM);
             double *oLo = a.stats + ((long long)nLo * a.nchunks + kT * WM + wm) * a.G * 2;
             double *oHi = a.stats + ((long long)(nLo + 1) * a.nchunks + wm) * a.G * 2;
-            typedef double f64x2 __attribute__((ext_vector_type(2)));
             auto sums = [&](auto cpgTag) __attribute__((always_inline)) {
                 constexpr int CPG = decltype(cpgTag)::value;
                 constexpr int NR = CPG >= 16 ? 8 : (CPG >= 4 ? 4 : 2);   // accumulator registers per group and lane

@@ -18,19 +18,12 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kUnit = 64;                               // bytes per row and K-step: 2 planes x 16 fp16
 constexpr int kOperand = 256 * kUnit;                   // one operand of one stage: 16 KB
-__device__ __forceinline__ int swz(int row) { return ((row >> 2) & 3) ^ (((row >> 1) & 1) << 1); }      // (csrc/xl_gemm_pair.hip)
 
 struct WgPairArgs {
     const float *x, *dy; float *partial;
@@ -114,9 +107,10 @@ void wgrad_pair_kernel(WgPairArgs a)
 #pragma unroll
         for (int h = 0; h < 4; ++h) {                                  // dY: {hi, lo} of dY sY (the tight, data-derived scale)
             const f32x2 v = f32x2{ ra[2 * h], ra[2 * h + 1] } * sY;
-            const f16x2 vh = __builtin_convertvector(v, f16x2);
+            f16x2 vh, vl;
+            xl_f16_pair_pk(v, vh, vl);
             w[0][h] = __builtin_bit_cast(unsigned, vh);
-            w[1][h] = __builtin_bit_cast(unsigned, __builtin_convertvector(v - __builtin_convertvector(vh, f32x2), f16x2));
+            w[1][h] = __builtin_bit_cast(unsigned, vl);
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p) *reinterpret_cast<u32x4 *>(sb + wOff[p]) = u32x4{ w[p][0], w[p][1], w[p][2], w[p][3] };
@@ -127,9 +121,10 @@ void wgrad_pair_kernel(WgPairArgs a)
 #pragma unroll
         for (int h = 0; h < 4; ++h) {                                  // X: {hi, lo' = (x - hi) 2^11} of x sX (the plan's scale)
             const f32x2 v = NORM ? f32x2{ rb[2 * h], rb[2 * h + 1] } : f32x2{ rb[2 * h], rb[2 * h + 1] } * sX;
-            const f16x2 vh = __builtin_convertvector(v, f16x2);
+            f16x2 vh, vl;
+            xl_f16_pair_scaled_pk(v, vh, vl);
             w[0][h] = __builtin_bit_cast(unsigned, vh);
-            w[1][h] = __builtin_bit_cast(unsigned, __builtin_convertvector((v - __builtin_convertvector(vh, f32x2)) * 2048.f, f16x2));
+            w[1][h] = __builtin_bit_cast(unsigned, vl);
         }
 #pragma unroll
         for (int p = 0; p < 2; ++p) *reinterpret_cast<u32x4 *>(sb + kOperand + wOff[p]) = u32x4{ w[p][0], w[p][1], w[p][2], w[p][3] };
@@ -174,7 +169,7 @@ void wgrad_pair_kernel(WgPairArgs a)
 #pragma unroll
             for (int j = 0; j < 2; ++j) fb[0][j] = ldB(st, 0, j);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) fas[i] = fa[0][i] * (_Float16)0.00048828125f;     // hs = hi 2^-11
+            for (int i = 0; i < 4; ++i) fas[i] = xl_f16_hs(fa[0][i]);
             mma(fb[1], fas);                                           // lo'(X) x hs(dY)
             __builtin_amdgcn_sched_barrier(0);
             // lo(dY) x hi(X) with the conversion of step kk + 1 threaded through it (the other stage: every wave finished

@@ -19,32 +19,12 @@
 #include "../../include/crossloc_cnn.h"
 #include "../../include/crossloc_dsac.h"   // status codes
 #include "xl_common.h"
+#include "xl_operand_math.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kUnit = 96;                               // bytes per row and K-step: 3 planes x 16 bf16
 constexpr int kOperand = 256 * kUnit;                   // one operand of one stage: 24 KB
-
-__device__ __forceinline__ unsigned pk_bf16(float x, float y)
-{
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ x, y }, bf16x2));
-}
-__device__ __forceinline__ float hi_f(unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ float lo_f(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ void split_pair(float x, float y, unsigned &w1, unsigned &w2, unsigned &w3)
-{
-    w1 = pk_bf16(x, y);
-    const float rx = x - lo_f(w1), ry = y - hi_f(w1);
-    w2 = pk_bf16(rx, ry);
-    w3 = pk_bf16(rx - lo_f(w2), ry - hi_f(w2));
-}
 
 struct WgSplitArgs {
     const float *x, *dy; float *partial;
@@ -118,7 +98,7 @@ void wgrad_split_kernel(WgSplitArgs a)
         unsigned char *sb = dsm + stage * kStage;
         unsigned w[3][4];
 #pragma unroll
-        for (int h = 0; h < 4; ++h) split_pair(ra[2 * h], ra[2 * h + 1], w[0][h], w[1][h], w[2][h]);
+        for (int h = 0; h < 4; ++h) xl_bf16_split3_pk(ra[2 * h], ra[2 * h + 1], w[0][h], w[1][h], w[2][h]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4 *>(sb + wOff[p]) = u32x4{ w[p][0], w[p][1], w[p][2], w[p][3] };
         if constexpr (NORM) {                                          // one fmaf, one max: the arithmetic of every apply site
@@ -126,7 +106,7 @@ void wgrad_split_kernel(WgSplitArgs a)
             for (int e = 0; e < 8; ++e) rb[e] = (okC && e < nLive) ? fmaxf(fmaf(rb[e], nSc, nSh), a.normLo) : 0.f;
         }
 #pragma unroll
-        for (int h = 0; h < 4; ++h) split_pair(rb[2 * h], rb[2 * h + 1], w[0][h], w[1][h], w[2][h]);
+        for (int h = 0; h < 4; ++h) xl_bf16_split3_pk(rb[2 * h], rb[2 * h + 1], w[0][h], w[1][h], w[2][h]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4 *>(sb + kOperand + wOff[p]) = u32x4{ w[p][0], w[p][1], w[p][2], w[p][3] };
     };
