@@ -14,7 +14,9 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
     (reset with `set_image_index`), and results do not depend on thread or rank count.
   * `forward_rgb_batch` localises B images per launch (the reference is batch-1 only).
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
-    form `backward_rgb_batch` run on the GPU as well; the RGB-D pair stays unimplemented.
+    form `backward_rgb_batch` run on the GPU as well.
+  * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
+    tensor or a depth map; the reference-shaped `forward_rgbd` / `backward_rgbd` still raise NotImplementedError.
 There is no CPU fallback: without the HIP library the call raises.
 """
 import ctypes
@@ -238,6 +240,97 @@ def backward_rgb(sceneCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypoth
                               ppointY, wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj, subSampling, randomSeed)
     g.copy_(gd)
     return float(loss.item())
+
+
+RGBD_DBG_DOUBLES = 16                    # XL_DSAC_RGBD_DBG_DOUBLES: doubles per image in forward_rgbd_batch's debug record
+RGBD_MAX_CELLS = 6144                    # XL_DSAC_RGBD_MAX_CELLS: largest Ho*Wo forward_rgbd_batch accepts
+
+
+def camera_coordinates(depth, focal, image_h, image_w, sub):
+    """Camera coordinates [B,3,Ho,Wo] float32 of a depth map [B,Ho,Wo] float32 (depth along the optical axis, 0 = no measurement):
+    the ray through the pixel centre (sub*x + sub//2, sub*y + sub//2) of every cell times its depth, principal point
+    (image_w/2, image_h/2) - the formula forward_rgbd_batch applies itself when it is given `depth`, with the same bits.
+    `focal`: one number or one per image.  The ray factors are computed on the host (correctly rounded float32 division)."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.dtype != torch.float32:
+        raise RuntimeError("depth must be a float32 [B,Ho,Wo] tensor")
+    B, Ho, Wo = depth.shape
+    f = torch.as_tensor(focal, dtype=torch.float32).reshape(-1).cpu()
+    if f.numel() not in (1, B):
+        raise RuntimeError("expected 1 or %d focal lengths, got %d" % (B, f.numel()))
+    px = (torch.arange(Wo, dtype=torch.int64) * int(sub) + int(sub) // 2).to(torch.float32)
+    py = (torch.arange(Ho, dtype=torch.int64) * int(sub) + int(sub) // 2).to(torch.float32)
+    rx = ((px - float(image_w / 2))[None, :] / f[:, None]).to(depth.device)              # [1 or B, Wo]
+    ry = ((py - float(image_h / 2))[None, :] / f[:, None]).to(depth.device)              # [1 or B, Ho]
+    return torch.stack([rx[:, None, :] * depth, ry[:, :, None] * depth, depth], dim=1)
+
+
+def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypotheses, inlierThreshold, inlierAlpha,
+                       maxDistError, image0=0, image_stride=1, seed=None, max_tries=None, debug=False, depth=None,
+                       focalLength=None, ppointX=None, ppointY=None, subSampling=None, focals=None):
+    """RGB-D DSAC* (dsacstar_rgbd_forward, dsacstar.cpp:495-612) for B images in one launch: Kabsch hypotheses from three cells'
+    scene and camera coordinates.  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides); EXACTLY ONE of cameraCoordinates
+    [B,3,Ho,Wo] float32 CUDA (any strides) and depth [B,Ho,Wo] float32 CUDA (any strides).  With `depth` the camera coordinates
+    are formed in the kernel from focalLength (or per-image `focals`), ppointX, ppointY and subSampling, as camera_coordinates
+    does.  inlierThreshold and maxDistError are in centimetres.  A cell is valid iff its camera z is nonzero.  outPoses [B,4,4]
+    float32 CUDA contiguous, written in place (asynchronous on the current stream).  With debug=True returns a dict of device
+    tensors: cells [B,nHyp,3] int32, tries [B,nHyp] int32, scores [B,nHyp] float64, dbg [B,16] float64 (layout:
+    include/crossloc_dsac.h)."""
+    _check_coords(sceneCoordinates, True)
+    if (cameraCoordinates is None) == (depth is None):
+        raise RuntimeError("forward_rgbd_batch takes exactly one of cameraCoordinates and depth")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    other = cameraCoordinates if depth is None else depth
+    if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
+        raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
+    if depth is None and tuple(other.shape) != (B, 3, Ho, Wo):
+        raise RuntimeError("cameraCoordinates must be [B,3,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+    if depth is not None:
+        if tuple(other.shape) != (B, Ho, Wo):
+            raise RuntimeError("depth must be [B,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+        if (focalLength is None and focals is None) or ppointX is None or ppointY is None or subSampling is None:
+            raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
+        if int(subSampling) <= 0:
+            raise RuntimeError("subSampling must be positive")
+    if Ho * Wo > RGBD_MAX_CELLS:
+        raise RuntimeError("forward_rgbd_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
+                           % (Ho * Wo, RGBD_MAX_CELLS))
+    if not isinstance(outPoses, torch.Tensor) or not sceneCoordinates.is_cuda or not other.is_cuda or not outPoses.is_cuda:
+        raise RuntimeError("forward_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    if other.device != dev or outPoses.device != dev:
+        raise RuntimeError("all tensors must be on the device of sceneCoordinates")
+    if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4) or not outPoses.is_contiguous():
+        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor")
+    if int(ransacHypotheses) <= 0:
+        raise RuntimeError("ransacHypotheses must be positive")
+    if focals is not None:
+        focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
+        if focals.numel() != B:
+            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+        if focalLength is None:
+            focalLength = 0.0
+    out = None
+    cells = tries = scores = dbg = None
+    if debug:
+        cells = torch.zeros((B, ransacHypotheses, 3), dtype=torch.int32, device=dev)
+        tries = torch.zeros((B, ransacHypotheses), dtype=torch.int32, device=dev)
+        scores = torch.zeros((B, ransacHypotheses), dtype=torch.float64, device=dev)
+        dbg = torch.zeros((B, RGBD_DBG_DOUBLES), dtype=torch.float64, device=dev)
+        out = dict(cells=cells, tries=tries, scores=scores, dbg=dbg)
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
+    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_forward_rgbd_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
+            B, Ho, Wo, _ptr(outPoses), int(ransacHypotheses), float(inlierThreshold), float(inlierAlpha), float(maxDistError),
+            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            int(RANSAC_SEED if seed is None else seed), int(image0), int(image_stride),
+            int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream),
+            _ptr(cells), _ptr(tries), _ptr(scores), _ptr(dbg))
+    _lib.check(rc)
+    return out
 
 
 def forward_rgbd(*args, **kwargs):

@@ -226,7 +226,7 @@ def _focal_args(focal, n):
 
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
-                   quality=False):
+                   quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
     (:354), HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda, predictions [B,4,Ho,Wo]).
     `quality=True`: the pose-quality pass (dsacstar.pose_quality_batch) is enqueued directly behind the solver on the
@@ -234,8 +234,13 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     `focal`: a number, or one focal length per frame.
     `scene_coords` overrides the solver input (synthetic scenes: untrained weights do not predict a scene).
     `plant` [B,3,Ho,Wo]: written into the coordinate channels of the network output after the head; the solver then
-    consumes the network's own output tensor (the strided `pred[:, :3]` view) exactly as with trained weights."""
+    consumes the network's own output tensor (the strided `pred[:, :3]` view) exactly as with trained weights.
+    `depth` [B,Ho,Wo] or `cam_coords` [B,3,Ho,Wo] (at most one; off by default): the RGB-D solver
+    (dsacstar.forward_rgbd_batch: Kabsch hypotheses from the cells' camera coordinates) runs in place of the RGB one, with
+    `rgbd_threshold` and `max_dist_error` in centimetres; `quality` still rates the pose by its reprojection residuals."""
     import dsacstar
+    if depth is not None and cam_coords is not None:
+        raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
     with torch.no_grad():
         pred = network(images)
     nt = network.num_task_channel
@@ -244,9 +249,15 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     coords = pred[:, :nt] if scene_coords is None else scene_coords
     poses = torch.zeros((coords.shape[0], 4, 4), dtype=torch.float32, device=coords.device)
     f0, focals = _focal_args(focal, coords.shape[0])
-    dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
-                               inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
-                               image0=image0, image_stride=image_stride, focals=focals)
+    if depth is not None or cam_coords is not None:
+        dsacstar.forward_rgbd_batch(coords, cam_coords, poses, n_hyp, rgbd_threshold, inlier_alpha, max_dist_error,
+                                    image0=image0, image_stride=image_stride, depth=depth, focalLength=f0,
+                                    ppointX=float(image_w / 2), ppointY=float(image_h / 2),
+                                    subSampling=network.OUTPUT_SUBSAMPLE, focals=focals)
+    else:
+        dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
+                                   inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
+                                   image0=image0, image_stride=image_stride, focals=focals)
     if quality:
         rows = dsacstar.pose_quality_batch(coords, poses, threshold, f0, float(image_w / 2), float(image_h / 2),
                                            inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE, focals=focals)
@@ -303,11 +314,15 @@ class PipelinedLocalizer:
             o.record_stream(self.cnn[0])
         return pred, [ev]
 
-    def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False):
+    def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False, depth=None,
+               cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
-        side stream and its rows [B,64] float64 are returned as a third value."""
+        side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
+        RGB-D solver runs in place of the RGB one, as in localize_batch."""
         import dsacstar
+        if depth is not None and cam_coords is not None:
+            raise RuntimeError("submit takes at most one of depth and cam_coords")
         pred, events = self.forward_cnn(images, plant)
         coords = pred[:, :self.net.num_task_channel] if scene_coords is None else scene_coords
         poses = torch.empty((coords.shape[0], 4, 4), dtype=torch.float32, device=coords.device)   # (the solver writes all 16)
@@ -315,9 +330,17 @@ class PipelinedLocalizer:
             self.side.wait_event(ev)
         self.side.wait_stream(torch.cuda.current_stream())      # `poses` / `scene_coords` come from the caller's stream
         with torch.cuda.stream(self.side):
-            dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
-                                       float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
-                                       image0=image0, image_stride=image_stride)
+            if depth is not None or cam_coords is not None:
+                f0, focals = _focal_args(self.focal, coords.shape[0])
+                dsacstar.forward_rgbd_batch(coords, cam_coords, poses, self.n_hyp, rgbd_threshold, self.alpha, max_dist_error,
+                                            image0=image0, image_stride=image_stride, depth=depth, focalLength=f0,
+                                            ppointX=float(self.w / 2), ppointY=float(self.h / 2),
+                                            subSampling=self.net.OUTPUT_SUBSAMPLE, focals=focals)
+                (depth if depth is not None else cam_coords).record_stream(self.side)
+            else:
+                dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
+                                           float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
+                                           image0=image0, image_stride=image_stride)
             if quality:
                 rows = dsacstar.pose_quality_batch(coords, poses, self.thr, self.focal, float(self.w / 2), float(self.h / 2),
                                                    self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE)

@@ -145,8 +145,65 @@ int xl_dsac_pose_quality_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                float thr, float focal, float ppx, float ppy, float alpha, float max_reproj, int sub,
                                const float *focals_dev, double *rows_dev /* [B,64] */, void *stream);
 
-/* Exported for symmetry with the reference module (dsacstar.cpp:889-891); not on CrossLoc's
- * path (no call site in the reference).  They return XL_ERR_UNSUPPORTED. */
+/*
+ * Batched RGB-D forward pass: the solver of dsacstar_rgbd_forward (dsacstar.cpp:495-612) for B independent images in one
+ * launch, one 256-thread workgroup per image.  Every cell has a scene coordinate X (world, metres) and a camera coordinate
+ * p (camera frame, metres); a pose hypothesis is the closed-form rigid (Kabsch) fit p = R X + t of three sampled cells.
+ *
+ *   coords_dev     [B,3,Ho,Wo] float32 scene coordinates, strides (sb, sc, sy, sx) in elements
+ *   cam_dev        [B,3,Ho,Wo] float32 camera coordinates, strides (mb, mc, my, mx), or NULL
+ *   depth_dev      [B,Ho,Wo] float32 depth along the optical axis, strides (db, dy, dx), or NULL.  EXACTLY ONE of cam_dev and
+ *                  depth_dev is non-null (otherwise XL_ERR_ARG).  In depth form the kernel forms the camera coordinate of cell
+ *                  (y, x) itself, in float32 without contraction:  px = x*sub + sub/2, py = y*sub + sub/2 (integers),
+ *                  p = ( ((float)px - ppx) / f * d,  ((float)py - ppy) / f * d,  d )  with f = focals_dev[b] or `focal`;
+ *                  a camera tensor built by the same formula gives the same bits.  focal, ppx, ppy, sub and focals_dev are
+ *                  read in depth form only.
+ *   thr, max_dist  inlierThreshold and maxDistError in CENTIMETRES: distances (metres) are multiplied by 100 before they are
+ *                  compared or clamped (dsacstar_util.h:296, 502)
+ *   alpha          inlierAlpha
+ *   other arguments as in xl_dsac_forward_rgb_batch.  Asynchronous on `stream`.
+ *
+ * Valid cells: a cell is valid iff its camera z is nonzero (zero depth = no measurement).  DEVIATION: the reference tests
+ * channel 0 three times (dsacstar.cpp:522-524), which drops the column x_cam == 0 of an odd-width grid.  The valid list is
+ * ordered x-major (x outer, y inner) like the reference's validPts; draw k of the sampler means its k-th entry.
+ * Sampling: try t of hypothesis h draws three entries draw(try_state(imageKey, h, t), j, nValid), j = 0..2 (repeats allowed),
+ * fits Kabsch on the three pairs and accepts iff all three residuals |p - (R X + t)| * 100 are < thr; the first accepted try
+ * wins; a hypothesis that exhausts max_tries keeps its last fit and is still scored.  With nValid == 0 nothing is sampled
+ * and the identity pose is written.
+ * Kabsch: centroids, centred cross-covariance A = sum (p - c_p)(X - c_X)^T, R = U diag(1, 1, det(U V^T)) V^T, t = c_p - R c_X,
+ * in double (Horn's quaternion form; rank-deficient A gives one of the optimal proper rotations, A = 0 the identity).
+ * Score: err = min((float)(|p - (R X + t)| * 100), max_dist) for valid cells and max_dist for invalid ones, which DO enter the
+ * sum; score = (alpha / Wo / Ho in float) * sum over all Ho*Wo cells of 1 - sigmoid(5/thr (err - thr)); first maximum wins.
+ * Refinement (dsacstar_util.h:611-677): inliers err < thr (float compare); stop when their number is <= the best so far
+ * (initially 3); else re-fit Kabsch on all inliers; at most XL_DSAC_MAX_REF_STEPS rounds.
+ * out_poses_dev: the inverse rigid transform, float32 cam->world 4x4, as xl_dsac_forward_rgb_batch writes it.
+ *
+ * max_tries <= XL_DSAC_RGBD_MAX_TRIES (the try counter is 32 bits wide and advances in steps of 64; tries_dev reports the
+ * exhausted budget as a negative int), otherwise XL_ERR_ARG.
+ * Limit: Ho*Wo <= XL_DSAC_RGBD_MAX_CELLS (the image is staged in the 160 KB LDS of one CU at 26 bytes per cell); larger grids
+ * return XL_ERR_GRID before any launch.  Argument errors are detected before any HIP call.
+ *
+ *   cells_dev      optional [B,n_hyp,3] int32: cells (y*Wo + x) of the accepted try (-1 when nothing was sampled)
+ *   tries_dev      optional [B,n_hyp] int32: tries used (negative: budget exhausted; 0: nothing sampled)
+ *   scores_dev     optional [B,n_hyp] float64 soft-inlier scores
+ *   dbg_dev        optional [B,XL_DSAC_RGBD_DBG_DOUBLES] float64: [0] winner, [1] nValid, [2] refinement rounds, [3] inliers of
+ *                  the last fitted round, [4..12] refined R row-major, [13..15] refined t (world->camera)
+ */
+#define XL_DSAC_RGBD_MAX_CELLS 6144
+#define XL_DSAC_RGBD_DBG_DOUBLES 16
+#define XL_DSAC_RGBD_MAX_TRIES 2147483584u          /* 2^31 - 64 */
+int xl_dsac_forward_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                               const float *cam_dev, int64_t mb, int64_t mc, int64_t my, int64_t mx,
+                               const float *depth_dev, int64_t db, int64_t dy, int64_t dx,
+                               int B, int Ho, int Wo, float *out_poses_dev,
+                               int n_hyp, float thr, float alpha, float max_dist,
+                               float focal, float ppx, float ppy, int sub, const float *focals_dev,
+                               uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                               void *stream,
+                               int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
+
+/* The reference-shaped single-image RGB-D entries (dsacstar.cpp:889-891) are not wired to the solver above yet: they
+ * return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);
 int xl_dsac_backward_rgbd(void);
 

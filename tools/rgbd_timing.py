@@ -1,0 +1,118 @@
+"""Times the RGB-D solver (csrc/xl_dsac_rgbd.hip through dsacstar.forward_rgbd_batch) beside the RGB solver
+(dsacstar.forward_rgb_batch) at the same shapes, with HIP events on warm clocks.  Not a test and not part of bench.py.
+
+  95 frames x 256 hypotheses on 60 x 90 (the bench batch) and 1 frame.  RGB-D: camera-tensor form and depth form, 0.5 m
+  coordinate noise, 1 % depth noise, 30 % outliers, thr 300 cm, maxDist 3000 cm.  RGB: thr 10 px, the bench's arguments.
+
+The sides run alternately in the same process (rounds of `--iters` calls each) after `--warmup` calls; the figure is the
+median over `--rounds` rounds of the per-call time.  The RGB-D poses are checked against ground truth before anything is timed.
+
+    python tools/rgbd_timing.py [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dsacstar                                                 # noqa: E402
+from crossloc_amd import synth                                  # noqa: E402
+
+RGB_ARGS = (10.0, synth.FOCAL, 360.0, 240.0, 100.0, 100.0, 8)   # threshold, focal, ppx, ppy, alpha, max reprojection, subsampling
+RGBD_ARGS = (300.0, 100.0, 3000.0)                              # threshold [cm], alpha, max distance [cm]
+
+
+def time_sides(fns, warmup, iters, rounds):
+    """median per-call milliseconds of every function and the spread over rounds, alternating; a round ends in an event synchronise"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            out[k].append(a.elapsed_time(b) / iters)
+    return [float(np.median(v)) for v in out], [float(np.max(v) - np.min(v)) for v in out]
+
+
+def depth_of(coords_gt, pose, rng, noise):
+    """depth a sensor at `pose` measures of the ground-truth scene coordinates [3,Ho,Wo]: z of R^T (gt - c), multiplicative noise.
+    Every ray of these scenes hits the terrain and no holes are cut, so the timed frames have no invalid cells: all 5400 cells
+    are staged, sampled from and scored (the most work the kernel does per frame)."""
+    z = np.einsum("k,khw->hw", pose[:3, 2], coords_gt.astype(np.float64) - pose[:3, 3][:, None, None])
+    return (z * (1.0 + noise * rng.normal(size=z.shape))).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=21)
+    ap.add_argument("--hypotheses", type=int, default=256)
+    ap.add_argument("--json", type=str, default=None)
+    opt = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rgbd_timing needs the GPU: a timing taken elsewhere says nothing")
+    dev = torch.device("cuda")
+
+    # warm clocks: a second of streaming work before the first timed window
+    x = torch.rand(64 << 20, device=dev)
+    for _ in range(200):
+        x.mul_(1.0000001)
+    torch.cuda.synchronize()
+    del x
+
+    results = []
+    for B in (95, 1):
+        coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
+        rng = np.random.default_rng(7)
+        depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
+        co = torch.from_numpy(coords).to(dev)
+        depth = torch.from_numpy(depth_np).to(dev)
+        cam = dsacstar.camera_coordinates(depth, synth.FOCAL, 480, 720, 8)
+        poses_rgb = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+        poses_cam = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+        poses_dep = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+
+        def rgb():
+            dsacstar.forward_rgb_batch(co, poses_rgb, opt.hypotheses, *RGB_ARGS)
+
+        def rgbd_cam():
+            dsacstar.forward_rgbd_batch(co, cam, poses_cam, opt.hypotheses, *RGBD_ARGS)
+
+        def rgbd_depth():
+            dsacstar.forward_rgbd_batch(co, None, poses_dep, opt.hypotheses, *RGBD_ARGS, depth=depth, focalLength=synth.FOCAL,
+                                        ppointX=360.0, ppointY=240.0, subSampling=8)
+
+        rgb(); rgbd_cam(); rgbd_depth()
+        torch.cuda.synchronize()
+        assert torch.equal(poses_cam, poses_dep)
+        errs = np.array([synth.pose_error(gt_poses[b], poses_cam[b].cpu().numpy().astype(np.float64)) for b in range(B)])
+        errs_rgb = np.array([synth.pose_error(gt_poses[b], poses_rgb[b].cpu().numpy().astype(np.float64)) for b in range(B)])
+        assert errs[:, 0].max() < 2.0 and errs[:, 1].max() < 0.5, errs.max(0)
+        (t_rgb, t_cam, t_dep), (s_rgb, s_cam, s_dep) = time_sides((rgb, rgbd_cam, rgbd_depth), opt.warmup, opt.iters, opt.rounds)
+        results.append(dict(frames=B, hypotheses=opt.hypotheses, grid=[60, 90], rounds=opt.rounds, iters=opt.iters,
+                            rgb_ms=t_rgb, rgb_spread_ms=s_rgb, rgbd_camera_ms=t_cam, rgbd_camera_spread_ms=s_cam,
+                            rgbd_depth_ms=t_dep, rgbd_depth_spread_ms=s_dep, rgbd_over_rgb=t_cam / t_rgb,
+                            rgb_launch_form=int(dsacstar._lib.lib().xl_dsac_forward_sub_blocks(B, opt.hypotheses)),
+                            rgbd_median_t_err_m=float(np.median(errs[:, 0])), rgbd_median_r_err_deg=float(np.median(errs[:, 1])),
+                            rgb_median_t_err_m=float(np.median(errs_rgb[:, 0])), rgb_median_r_err_deg=float(np.median(errs_rgb[:, 1]))))
+    for r in results:
+        print(json.dumps(r))
+    if opt.json:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
+        with open(opt.json, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
