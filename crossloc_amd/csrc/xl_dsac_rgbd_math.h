@@ -8,6 +8,7 @@
  *
  *   crossloc_amd/csrc/xl_dsac_rgbd.hip   the product: staging, ballots, wave / block reductions, selection, refinement loop
  *   tests/dsac_rgbd_ref.c                test infrastructure: the same orchestration restated serially in C99 for gcc
+ * (and, through xl_dsac_rgbd_bwd_math.h, the backward pass: xl_dsac_rgbd_bwd.hip and tests/dsac_rgbd_bwd_ref.c)
  *
  * Arithmetic contract as in xl_dsac_math.h: + - * / sqrt and the header's polynomials only, -ffp-contract=off on both
  * sides, expression order is part of the interface.  Reference line numbers are relative to the reference project's
@@ -97,13 +98,18 @@ XL_MATH_FN void rgbd_acc_cov(double *a, const double *cp, const double *cX,
         }                                                                           \
     } while (0)
 
+/* what the Jacobi sweeps leave behind: all four eigenpairs of N(A) (eigenvector m is the column V[4 i + m], i = 0..3), the
+ * index of the FIRST largest eigenvalue and its eigenvector normalised once more (the quaternion of R).  The backward pass
+ * (xl_dsac_rgbd_bwd_math.h) differentiates the fit through them. */
+typedef struct { double lam[4]; double V[16]; double q[4]; int top; } HornEig;
+
 /* The rigid fit from the centroids and the centred cross-covariance: the proper rotation R maximising trace(R A^T)
  * (= U diag(1, 1, det(U V^T)) V^T of the SVD A = U W V^T) and t = c_p - R c_X.  Horn's closed form: R is the rotation of
  * the unit quaternion that is the eigenvector of the largest eigenvalue of the symmetric 4x4 N(A).  A rank-2 A (three
  * points) or rank <= 1 A (repeated draws) needs no special case: a repeated largest eigenvalue only means that several
  * rotations are optimal, Jacobi still returns an orthonormal eigenbasis, the FIRST largest diagonal entry is taken, and
  * A == 0 leaves V = I, i.e. the identity rotation. */
-XL_MATH_FN void rgbd_kabsch_fit(const double *cp, const double *cX, const double *A, Pose *out)
+XL_MATH_FN void rgbd_kabsch_fit_eig(const double *cp, const double *cX, const double *A, Pose *out, HornEig *e)
 {
     /* S_ab = sum X_a p_b = A[b][a] */
     double Sxx = A[0], Sxy = A[3], Sxz = A[6];
@@ -124,12 +130,21 @@ XL_MATH_FN void rgbd_kabsch_fit(const double *cp, const double *cX, const double
         XLR_ROTATE(1, 2); XLR_ROTATE(1, 3); XLR_ROTATE(2, 3);
     }
     double lam = M[0][0];
+    int top = 0;
     double q0 = V[0][0], qx = V[1][0], qy = V[2][0], qz = V[3][0];
-    if (M[1][1] > lam) { lam = M[1][1]; q0 = V[0][1]; qx = V[1][1]; qy = V[2][1]; qz = V[3][1]; }
-    if (M[2][2] > lam) { lam = M[2][2]; q0 = V[0][2]; qx = V[1][2]; qy = V[2][2]; qz = V[3][2]; }
-    if (M[3][3] > lam) { lam = M[3][3]; q0 = V[0][3]; qx = V[1][3]; qy = V[2][3]; qz = V[3][3]; }
+    if (M[1][1] > lam) { lam = M[1][1]; top = 1; q0 = V[0][1]; qx = V[1][1]; qy = V[2][1]; qz = V[3][1]; }
+    if (M[2][2] > lam) { lam = M[2][2]; top = 2; q0 = V[0][2]; qx = V[1][2]; qy = V[2][2]; qz = V[3][2]; }
+    if (M[3][3] > lam) { lam = M[3][3]; top = 3; q0 = V[0][3]; qx = V[1][3]; qy = V[2][3]; qz = V[3][3]; }
     double nq = sqrt(q0 * q0 + qx * qx + qy * qy + qz * qz);
     q0 = q0 / nq; qx = qx / nq; qy = qy / nq; qz = qz / nq;
+    XL_MATH_UNROLL
+    for (int i = 0; i < 4; ++i) {
+        e->lam[i] = M[i][i];
+        XL_MATH_UNROLL
+        for (int j = 0; j < 4; ++j) e->V[4 * i + j] = V[i][j];
+    }
+    e->q[0] = q0; e->q[1] = qx; e->q[2] = qy; e->q[3] = qz;
+    e->top = top;
     double *R = out->R;
     R[0] = q0 * q0 + qx * qx - qy * qy - qz * qz; R[1] = 2.0 * (qx * qy - q0 * qz); R[2] = 2.0 * (qx * qz + q0 * qy);
     R[3] = 2.0 * (qy * qx + q0 * qz); R[4] = q0 * q0 - qx * qx + qy * qy - qz * qz; R[5] = 2.0 * (qy * qz - q0 * qx);
@@ -140,6 +155,13 @@ XL_MATH_FN void rgbd_kabsch_fit(const double *cp, const double *cX, const double
 }
 
 #undef XLR_ROTATE
+
+/* the fit alone (the forward pass): the eigen-decomposition is dropped */
+XL_MATH_FN void rgbd_kabsch_fit(const double *cp, const double *cX, const double *A, Pose *out)
+{
+    HornEig e;
+    rgbd_kabsch_fit_eig(cp, cX, A, out, &e);
+}
 
 /* ------------------------------------------------------------------------------ cell error, score term, sampling try */
 

@@ -16,7 +16,8 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
     form `backward_rgb_batch` run on the GPU as well.
   * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
-    tensor or a depth map; the reference-shaped `forward_rgbd` / `backward_rgbd` still raise NotImplementedError.
+    tensor or a depth map, and `backward_rgbd_batch` its backward pass (dsacstar.cpp:631-885): the expected pose loss and its
+    gradient w.r.t. the scene coordinates; the reference-shaped `forward_rgbd` / `backward_rgbd` still raise NotImplementedError.
 There is no CPU fallback: without the HIP library the call raises.
 """
 import ctypes
@@ -331,6 +332,77 @@ def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypo
             _ptr(cells), _ptr(tries), _ptr(scores), _ptr(dbg))
     _lib.check(rc)
     return out
+
+
+RGBD_BWD_REC = 64                        # XL_DSAC_RGBD_BWD_REC: doubles per hypothesis in backward_rgbd_batch's debug record
+
+
+def backward_rgbd_batch(sceneCoordinates, cameraCoordinates, outSceneCoordinatesGrad, gtPoses, ransacHypotheses, inlierThreshold,
+                        wLossRot, wLossTrans, softClamp, inlierAlpha, maxDistError, randomSeed, image0=0, image_stride=1,
+                        max_tries=None, debug=False, depth=None, focalLength=None, ppointX=None, ppointY=None, subSampling=None,
+                        focals=None):
+    """RGB-D DSAC* backward pass (dsacstar_rgbd_backward, dsacstar.cpp:631-885) for B images: the expected pose loss over the
+    hypothesis distribution and its gradient w.r.t. the scene coordinates, Kabsch hypotheses from depth.  Tensor rules as in
+    forward_rgbd_batch: sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides), EXACTLY ONE of cameraCoordinates [B,3,Ho,Wo] and
+    depth [B,Ho,Wo] (float32 CUDA, any strides; depth needs focalLength or focals, ppointX, ppointY, subSampling),
+    Ho*Wo <= RGBD_MAX_CELLS, thresholds in centimetres.  outSceneCoordinatesGrad: float32 with the shape of sceneCoordinates, any
+    strides, ACCUMULATED (+=) like backward_rgb_batch.  gtPoses [B,4,4] cam->world.  randomSeed is the sampler's seed: with the
+    seed and image keys of a forward_rgbd_batch call the hypotheses and scores are that call's, bit for bit.  Returns the expected
+    losses as a float64 CUDA tensor [B] (asynchronous on the current stream); with debug=True also the per-hypothesis records
+    [B,nHyp,RGBD_BWD_REC] (layout, deviations from the reference and the two guards: include/crossloc_dsac.h)."""
+    _check_coords(sceneCoordinates, True)
+    if (cameraCoordinates is None) == (depth is None):
+        raise RuntimeError("backward_rgbd_batch takes exactly one of cameraCoordinates and depth")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    other = cameraCoordinates if depth is None else depth
+    if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
+        raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
+    if depth is None and tuple(other.shape) != (B, 3, Ho, Wo):
+        raise RuntimeError("cameraCoordinates must be [B,3,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+    if depth is not None:
+        if tuple(other.shape) != (B, Ho, Wo):
+            raise RuntimeError("depth must be [B,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+        if (focalLength is None and focals is None) or ppointX is None or ppointY is None or subSampling is None:
+            raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
+        if int(subSampling) <= 0:
+            raise RuntimeError("subSampling must be positive")
+    if Ho * Wo > RGBD_MAX_CELLS:
+        raise RuntimeError("backward_rgbd_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
+                           % (Ho * Wo, RGBD_MAX_CELLS))
+    g = outSceneCoordinatesGrad
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != tuple(sceneCoordinates.shape):
+        raise RuntimeError("outSceneCoordinatesGrad must be float32 with the shape of sceneCoordinates")
+    if not isinstance(gtPoses, torch.Tensor) or gtPoses.numel() != B * 16:
+        raise RuntimeError("gtPoses must be a [B,4,4] tensor")
+    if int(ransacHypotheses) <= 0:
+        raise RuntimeError("ransacHypotheses must be positive")
+    if not sceneCoordinates.is_cuda or not other.is_cuda or not g.is_cuda:
+        raise RuntimeError("backward_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    if other.device != dev or g.device != dev:
+        raise RuntimeError("all tensors must be on the device of sceneCoordinates")
+    if focals is not None:
+        focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
+        if focals.numel() != B:
+            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    gt = gtPoses.to(device=dev, dtype=torch.float32).reshape(B, 16).contiguous()
+    loss = torch.zeros((B,), dtype=torch.float64, device=dev)
+    rec = torch.zeros((B, int(ransacHypotheses), RGBD_BWD_REC), dtype=torch.float64, device=dev) if debug else None
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
+    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
+    gb, gc, gy, gx = g.stride()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_backward_rgbd_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
+            B, Ho, Wo, _ptr(g), gb, gc, gy, gx, _ptr(gt), _ptr(loss), int(ransacHypotheses), float(inlierThreshold),
+            float(inlierAlpha), float(maxDistError), float(wLossRot), float(wLossTrans), float(softClamp),
+            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            int(randomSeed), int(image0), int(image_stride),
+            int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream), _ptr(rec))
+    _lib.check(rc)
+    return (loss, rec) if debug else loss
 
 
 def forward_rgbd(*args, **kwargs):

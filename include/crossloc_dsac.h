@@ -202,6 +202,68 @@ int xl_dsac_forward_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                void *stream,
                                int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
 
+/*
+ * Batched RGB-D backward pass: dsacstar_rgbd_backward (dsacstar.cpp:631-885) for B independent images: the DSAC* expectation
+ * of the pose loss over the hypothesis distribution, written to out_loss_dev [B] (float64), and its gradient w.r.t. the scene
+ * coordinates, ACCUMULATED (+=) into grad_dev ([B,3,Ho,Wo] float32, strides (gsb, gsc, gsy, gsx) in elements).  Five launches
+ * on `stream`, no host synchronisation; the workspace comes from hipMallocAsync / hipFreeAsync on `stream`.
+ *
+ *   coords / cam / depth, thr, alpha, max_dist, focal, ppx, ppy, sub, focals_dev, seed, image0, image_stride, max_tries
+ *                  as in xl_dsac_forward_rgbd_batch; the same limits (XL_ERR_ARG, XL_ERR_GRID) are checked before any HIP call
+ *   gt_poses_dev   [B,16] float32 cam->world 4x4, row-major
+ *   w_rot, w_trans, soft_clamp   weights of the pose loss and its soft clamp, as in xl_dsac_backward_rgb_batch
+ *   rec_dev        optional [B,n_hyp,XL_DSAC_RGBD_BWD_REC] float64 per-hypothesis records (layout below)
+ *
+ * Sampling, scores and the selection distribution are the forward pass's: the same sampler keys with `seed`, the same score
+ * bits.  p = softmax(scores); a hypothesis with p < 1e-3 is inactive: it enters the expectation with the loss of its unrefined
+ * pose and gets no gradient.  An active hypothesis is refined with the forward pass's refinement loop; its loss is the pose
+ * loss (dsacstar_loss.h:47-88) of the refined pose.  Expected loss E = sum_h p_h loss_h; soft-max gradient
+ * dE/dscore_h = p_h (loss_h - E).
+ *
+ * Gradient of E w.r.t. the scene coordinate X of a valid cell (an invalid cell gets nothing), hypotheses added in ascending
+ * order in float:  acc = (float)((double)acc + (p_h * gI + gII)).
+ *   Path I  (through the refined pose): the closed-form adjoint of the Horn/Kabsch fit of the last fitted refinement round:
+ *           gI = H^T (p - c_p) - v for the cells of that round's inlier set, H = dloss/dA, v = R^T g_t / n.  dloss/dR and g_t =
+ *           dloss/dt are taken from dLoss (dsacstar_loss.h:99-212) with all its quirks.  None when no round was fitted.
+ *   Path II (through the score): w = -s (1 - s) (5 / thr) dE/dscore_h (alpha / Wo / Ho) per valid cell, s the sigmoid of the
+ *           score term, d^ = d / (|d| + 1e-8) of the metre residual d = p - (R X + t) under the UNREFINED pose; a cell whose
+ *           unclamped float error exceeds max_dist has w = 0.  Direct term gII = w (-100 R^T d^); the three drawn cells also get
+ *           the adjoint of the minimal fit for G_R = sum w (-100 d^ X^T), g_t = sum w (-100 d^) (a repeated draw: every one of
+ *           its columns).
+ * DEVIATIONS from the reference, beside those of the forward pass:
+ *   - the factor 100: the reference differentiates the metre error while its score uses centimetres
+ *     (dsacstar_derivative.h:443-458 against dsacstar_util.h:502); here the gradient is the derivative of the score computed.
+ *   - the Kabsch derivative is analytic everywhere (the reference: SVD backward, central differences for a zero singular
+ *     value, i.e. for every three-point set).
+ *   - eigen-gap guard: a fit whose (lambda_top - lambda_second) / max |lambda| of Horn's 4x4 is <= 1e-8 is not unique
+ *     (collinear or repeated points): the hypothesis contributes nothing through that fit (path I: gI = 0; path II: the
+ *     support-point gradients are 0, the direct term stays) and the record flags it.
+ *   - path-II guard: the same when the largest entry of the 3x9 rotation Jacobian d omega / d X of the support points
+ *     (delta R = [delta omega]x R) exceeds 10 rad/m.  The reference's clamp max |d(rvec, tvec)/dX| > 10
+ *     (dsacstar_derivative.h:638) is NOT taken over: its tvec rows scale with the distance of the scene from the origin.
+ *
+ * Record of hypothesis h (XL_DSAC_RGBD_BWD_REC = 64 doubles); an inactive hypothesis has [0], [1] and zeros:
+ *     [0] prob   [1] loss   [2] active   [3] inliers of the last fitted round (0 if none)   [4] path-I guard flag
+ *     [5] soft-max gradient dE/dscore    [6..17] refined pose: R row-major, t (world->camera)
+ *     [18..26] H row-major   [27..29] v   [30..32] c_p of the final inlier set
+ *     [33..41] support-point gradients [draw j][xyz]   [42] max |d omega / d X| over the support points
+ *     [43] path-II guard flag (eigen-gap of the minimal fit, the rotation Jacobian, or nothing sampled)
+ *     [44..52] G_R row-major and [53..55] g_t: the twelve score sums
+ *     [56] relative eigen-gap of the refined fit   [57] of the minimal fit   [58..63] 0
+ */
+#define XL_DSAC_RGBD_BWD_REC 64
+int xl_dsac_backward_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                const float *cam_dev, int64_t mb, int64_t mc, int64_t my, int64_t mx,
+                                const float *depth_dev, int64_t db, int64_t dy, int64_t dx,
+                                int B, int Ho, int Wo,
+                                float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                                const float *gt_poses_dev, double *out_loss_dev,
+                                int n_hyp, float thr, float alpha, float max_dist,
+                                float w_rot, float w_trans, float soft_clamp,
+                                float focal, float ppx, float ppy, int sub, const float *focals_dev,
+                                uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                                void *stream, double *rec_dev);
+
 /* The reference-shaped single-image RGB-D entries (dsacstar.cpp:889-891) are not wired to the solver above yet: they
  * return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);

@@ -1,0 +1,338 @@
+/*
+ * tests/dsac_rgbd_bwd_ref.c — CPU restatement of the RGB-D DSAC* backward pass (crossloc_amd/csrc/xl_dsac_rgbd_bwd.hip).
+ *
+ * TEST INFRASTRUCTURE ONLY.  The lane-local arithmetic is the product's xl_dsac_rgbd_bwd_math.h, compiled here by gcc as C99
+ * with -ffp-contract=off.  This file restates serially what kernels K0-K4 do in parallel around it, with their reduction
+ * orders: K0 is the forward restatement's sampling and scoring (tests/dsac_rgbd_ref.c, included below), K1 the refinement's
+ * walk of 256 virtual threads with the waves added in order, K2 the serial expectation, K3 the twelve sums per virtual thread
+ * and their block reduction, K4 the per-cell assembly over the hypotheses in ascending order with float accumulation.
+ * Bitwise GPU == this file checks the kernels' orchestration; the formulas are checked against tests/indep_dsac_rgbd_bwd.py
+ * (numpy SVD Kabsch and central differences), which shares no code with the header.
+ *
+ * With -DXB_MAIN the file is a program of its own (for the sanitizer run): see main() at the end.
+ */
+#include "dsac_rgbd_ref.c"            /* staging, butterflies, block reduction, the forward restatement (K0) */
+#include "xl_dsac_rgbd_bwd_math.h"    /* crossloc_amd/csrc: shared with the kernels */
+
+#define XB_REC XLR_BWD_REC
+
+typedef struct { unsigned finalInl; int rounds; double cp[3], cX[3], a[XLR_SUMS_COV]; } XbRefine;
+
+/* the refinement loop of the forward restatement for one hypothesis; inl [nValid] = the inlier set of the last FITTED round */
+static void xb_refine(const Staged *S, int nValid, float thr, float maxDist, Pose *pose, XbRefine *ro, uint8_t *inlOut,
+                      uint8_t *inl, double *part)
+{
+    unsigned best = 3;
+    memset(ro, 0, sizeof(*ro));
+    memset(inlOut, 0, (size_t)(nValid > 0 ? nValid : 1));
+    for (int step = 0; step < XR_MAX_REF_STEPS; ++step) {
+        unsigned cnt = 0;
+        for (int k = 0; k < nValid; ++k) {
+            inl[k] = xr_err(S, pose, k, maxDist) < thr;
+            cnt += inl[k];
+        }
+        if (cnt <= best) break;
+        best = cnt;
+        double s[XLR_SUMS_CENTROID], a[XLR_SUMS_COV], cp[3], cX[3];
+        for (int tid = 0; tid < XR_T; ++tid) {
+            double *v = part + tid * XLR_SUMS_CENTROID;
+            for (int k = 0; k < XLR_SUMS_CENTROID; ++k) v[k] = 0.0;
+            for (int k = tid; k < nValid; k += XR_T)
+                if (inl[k]) rgbd_acc_centroid(v, (double)S->p[0][k], (double)S->p[1][k], (double)S->p[2][k],
+                                              (double)S->X[0][k], (double)S->X[1][k], (double)S->X[2][k]);
+        }
+        xr_block_reduce(part, XLR_SUMS_CENTROID, s);
+        rgbd_centroids(s, cp, cX);
+        for (int tid = 0; tid < XR_T; ++tid) {
+            double *v = part + tid * XLR_SUMS_COV;
+            for (int k = 0; k < XLR_SUMS_COV; ++k) v[k] = 0.0;
+            for (int k = tid; k < nValid; k += XR_T)
+                if (inl[k]) rgbd_acc_cov(v, cp, cX, (double)S->p[0][k], (double)S->p[1][k], (double)S->p[2][k],
+                                         (double)S->X[0][k], (double)S->X[1][k], (double)S->X[2][k]);
+        }
+        xr_block_reduce(part, XLR_SUMS_COV, a);
+        rgbd_kabsch_fit(cp, cX, a, pose);
+        ro->finalInl = cnt;
+        ++ro->rounds;
+        memcpy(inlOut, inl, (size_t)nValid);
+        for (int i = 0; i < 3; ++i) { ro->cp[i] = cp[i]; ro->cX[i] = cX[i]; }
+        for (int i = 0; i < XLR_SUMS_COV; ++i) ro->a[i] = a[i];
+    }
+}
+
+static void xb_load_pose(const double *src, Pose *p)
+{
+    for (int i = 0; i < 9; ++i) p->R[i] = src[i];
+    for (int i = 0; i < 3; ++i) p->t[i] = src[9 + i];
+}
+
+/*
+ * One image.  grad [3,Ho,Wo] float32 (strides gc, gy, gx) is ACCUMULATED.  rec [nHyp, 64] as the kernels write it.  Optional
+ * outputs: cells [nHyp,3] (cell indices of the drawn places, -1: nothing sampled), scores [nHyp], hypPoses [nHyp,12] (the
+ * unrefined poses) and masks [nHyp, Ho*Wo] (per cell: member of the inlier set of the last fitted round).
+ */
+int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
+                     const float *cam, int64_t cc, int64_t cy, int64_t cx, const float *depth, int64_t dy, int64_t dx,
+                     int Ho, int Wo, float *grad, int64_t gc, int64_t gy, int64_t gx, const float *gt16,
+                     int nHyp, float thr, float alpha, float maxDist, float wRot, float wTrans, float softClamp,
+                     float focal, float ppx, float ppy, int sub, uint64_t seed, uint64_t image, uint32_t maxTries,
+                     double *outLoss, double *rec, int32_t *cells, double *scoresOut, double *hypPosesOut, uint8_t *masksOut)
+{
+    if (!coords || !grad || !gt16 || !outLoss || !rec || (cam == NULL) == (depth == NULL) || Ho <= 0 || Wo <= 0 || nHyp <= 0 ||
+        maxTries == 0)
+        return -1;
+    if (!cam && sub <= 0) return -1;
+    const int N = Ho * Wo;
+    if (N > XR_MAX_CELLS) return -2;
+
+    /* ---- K0: the forward restatement's sampling and scoring */
+    int32_t *cellOf = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nHyp);
+    double *scores = (double *)malloc(sizeof(double) * (size_t)nHyp);
+    double *hyp = (double *)malloc(sizeof(double) * 12 * (size_t)nHyp);
+    float pose16[16];
+    int st = xr_forward_rgbd(coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, nHyp, thr, alpha, maxDist, focal, ppx, ppy,
+                             sub, seed, image, maxTries, pose16, cellOf, NULL, scores, NULL, hyp, NULL, NULL, NULL);
+    if (st != 0) { free(hyp); free(scores); free(cellOf); return st; }
+    Staged S;
+    const int nValid = xr_stage(&S, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, focal, ppx, ppy, sub);
+    int32_t *placeOf = (int32_t *)malloc(sizeof(int32_t) * (size_t)N);
+    for (int i = 0; i < N; ++i) placeOf[i] = -1;
+    for (int k = 0; k < nValid; ++k) placeOf[S.cell[k]] = k;
+    int32_t *places = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nHyp);
+    for (int i = 0; i < 3 * nHyp; ++i) places[i] = (cellOf[i] >= 0) ? placeOf[cellOf[i]] : -1;
+
+    const float beta = 5.0f / thr;
+    const float facf = alpha / (float)Wo / (float)Ho;
+    Gt gt;
+    gt_from_pose16(gt16, &gt);
+    uint8_t *masks = (uint8_t *)calloc((size_t)nHyp * (size_t)(nValid > 0 ? nValid : 1), 1);
+    uint8_t *inl = (uint8_t *)malloc((size_t)(nValid > 0 ? nValid : 1));
+    double *part = (double *)malloc(sizeof(double) * XR_T * 12);
+
+    /* ---- K1: probability, refinement, loss, path-I quantities */
+    for (int h = 0; h < nHyp; ++h) {
+        double *r = rec + (size_t)h * XB_REC;
+        for (int i = 0; i < XB_REC; ++i) r[i] = 0.0;
+        const double prob = rgbd_softmax_prob(scores, nHyp, h);
+        Pose pose;
+        xb_load_pose(hyp + 12 * h, &pose);
+        if (prob < XLM_PROB_THRESH) {
+            r[0] = prob;
+            r[1] = pose_loss(&pose, &gt, (double)wRot, (double)wTrans, (double)softClamp);
+            continue;
+        }
+        XbRefine ro;
+        xb_refine(&S, nValid, thr, maxDist, &pose, &ro, masks + (size_t)h * (size_t)(nValid > 0 ? nValid : 1), inl, part);
+        const double loss = pose_loss(&pose, &gt, (double)wRot, (double)wTrans, (double)softClamp);
+        double H[9] = { 0 }, v[3] = { 0 }, gap = 0.0;
+        int guardI = 0;
+        if (ro.rounds > 0) {
+            Pose again;
+            HornEig e;
+            rgbd_kabsch_fit_eig(ro.cp, ro.cX, ro.a, &again, &e);
+            guardI = rgbd_eig_gap(&e, &gap) ? 1 : 0;
+            if (!guardI) {
+                double GR[9], g3[3];
+                rgbd_loss_grad(&pose, &gt, (double)wRot, (double)wTrans, (double)softClamp, GR, g3);
+                rgbd_kabsch_adjoint(&e, ro.cX, GR, g3, H);
+                rgbd_Rt_mul_div(pose.R, g3, (double)ro.finalInl, v);
+            }
+        }
+        r[0] = prob; r[1] = loss; r[2] = 1.0; r[3] = (double)ro.finalInl; r[4] = (double)guardI;
+        xr_store12(&pose, r + 6);
+        for (int i = 0; i < 9; ++i) r[18 + i] = H[i];
+        for (int i = 0; i < 3; ++i) { r[27 + i] = v[i]; r[30 + i] = ro.cp[i]; }
+        r[56] = gap;
+    }
+
+    /* ---- K2: expected loss, soft-max gradient */
+    {
+        double e = 0.0;
+        for (int h = 0; h < nHyp; ++h) e += rec[(size_t)h * XB_REC] * rec[(size_t)h * XB_REC + 1];
+        *outLoss = e;
+        for (int i = 0; i < nHyp; ++i) {
+            const double pi = rec[(size_t)i * XB_REC];
+            if (pi < XLM_PROB_THRESH) continue;
+            double g = pi * rec[(size_t)i * XB_REC + 1];
+            for (int j = 0; j < nHyp; ++j) g -= pi * rec[(size_t)j * XB_REC] * rec[(size_t)j * XB_REC + 1];
+            rec[(size_t)i * XB_REC + 5] = g;
+        }
+    }
+
+    /* ---- K3: the twelve sums, the minimal fit's adjoint, support-point gradients */
+    for (int h = 0; h < nHyp; ++h) {
+        double *r = rec + (size_t)h * XB_REC;
+        if (r[0] < XLM_PROB_THRESH) continue;
+        Pose init;
+        xb_load_pose(hyp + 12 * h, &init);
+        const double sog = r[5];
+        for (int tid = 0; tid < XR_T; ++tid) {
+            double *s = part + tid * 12;
+            for (int i = 0; i < 12; ++i) s[i] = 0.0;
+            for (int k = tid; k < nValid; k += XR_T) {
+                double w, dhat[3];
+                const double X = (double)S.X[0][k], Y = (double)S.X[1][k], Z = (double)S.X[2][k];
+                if (rgbd_cell_weight(&init, X, Y, Z, (double)S.p[0][k], (double)S.p[1][k], (double)S.p[2][k], maxDist, beta, thr, sog,
+                                     facf, &w, dhat))
+                    rgbd_acc_score_sums(s, w, dhat, X, Y, Z);
+            }
+        }
+        double sum[12];
+        xr_block_reduce(part, 12, sum);          /* (component-wise: the kernel's reductions of 9 and of 3 give the same bits) */
+        const double *sR = sum, *sT = sum + 9;
+        const int32_t *pl = places + 3 * h;
+        double sup[9] = { 0 }, maxW = 0.0, gap = 0.0;
+        int guardII = 1;
+        if (pl[0] >= 0 && pl[1] >= 0 && pl[2] >= 0) {
+            double pc[9], Xw[9], cp[3], cX[3];
+            for (int j = 0; j < 3; ++j)
+                for (int c = 0; c < 3; ++c) { pc[3 * j + c] = (double)S.p[c][pl[j]]; Xw[3 * j + c] = (double)S.X[c][pl[j]]; }
+            Pose fit;
+            HornEig e;
+            rgbd_fit3_eig(pc, Xw, &fit, &e, cp, cX);
+            guardII = rgbd_eig_gap(&e, &gap) ? 1 : 0;
+            if (!guardII) {
+                maxW = rgbd_max_domega(&e, &init, pc, cp, cX);
+                if (!(maxW <= XLR_MAX_DOMEGA)) guardII = 1;
+            }
+            if (!guardII) {
+                double H[9], v[3];
+                rgbd_kabsch_adjoint(&e, cX, sR, sT, H);
+                rgbd_Rt_mul_div(init.R, sT, 3.0, v);
+                for (int j = 0; j < 3; ++j) {
+                    double g[3];
+                    rgbd_Ht_mul(H, pc[3 * j] - cp[0], pc[3 * j + 1] - cp[1], pc[3 * j + 2] - cp[2], g);
+                    for (int c = 0; c < 3; ++c) sup[3 * j + c] = g[c] - v[c];
+                }
+            }
+        }
+        for (int i = 0; i < 9; ++i) r[33 + i] = sup[i];
+        r[42] = maxW; r[43] = (double)guardII;
+        for (int i = 0; i < 12; ++i) r[44 + i] = sum[i];
+        r[57] = gap;
+    }
+
+    /* ---- K4: assembly per valid cell */
+    for (int i = 0; i < N; ++i) {
+        const int place = placeOf[i];
+        if (place < 0) continue;
+        const int y = i / Wo, x = i - y * Wo;
+        const double X = (double)S.X[0][place], Y = (double)S.X[1][place], Z = (double)S.X[2][place];
+        const double px = (double)S.p[0][place], py = (double)S.p[1][place], pz = (double)S.p[2][place];
+        float *g = grad + (int64_t)y * gy + (int64_t)x * gx;
+        float acc[3] = { g[0], g[gc], g[2 * gc] };
+        for (int h = 0; h < nHyp; ++h) {
+            const double *r = rec + (size_t)h * XB_REC;
+            const double prob = r[0];
+            if (prob < XLM_PROB_THRESH) continue;
+            double gI[3] = { 0.0, 0.0, 0.0 };
+            if (r[3] > 0.0 && r[4] == 0.0 && masks[(size_t)h * (size_t)nValid + (size_t)place]) {
+                rgbd_Ht_mul(r + 18, px - r[30], py - r[31], pz - r[32], gI);
+                gI[0] = gI[0] - r[27]; gI[1] = gI[1] - r[28]; gI[2] = gI[2] - r[29];
+            }
+            Pose init;
+            xb_load_pose(hyp + 12 * h, &init);
+            double jac[3] = { 0.0, 0.0, 0.0 }, w, dhat[3];
+            if (rgbd_cell_weight(&init, X, Y, Z, px, py, pz, maxDist, beta, thr, r[5], facf, &w, dhat))
+                rgbd_cell_direct(&init, w, dhat, jac);
+            for (int j = 0; j < 3; ++j)
+                if (places[3 * h + j] == place)
+                    for (int k = 0; k < 3; ++k) jac[k] += r[33 + 3 * j + k];
+            for (int k = 0; k < 3; ++k) acc[k] = (float)((double)acc[k] + (prob * gI[k] + jac[k]));
+        }
+        g[0] = acc[0]; g[gc] = acc[1]; g[2 * gc] = acc[2];
+    }
+
+    if (cells) memcpy(cells, cellOf, sizeof(int32_t) * 3 * (size_t)nHyp);
+    if (scoresOut) memcpy(scoresOut, scores, sizeof(double) * (size_t)nHyp);
+    if (hypPosesOut) memcpy(hypPosesOut, hyp, sizeof(double) * 12 * (size_t)nHyp);
+    if (masksOut) {
+        memset(masksOut, 0, (size_t)nHyp * (size_t)N);
+        for (int h = 0; h < nHyp; ++h)
+            for (int k = 0; k < nValid; ++k)
+                if (masks[(size_t)h * (size_t)nValid + (size_t)k]) masksOut[(size_t)h * (size_t)N + (size_t)S.cell[k]] = 1;
+    }
+    free(part); free(inl); free(masks); free(places); free(placeOf);
+    xr_free(&S);
+    free(hyp); free(scores); free(cellOf);
+    return 0;
+}
+
+/* --- hooks for the formula tests: thin calls into the shared header --- */
+
+/* the Kabsch adjoint on n pairs (p camera, X scene, [n,3] doubles; sums taken serially) for G_R [9] and g_t [3]:
+ * gradOut [n,3] = dL/dX_k (all zero when the guard fires), out12 = the fit, relGap; returns the guard flag */
+int xb_test_adjoint(int n, const double *p, const double *X, const double *GR, const double *gt, double *gradOut, double *out12,
+                    double *relGap)
+{
+    double s[XLR_SUMS_CENTROID] = { 0 }, a[XLR_SUMS_COV] = { 0 }, cp[3], cX[3];
+    for (int i = 0; i < n; ++i) rgbd_acc_centroid(s, p[3 * i], p[3 * i + 1], p[3 * i + 2], X[3 * i], X[3 * i + 1], X[3 * i + 2]);
+    rgbd_centroids(s, cp, cX);
+    for (int i = 0; i < n; ++i) rgbd_acc_cov(a, cp, cX, p[3 * i], p[3 * i + 1], p[3 * i + 2], X[3 * i], X[3 * i + 1], X[3 * i + 2]);
+    Pose o;
+    HornEig e;
+    rgbd_kabsch_fit_eig(cp, cX, a, &o, &e);
+    xr_store12(&o, out12);
+    const int guard = rgbd_eig_gap(&e, relGap) ? 1 : 0;
+    for (int i = 0; i < 3 * n; ++i) gradOut[i] = 0.0;
+    if (guard) return 1;
+    double H[9], v[3];
+    rgbd_kabsch_adjoint(&e, cX, GR, gt, H);
+    rgbd_Rt_mul_div(o.R, gt, (double)n, v);
+    for (int i = 0; i < n; ++i) {
+        double g[3];
+        rgbd_Ht_mul(H, p[3 * i] - cp[0], p[3 * i + 1] - cp[1], p[3 * i + 2] - cp[2], g);
+        for (int c = 0; c < 3; ++c) gradOut[3 * i + c] = g[c] - v[c];
+    }
+    return 0;
+}
+
+void xb_test_softmax(const double *scores, int n, double *probs)
+{
+    for (int h = 0; h < n; ++h) probs[h] = rgbd_softmax_prob(scores, n, h);
+}
+
+/* pose_loss of a world->camera pose (R row-major, t) against a float cam->world ground truth */
+double xb_test_pose_loss(const double *Rt12, const float *gt16, double wRot, double wTrans, double cut)
+{
+    Pose p;
+    Gt g;
+    xb_load_pose(Rt12, &p);
+    gt_from_pose16(gt16, &g);
+    return pose_loss(&p, &g, wRot, wTrans, cut);
+}
+
+#ifdef XB_MAIN
+/* dsac_rgbd_bwd_ref FILE Ho Wo nHyp thr maxDist: FILE holds float32 coords [3,Ho,Wo], camera coordinates [3,Ho,Wo] and the
+ * ground-truth pose [16].  Runs the camera form, then the depth form on the camera tensor's z plane; prints both losses. */
+int main(int argc, char **argv)
+{
+    if (argc != 7) { fprintf(stderr, "usage: %s FILE Ho Wo nHyp thr maxDist\n", argv[0]); return 2; }
+    const int Ho = atoi(argv[2]), Wo = atoi(argv[3]), nHyp = atoi(argv[4]);
+    const float thr = (float)atof(argv[5]), maxDist = (float)atof(argv[6]);
+    if (Ho <= 0 || Wo <= 0 || nHyp <= 0 || Ho * Wo > XR_MAX_CELLS) return 2;
+    const size_t N = (size_t)Ho * (size_t)Wo;
+    float *buf = (float *)malloc(sizeof(float) * (6 * N + 16));
+    FILE *f = fopen(argv[1], "rb");
+    if (!f || fread(buf, sizeof(float), 6 * N + 16, f) != 6 * N + 16) { fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
+    fclose(f);
+    float *grad = (float *)calloc(3 * N, sizeof(float));
+    double *rec = (double *)malloc(sizeof(double) * XB_REC * (size_t)nHyp);
+    int32_t *cells = (int32_t *)malloc(sizeof(int32_t) * 3 * (size_t)nHyp);
+    double *scores = (double *)malloc(sizeof(double) * (size_t)nHyp), *hyp = (double *)malloc(sizeof(double) * 12 * (size_t)nHyp);
+    uint8_t *masks = (uint8_t *)malloc(N * (size_t)nHyp);
+    double loss = 0.0, loss2 = 0.0;
+    int st = xb_backward_rgbd(buf, (int64_t)N, Wo, 1, buf + 3 * N, (int64_t)N, Wo, 1, NULL, 0, 0, Ho, Wo, grad, (int64_t)N, Wo, 1,
+                              buf + 6 * N, nHyp, thr, 100.0f, maxDist, 1.0f, 100.0f, 1.0e6f, 480.0f, Wo * 4.0f, Ho * 4.0f, 8, 1305, 0,
+                              1000000u, &loss, rec, cells, scores, hyp, masks);
+    double gsum = 0.0;
+    for (size_t i = 0; i < 3 * N; ++i) gsum += fabs((double)grad[i]);
+    printf("camera form: status %d loss %.9g sum |grad| %.9g\n", st, loss, gsum);
+    int st2 = xb_backward_rgbd(buf, (int64_t)N, Wo, 1, NULL, 0, 0, 0, buf + 5 * N, Wo, 1, Ho, Wo, grad, (int64_t)N, Wo, 1,
+                               buf + 6 * N, nHyp, thr, 100.0f, maxDist, 1.0f, 100.0f, 50.0f, 480.0f, Wo * 4.0f, Ho * 4.0f, 8, 1305, 0,
+                               1000000u, &loss2, rec, NULL, NULL, NULL, NULL);
+    printf("depth form: status %d loss %.9g\n", st2, loss2);
+    free(masks); free(hyp); free(scores); free(cells); free(rec); free(grad); free(buf);
+    return (st == 0 && st2 == 0) ? 0 : 1;
+}
+#endif

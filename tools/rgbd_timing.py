@@ -8,6 +8,12 @@ The sides run alternately in the same process (rounds of `--iters` calls each) a
 median over `--rounds` rounds of the per-call time.  The RGB-D poses are checked against ground truth before anything is timed.
 
     python tools/rgbd_timing.py [--json out.json]
+
+With --backward the two backward passes are timed instead, alternately in the same way: dsacstar.backward_rgbd_batch (camera-tensor
+form) beside dsacstar.backward_rgb_batch at 24 frames x 256 hypotheses on 60 x 90 and at 1 frame, pose-loss weights 1 / 100, soft
+clamp 100, against the scenes' ground-truth poses.  Each call accumulates into its own gradient tensor.
+
+    python tools/rgbd_timing.py --backward [--json out.json]
 """
 import argparse
 import json
@@ -52,6 +58,39 @@ def depth_of(coords_gt, pose, rng, noise):
     return (z * (1.0 + noise * rng.normal(size=z.shape))).astype(np.float32)
 
 
+def backward_results(opt, dev):
+    """one dict per batch size: per-call milliseconds of backward_rgb_batch and backward_rgbd_batch, alternately"""
+    results = []
+    for B in (24, 1):
+        coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
+        rng = np.random.default_rng(7)
+        depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
+        co = torch.from_numpy(coords).to(dev)
+        cam = dsacstar.camera_coordinates(torch.from_numpy(depth_np).to(dev), synth.FOCAL, 480, 720, 8)
+        poses = torch.from_numpy(np.asarray(gt_poses, np.float32)).to(dev)
+        g_rgb, g_rgbd = torch.zeros_like(co), torch.zeros_like(co)
+        losses = {}
+
+        def rgb():
+            losses["rgb"] = dsacstar.backward_rgb_batch(co, g_rgb, poses, opt.hypotheses, RGB_ARGS[0], RGB_ARGS[1], RGB_ARGS[2],
+                                                        RGB_ARGS[3], 1.0, 100.0, 100.0, RGB_ARGS[4], RGB_ARGS[5], RGB_ARGS[6], 1305)
+
+        def rgbd():
+            losses["rgbd"] = dsacstar.backward_rgbd_batch(co, cam, g_rgbd, poses, opt.hypotheses, RGBD_ARGS[0], 1.0, 100.0, 100.0,
+                                                          RGBD_ARGS[1], RGBD_ARGS[2], 1305)
+
+        rgb(); rgbd()
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(g_rgb).all()) and bool(torch.isfinite(g_rgbd).all()) and bool(g_rgbd.abs().max() > 0)
+        first = {k: v.cpu().numpy() for k, v in losses.items()}
+        (t_rgb, t_rgbd), (s_rgb, s_rgbd) = time_sides((rgb, rgbd), opt.warmup, opt.iters, opt.rounds)
+        results.append(dict(mode="backward", frames=B, hypotheses=opt.hypotheses, grid=[60, 90], rounds=opt.rounds, iters=opt.iters,
+                            rgb_backward_ms=t_rgb, rgb_backward_spread_ms=s_rgb, rgbd_backward_ms=t_rgbd,
+                            rgbd_backward_spread_ms=s_rgbd, rgbd_over_rgb=t_rgbd / t_rgb,
+                            rgb_mean_expected_loss=float(first["rgb"].mean()), rgbd_mean_expected_loss=float(first["rgbd"].mean())))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -59,6 +98,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=21)
     ap.add_argument("--hypotheses", type=int, default=256)
     ap.add_argument("--json", type=str, default=None)
+    ap.add_argument("--backward", action="store_true", help="time backward_rgbd_batch beside backward_rgb_batch instead")
     opt = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rgbd_timing needs the GPU: a timing taken elsewhere says nothing")
@@ -71,8 +111,8 @@ def main():
     torch.cuda.synchronize()
     del x
 
-    results = []
-    for B in (95, 1):
+    results = backward_results(opt, dev) if opt.backward else []
+    for B in (() if opt.backward else (95, 1)):
         coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
         rng = np.random.default_rng(7)
         depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
