@@ -171,6 +171,38 @@ XL_MATH_FN bool quality_inv6(const double *ut, double *inv)
     return ok;
 }
 
+/* what follows from the pose covariance S (full 6x6, row-major, parameters (w, d) as above) at the world -> camera pose:
+ * row[52..57] the covariance of the camera centre, row[8] sigma_pos_m, row[9] sigma_rot_deg.  Shared with the RGB-D row
+ * (xl_dsac_rgbd_quality_math.h). */
+XL_MATH_CALL_FN void quality_center_tail(const double *S, const Pose *pose, double *row)
+{
+    /* camera centre C = -R^T t in world coordinates: dC = A (w, d) with A = [ -R^T [t]x , -R^T ] (3x6) */
+    const double *R = pose->R, *t = pose->t;
+    const double tx[9] = { 0.0, -t[2], t[1], t[2], 0.0, -t[0], -t[1], t[0], 0.0 };
+    double A[18], AS[18];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            A[6 * i + j] = -(R[i] * tx[j] + R[3 + i] * tx[3 + j] + R[6 + i] * tx[6 + j]);
+            A[6 * i + 3 + j] = -R[3 * j + i];
+        }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 6; ++j) {
+            double v = 0.0;
+            for (int m = 0; m < 6; ++m) v += A[6 * i + m] * S[6 * m + j];
+            AS[6 * i + j] = v;
+        }
+    double SC[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            double v = 0.0;
+            for (int m = 0; m < 6; ++m) v += AS[6 * i + m] * A[6 * j + m];
+            SC[3 * i + j] = v;
+        }
+    row[52] = SC[0]; row[53] = SC[1]; row[54] = SC[2]; row[55] = SC[4]; row[56] = SC[5]; row[57] = SC[8];
+    row[8] = sqrt(SC[0] + SC[4] + SC[8]);
+    row[9] = sqrt(S[0] + S[7] + S[14]) * (180.0 / XLM_CV_PI);
+}
+
 /* the per-image step from the 32 reduced sums to the output row (layout: include/crossloc_dsac.h).  pose: world -> camera;
  * poseOk false: a pose entry was not finite and the sums were not formed. */
 XL_MATH_CALL_FN void quality_row(const double *s, const Pose *pose, const Cam *cam, bool poseOk, double *row)
@@ -207,31 +239,7 @@ XL_MATH_CALL_FN void quality_row(const double *s, const Pose *pose, const Cam *c
         for (int r = 0; r < 6; ++r)
             for (int c = r; c < 6; ++c) row[31 + k++] = S[6 * r + c];
     }
-    /* camera centre C = -R^T t in world coordinates: dC = A (w, d) with A = [ -R^T [t]x , -R^T ] (3x6) */
-    const double *R = pose->R, *t = pose->t;
-    const double tx[9] = { 0.0, -t[2], t[1], t[2], 0.0, -t[0], -t[1], t[0], 0.0 };
-    double A[18], AS[18];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            A[6 * i + j] = -(R[i] * tx[j] + R[3 + i] * tx[3 + j] + R[6 + i] * tx[6 + j]);
-            A[6 * i + 3 + j] = -R[3 * j + i];
-        }
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 6; ++j) {
-            double v = 0.0;
-            for (int m = 0; m < 6; ++m) v += A[6 * i + m] * S[6 * m + j];
-            AS[6 * i + j] = v;
-        }
-    double SC[9];
-    for (int i = 0; i < 3; ++i)
-        for (int j = i; j < 3; ++j) {
-            double v = 0.0;
-            for (int m = 0; m < 6; ++m) v += AS[6 * i + m] * A[6 * j + m];
-            SC[3 * i + j] = v;
-        }
-    row[52] = SC[0]; row[53] = SC[1]; row[54] = SC[2]; row[55] = SC[4]; row[56] = SC[5]; row[57] = SC[8];
-    row[8] = sqrt(SC[0] + SC[4] + SC[8]);
-    row[9] = sqrt(S[0] + S[7] + S[14]) * (180.0 / XLM_CV_PI);
+    quality_center_tail(S, pose, row);
 }
 
 #endif  /* XL_DSAC_QUALITY_MATH_H */

@@ -18,6 +18,8 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
   * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
     tensor or a depth map, and `backward_rgbd_batch` its backward pass (dsacstar.cpp:631-885): the expected pose loss and its
     gradient w.r.t. the scene coordinates; the reference-shaped `forward_rgbd` / `backward_rgbd` still raise NotImplementedError.
+  * `pose_quality_batch` / `pose_quality_rgbd_batch` rate one given pose per image (inlier statistics, JtJ, covariance) by its
+    reprojection residuals and by its metric 3-D residuals.
 There is no CPU fallback: without the HIP library the call raises.
 """
 import ctypes
@@ -403,6 +405,66 @@ def backward_rgbd_batch(sceneCoordinates, cameraCoordinates, outSceneCoordinates
             int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream), _ptr(rec))
     _lib.check(rc)
     return (loss, rec) if debug else loss
+
+
+# field name -> column (or columns) of a pose_quality_rgbd_batch row; layout and meaning: include/crossloc_dsac.h.  The columns
+# the RGB row shares keep their position (QUALITY_FIELDS); sigma_m takes the place of sigma_px
+RGBD_QUALITY_FIELDS = {
+    "n_cells": 0, "n_inliers": 1, "soft_score": 2, "sum_err": 3, "sum_err2": 4, "sse": 5, "status": 6,
+    "sigma_m": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
+    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58), "n_valid": 58, "reserved": slice(59, 64),
+}
+
+
+def pose_quality_rgbd_batch(sceneCoordinates, cameraCoordinates, poses, inlierThreshold, inlierAlpha, maxDistError, depth=None,
+                            focalLength=None, ppointX=None, ppointY=None, subSampling=None, focals=None):
+    """How far the RGB-D poses of B images can be trusted: inlier statistics of the metric 3-D residuals p - (R X + t), their
+    JtJ over the inliers and the covariance of the rigid least-squares fit, at the given pose of each image (usually what
+    forward_rgbd_batch wrote; enqueue this behind it on the same stream).  Tensor rules as in forward_rgbd_batch, without its
+    cell limit: sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, any grid size), EXACTLY ONE of cameraCoordinates
+    [B,3,Ho,Wo] and depth [B,Ho,Wo] (float32 CUDA, any strides; depth needs focalLength or focals, ppointX, ppointY, subSampling),
+    thresholds in centimetres; poses [B,4,4] float32 CUDA contiguous cam->world.  Returns a float64 CUDA tensor [B,64]
+    (RGBD_QUALITY_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    _check_coords(sceneCoordinates, True)
+    if (cameraCoordinates is None) == (depth is None):
+        raise RuntimeError("pose_quality_rgbd_batch takes exactly one of cameraCoordinates and depth")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    other = cameraCoordinates if depth is None else depth
+    if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
+        raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
+    if depth is None and tuple(other.shape) != (B, 3, Ho, Wo):
+        raise RuntimeError("cameraCoordinates must be [B,3,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+    if depth is not None:
+        if tuple(other.shape) != (B, Ho, Wo):
+            raise RuntimeError("depth must be [B,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
+        if (focalLength is None and focals is None) or ppointX is None or ppointY is None or subSampling is None:
+            raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
+        if int(subSampling) <= 0:
+            raise RuntimeError("subSampling must be positive")
+    if not isinstance(poses, torch.Tensor) or not sceneCoordinates.is_cuda or not other.is_cuda or not poses.is_cuda:
+        raise RuntimeError("pose_quality_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    if other.device != dev or poses.device != dev:
+        raise RuntimeError("all tensors must be on the device of sceneCoordinates")
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
+        raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
+    if focals is not None:
+        focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
+        if focals.numel() != B:
+            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    rows = torch.empty((B, QUALITY_DOUBLES), dtype=torch.float64, device=dev)      # (the kernel writes all 64 of every row)
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
+    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_pose_quality_rgbd_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
+            B, Ho, Wo, _ptr(poses), float(inlierThreshold), float(inlierAlpha), float(maxDistError),
+            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            _ptr(rows), ctypes.c_void_p(stream))
+    _lib.check(rc)
+    return rows
 
 
 def forward_rgbd(*args, **kwargs):

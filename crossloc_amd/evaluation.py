@@ -224,6 +224,18 @@ def _focal_args(focal, n):
     return float(f[0]), f
 
 
+def _is_rgbd_quality(quality):
+    return isinstance(quality, str) and quality == "rgbd"
+
+
+def _check_quality_mode(quality, depth, cam_coords):
+    """`quality`: False, True (the reprojection pass) or "rgbd" (the 3-D pass, which needs the RGB-D solver's inputs)"""
+    if isinstance(quality, str) and quality != "rgbd":
+        raise RuntimeError("quality must be False, True or \"rgbd\", got %r" % (quality,))
+    if _is_rgbd_quality(quality) and depth is None and cam_coords is None:
+        raise RuntimeError("quality=\"rgbd\" rates the RGB-D solver's pose: it needs depth or cam_coords")
+
+
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
                    quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0):
@@ -237,10 +249,14 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     consumes the network's own output tensor (the strided `pred[:, :3]` view) exactly as with trained weights.
     `depth` [B,Ho,Wo] or `cam_coords` [B,3,Ho,Wo] (at most one; off by default): the RGB-D solver
     (dsacstar.forward_rgbd_batch: Kabsch hypotheses from the cells' camera coordinates) runs in place of the RGB one, with
-    `rgbd_threshold` and `max_dist_error` in centimetres; `quality` still rates the pose by its reprojection residuals."""
+    `rgbd_threshold` and `max_dist_error` in centimetres; `quality=True` still rates the pose by its reprojection residuals.
+    `quality="rgbd"` (only with `depth` or `cam_coords`): the RGB-D pose-quality pass (dsacstar.pose_quality_rgbd_batch) runs
+    behind the RGB-D solver instead and rates the pose by its metric 3-D residuals; its rows [B,64] are the third value
+    (status and sigma_pos_m in the columns of the RGB row, so selective_accuracy takes either)."""
     import dsacstar
     if depth is not None and cam_coords is not None:
         raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
+    _check_quality_mode(quality, depth, cam_coords)
     with torch.no_grad():
         pred = network(images)
     nt = network.num_task_channel
@@ -258,6 +274,11 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
         dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
                                    inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
                                    image0=image0, image_stride=image_stride, focals=focals)
+    if _is_rgbd_quality(quality):
+        rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, inlier_alpha, max_dist_error,
+                                                depth=depth, focalLength=f0, ppointX=float(image_w / 2),
+                                                ppointY=float(image_h / 2), subSampling=network.OUTPUT_SUBSAMPLE, focals=focals)
+        return poses, pred, rows
     if quality:
         rows = dsacstar.pose_quality_batch(coords, poses, threshold, f0, float(image_w / 2), float(image_h / 2),
                                            inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE, focals=focals)
@@ -319,10 +340,12 @@ class PipelinedLocalizer:
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
         side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
-        RGB-D solver runs in place of the RGB one, as in localize_batch."""
+        RGB-D solver runs in place of the RGB one, as in localize_batch; `quality="rgbd"` (only with them): the RGB-D
+        pose-quality pass runs behind it instead of the reprojection pass."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
+        _check_quality_mode(quality, depth, cam_coords)
         pred, events = self.forward_cnn(images, plant)
         coords = pred[:, :self.net.num_task_channel] if scene_coords is None else scene_coords
         poses = torch.empty((coords.shape[0], 4, 4), dtype=torch.float32, device=coords.device)   # (the solver writes all 16)
@@ -341,7 +364,12 @@ class PipelinedLocalizer:
                 dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
                                            image0=image0, image_stride=image_stride)
-            if quality:
+            if _is_rgbd_quality(quality):
+                rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, self.alpha, max_dist_error,
+                                                        depth=depth, focalLength=f0, ppointX=float(self.w / 2),
+                                                        ppointY=float(self.h / 2), subSampling=self.net.OUTPUT_SUBSAMPLE,
+                                                        focals=focals)
+            elif quality:
                 rows = dsacstar.pose_quality_batch(coords, poses, self.thr, self.focal, float(self.w / 2), float(self.h / 2),
                                                    self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE)
         pred.record_stream(self.side)

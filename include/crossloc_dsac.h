@@ -264,6 +264,60 @@ int xl_dsac_backward_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc,
                                 uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
                                 void *stream, double *rec_dev);
 
+/*
+ * Per-frame pose quality of the RGB-D solver: how far ONE given pose per image can be trusted, rated by its metric 3-D
+ * residuals.  A stand-alone pass (one 256-thread workgroup per image, two walks over the cells, nothing staged in LDS: any grid
+ * size, XL_DSAC_RGBD_MAX_CELLS does not apply), the sibling of xl_dsac_pose_quality_batch; usually enqueued on the stream of
+ * xl_dsac_forward_rgbd_batch directly behind it, on the poses that call wrote.
+ *
+ *   coords / cam / depth with their strides, thr, alpha, max_dist (centimetres), focal, ppx, ppy, sub, focals_dev
+ *                  as in xl_dsac_forward_rgbd_batch: EXACTLY ONE of cam_dev and depth_dev is non-null, the depth form builds the
+ *                  camera coordinate with the same float formula and bits
+ *   poses_dev      [B,16] float32 cam->world 4x4, row-major; read as the world->camera pose {R, t} the backward passes derive
+ *   rows_dev       [B,XL_DSAC_QUALITY_DOUBLES] float64, one row per image, all 64 written
+ *
+ * Model.  m = R X + t is the predicted camera point of a cell (X its scene coordinate), r = p - m its residual in metres (p
+ * its camera coordinate).  A cell is valid iff its camera z != 0; a valid cell is an inlier iff
+ * e = min((float)(|r| * 100), max_dist) < thr, the float comparison of the solver's refinement.  The covariance is that of the
+ * unweighted rigid least-squares fit the refinement performs on the n inliers, with isotropic noise of sigma metres per axis:
+ * sigma^2 = SSE / (3 n - 6).  Everything is accumulated about the inlier centroid c of m in the camera frame (scene coordinates
+ * lie up to 1200 m from the world origin; the uncentred normal matrix has a condition number of 1e6 to 1e9): with u = m - c and
+ * C = sum u u^T the fit decouples into a rotation about c with information M = tr(C) I - C (3x3) and the centroid translation
+ * tau with information n I.  JtJ and Sigma are reported in the parameters of the RGB row, (wx, wy, wz, tx, ty, tz) with
+ * R' = Exp(w) R, t' = t + d, through d = tau - [t - c]x w:  G = [[I, 0], [-[t - c]x, I]],
+ * Sigma = G diag(sigma^2 M^-1, sigma^2 / n I) G^T,  JtJ = G^-T diag(M, n I) G^-1  (= sum J^T J, J = [[R X]x, -I]).
+ * Degenerate: inliers on one line or at one point leave M singular; M is factored by Cholesky and a pivot that is not above
+ * 1e-12 times its diagonal entry (or is not finite) is a breakdown (rounding leaves about 3e-16, three neighbouring cells of a
+ * grid row 3e-6 or more on the test scenes).
+ *
+ * Row of image b (doubles; the RGB row's positions wherever the meaning is the same):
+ *     [0]      n_cells = Ho * Wo
+ *     [1]      n_inliers
+ *     [2]      soft score of the pose over ALL cells, invalid ones at the error max_dist: the solver's score at this pose
+ *     [3]      sum of e over the inliers (centimetres)        [4]  sum of e^2 over the inliers
+ *     [5]      SSE = sum |r|^2 over the inliers, m^2
+ *     [6]      status: 0 ok; 1 fewer than 3 inliers (no valid cell included); 2 degenerate (see above); 3 a pose entry is not finite
+ *     [7]      sigma_m = sqrt(SSE / (3 n - 6)), metres per axis
+ *     [8]      sigma_pos_m = sqrt(trace Sigma_C)
+ *     [9]      sigma_rot_deg = sqrt(Sigma_00 + Sigma_11 + Sigma_22) * 180/pi
+ *     [10..30] JtJ over the inliers, upper triangle row-major
+ *     [31..51] Sigma, upper triangle row-major
+ *     [52..57] Sigma_C = A Sigma A^T, upper triangle: covariance of the camera centre, as in the RGB row
+ *     [58]     n_valid
+ *     [59..63] 0.0 (reserved)
+ *   With status 1 or 2, [7..9] and [31..57] are NaN and the rest is valid; with status 3 every field except [0] and [6] is NaN.
+ *
+ * XL_ERR_ARG (before any HIP call): a null coords / poses / rows pointer, neither or both of cam_dev and depth_dev, B, Ho, Wo or
+ * sub not positive.  XL_ERR_GRID: Ho * Wo does not fit the int cell index.
+ */
+int xl_dsac_pose_quality_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                    const float *cam_dev, int64_t mb, int64_t mc, int64_t my, int64_t mx,
+                                    const float *depth_dev, int64_t db, int64_t dy, int64_t dx,
+                                    int B, int Ho, int Wo, const float *poses_dev /* [B,16] cam->world */,
+                                    float thr, float alpha, float max_dist,
+                                    float focal, float ppx, float ppy, int sub, const float *focals_dev,
+                                    double *rows_dev /* [B,64] */, void *stream);
+
 /* The reference-shaped single-image RGB-D entries (dsacstar.cpp:889-891) are not wired to the solver above yet: they
  * return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);

@@ -14,6 +14,13 @@ form) beside dsacstar.backward_rgb_batch at 24 frames x 256 hypotheses on 60 x 9
 clamp 100, against the scenes' ground-truth poses.  Each call accumulates into its own gradient tensor.
 
     python tools/rgbd_timing.py --backward [--json out.json]
+
+With --quality the two pose-quality passes are timed behind their solvers, four sides alternately in the same way:
+forward_rgbd_batch (camera-tensor form) alone and with pose_quality_rgbd_batch enqueued behind it, forward_rgb_batch alone and
+with pose_quality_batch behind it, at 95 frames x 256 hypotheses on 60 x 90 and at 1 frame.  The cost of a pass is the
+difference of the pair.
+
+    python tools/rgbd_timing.py --quality [--json out.json]
 """
 import argparse
 import json
@@ -91,6 +98,52 @@ def backward_results(opt, dev):
     return results
 
 
+def quality_results(opt, dev):
+    """one dict per batch size: per-call milliseconds of each solver alone and with its pose-quality pass behind it, alternately"""
+    results = []
+    for B in (95, 1):
+        coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
+        rng = np.random.default_rng(7)
+        depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
+        co = torch.from_numpy(coords).to(dev)
+        cam = dsacstar.camera_coordinates(torch.from_numpy(depth_np).to(dev), synth.FOCAL, 480, 720, 8)
+        poses = [torch.zeros((B, 4, 4), dtype=torch.float32, device=dev) for _ in range(4)]
+        rows = {}
+
+        def rgbd():
+            dsacstar.forward_rgbd_batch(co, cam, poses[0], opt.hypotheses, *RGBD_ARGS)
+
+        def rgbd_quality():
+            dsacstar.forward_rgbd_batch(co, cam, poses[1], opt.hypotheses, *RGBD_ARGS)
+            rows["rgbd"] = dsacstar.pose_quality_rgbd_batch(co, cam, poses[1], *RGBD_ARGS)
+
+        def rgb():
+            dsacstar.forward_rgb_batch(co, poses[2], opt.hypotheses, *RGB_ARGS)
+
+        def rgb_quality():
+            dsacstar.forward_rgb_batch(co, poses[3], opt.hypotheses, *RGB_ARGS)
+            rows["rgb"] = dsacstar.pose_quality_batch(co, poses[3], *RGB_ARGS)
+
+        sides = (rgbd, rgbd_quality, rgb, rgb_quality)
+        for fn in sides:
+            fn()
+        torch.cuda.synchronize()
+        assert torch.equal(poses[0], poses[1]) and torch.equal(poses[2], poses[3])
+        first = {k: v.cpu().numpy() for k, v in rows.items()}
+        assert (first["rgbd"][:, 6] == 0).all() and (first["rgb"][:, 6] == 0).all()
+        t, sp = time_sides(sides, opt.warmup, opt.iters, opt.rounds)
+        results.append(dict(mode="quality", frames=B, hypotheses=opt.hypotheses, grid=[60, 90], rounds=opt.rounds, iters=opt.iters,
+                            rgbd_ms=t[0], rgbd_spread_ms=sp[0], rgbd_with_quality_ms=t[1], rgbd_with_quality_spread_ms=sp[1],
+                            rgbd_quality_cost_ms=t[1] - t[0],
+                            rgb_ms=t[2], rgb_spread_ms=sp[2], rgb_with_quality_ms=t[3], rgb_with_quality_spread_ms=sp[3],
+                            rgb_quality_cost_ms=t[3] - t[2],
+                            rgbd_median_inliers=float(np.median(first["rgbd"][:, 1])),
+                            rgbd_median_sigma_m=float(np.median(first["rgbd"][:, 7])),
+                            rgbd_median_sigma_pos_m=float(np.median(first["rgbd"][:, 8])),
+                            rgb_median_sigma_pos_m=float(np.median(first["rgb"][:, 8]))))
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -99,6 +152,7 @@ def main():
     ap.add_argument("--hypotheses", type=int, default=256)
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--backward", action="store_true", help="time backward_rgbd_batch beside backward_rgb_batch instead")
+    ap.add_argument("--quality", action="store_true", help="time each solver alone and with its pose-quality pass behind it instead")
     opt = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rgbd_timing needs the GPU: a timing taken elsewhere says nothing")
@@ -111,8 +165,8 @@ def main():
     torch.cuda.synchronize()
     del x
 
-    results = backward_results(opt, dev) if opt.backward else []
-    for B in (() if opt.backward else (95, 1)):
+    results = backward_results(opt, dev) if opt.backward else quality_results(opt, dev) if opt.quality else []
+    for B in (() if opt.backward or opt.quality else (95, 1)):
         coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
         rng = np.random.default_rng(7)
         depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
