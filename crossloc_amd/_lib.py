@@ -66,21 +66,19 @@ def lib():
         L.xl_dsac_pose_quality_batch.restype = c_i32
         L.xl_dsac_pose_quality_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
                                                  c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_vp]
+        # where an RGB-D image comes from (coords, camera tensor, depth with their strides; B, Ho, Wo) and the intrinsics tail
+        # (focal, ppx, ppy, sub, focals): the same in the three entry points
+        rgbd_in = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32]
+        intr = [c_f, c_f, c_f, c_i32, c_vp]
         L.xl_dsac_forward_rgbd_batch.restype = c_i32
-        L.xl_dsac_forward_rgbd_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64,
-                                                 c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
-                                                 c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp,
-                                                 c_u64, c_u64, c_u64, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.xl_dsac_forward_rgbd_batch.argtypes = rgbd_in + [c_vp, c_i32, c_f, c_f, c_f] + intr + [
+            c_u64, c_u64, c_u64, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.xl_dsac_backward_rgbd_batch.restype = c_i32
-        L.xl_dsac_backward_rgbd_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64,
-                                                  c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
-                                                  c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
-                                                  c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp,
-                                                  c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
+        L.xl_dsac_backward_rgbd_batch.argtypes = rgbd_in + [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp,
+                                                            c_i32, c_f, c_f, c_f, c_f, c_f, c_f] + intr + [
+            c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
         L.xl_dsac_pose_quality_rgbd_batch.restype = c_i32
-        L.xl_dsac_pose_quality_rgbd_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64,
-                                                      c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
-                                                      c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_vp]
+        L.xl_dsac_pose_quality_rgbd_batch.argtypes = rgbd_in + [c_vp, c_f, c_f, c_f] + intr + [c_vp, c_vp]
         # include/crossloc_metrics.h
         L.xl_metrics_workspace_bytes.restype = c_i64
         L.xl_metrics_workspace_bytes.argtypes = [c_i32, c_i32]

@@ -25,7 +25,8 @@
 // + - * / sqrt; reductions use a fixed order.  What one lane computes on its own (the polynomials, the RNG, projection,
 // quartic, P3P, the Cholesky step, the backward pass's derivatives) lives in xl_dsac_math.h, which the CPU oracle compiles
 // too; this file keeps what is parallel: LDS staging, ballots, wave and block reductions, the LM state machine, the
-// kernels and the host entry points.  tests/test_dsac_gpu.py checks sampled cells, tries, scores, winner and refined pose
+// kernels and the host entry points.  The order of a block sum is stated in xl_dsac_reduce.h (block_sum), the 12-double pose form
+// in xl_dsac_math.h (pose_load12 / pose_store12).  tests/test_dsac_gpu.py checks sampled cells, tries, scores, winner and refined pose
 // against oracle/dsac_oracle.c bit for bit - a check of that parallel part and of gcc == hipcc, not of the shared
 // formulas (those: tests/indep_dsac.py and tests/test_oracle_dsac_pin.py).  The oracle includes the header; nothing here
 // includes the oracle.
@@ -50,6 +51,7 @@ constexpr double kFltEps = 1.1920928955078125e-07;
 // Pose, Cam, V3 and every function one lane evaluates on its own (deterministic exp / sincos / atan2, RNG, projection,
 // quartic, P3P, Cholesky step, the backward pass's derivatives): shared with the CPU oracle, written once
 #include "xl_dsac_math.h"
+#include "xl_dsac_reduce.h"             // the canonical block sum (block_sum: the order is stated there) and wave_bcast_pose
 
 // scene coordinates of the image: SoA planes in LDS (cell i = y * Wo + x)
 struct Coords {
@@ -114,18 +116,6 @@ __device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, 
     return ok;
 }
 
-// ------------------------------------------------------------------------------ wave / block reductions
-
-__device__ __forceinline__ Pose wave_bcast_pose(const Pose &p, int src)
-{
-    Pose o;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o.R[i] = __shfl(p.R[i], src);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o.t[i] = __shfl(p.t[i], src);
-    return o;
-}
-
 // ------------------------------------------------------------------------------ LM pieces
 
 // per-thread accumulation of the normal equations over this thread's inlier cells
@@ -164,25 +154,6 @@ __device__ __forceinline__ void normal_eq_thread(const Coords &co, const Cam &ca
 #pragma unroll
         for (int r = 0; r < 6; ++r) a[21 + r] += Ju[r] * ru + Jv[r] * rv;
         a[27] += ru * ru + rv * rv;
-    }
-}
-
-// canonical block sum of the 28 per-thread values: butterfly per wave, waves added in order.
-// `red` points at a [kWaves][28] double LDS buffer; the caller alternates two buffers.
-__device__ __forceinline__ void block_reduce28(double (&a)[28], double *red, int wave, int lane)
-{
-#pragma unroll
-    for (int k = 0; k < 28; ++k) {
-        double v = wave_butterfly(a[k]);
-        if (lane == 0) red[wave * 28 + k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 28; ++k) {
-        double tot = red[k];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) tot = tot + red[w * 28 + k];
-        a[k] = tot;
     }
 }
 
@@ -252,7 +223,7 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
         int lg = -3, iters = 0;
         bool failed = false;
         normal_eq_thread(co, cam, cur, inl, tid, ne);
-        block_reduce28(ne, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
+        block_sum(ne, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
         for (;;) {
             double d[6];
             prev = cur;
@@ -260,13 +231,13 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
             apply_step(&prev, d, &cur);
             double prevErr = ne[27];
             normal_eq_thread(co, cam, cur, inl, tid, neNew);
-            block_reduce28(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
+            block_sum(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
             while (neNew[27] > prevErr) {
                 if (++lg <= 16) {
                     if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
                     apply_step(&prev, d, &cur);
                     normal_eq_thread(co, cam, cur, inl, tid, neNew);
-                    block_reduce28(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
+                    block_sum(neNew, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
                 } else break;
             }
             if (failed) break;
@@ -551,14 +522,6 @@ __device__ __forceinline__ void stage_coords(const BwdParams &P, int b, float *s
     }
 }
 
-__device__ __forceinline__ void load_pose(const double *src, Pose &p)
-{
-#pragma unroll
-    for (int i = 0; i < 9; ++i) p.R[i] = src[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p.t[i] = src[9 + i];
-}
-
 // K1 (grid nHyp x B): soft-max probability of the hypothesis, refinement if it matters, loss, path-I quantities
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_hyp_kernel(BwdParams P)
@@ -582,7 +545,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     const bool active = !(prob < XLM_PROB_THRESH);
 
     Pose init, pose;
-    load_pose(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, init);
+    pose_load12(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, &init);
     pose = init;
     RefineOut ro;
     ro.inlAcc = 0ull; ro.finalInl = 0; ro.rounds = 0; ro.evals = 0;
@@ -627,7 +590,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
 #pragma unroll
                     for (int c = r; c < 6; ++c) { a[k] += J6[r] * J6[c]; ++k; }
             }
-            block_reduce28(a, S.red[redSel], wave, lane); redSel ^= 1;
+            block_sum(a, S.red[redSel], wave, lane); redSel ^= 1;
             double A[36], Ainv[36];
             {
                 int k = 0;
@@ -719,7 +682,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
     __syncthreads();
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
     Pose init;
-    load_pose(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, init);
+    pose_load12(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, &init);
     double dRi[27];
     for (int i = 0; i < 27; ++i) dRi[i] = rec[kRecDRinit + i];
     const double sog = rec[5];
@@ -742,7 +705,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
 #pragma unroll
         for (int k = 0; k < 6; ++k) a[k] += dRep * J6[k];
     }
-    block_reduce28(a, S.red[0], wave, lane);
+    block_sum(a, S.red[0], wave, lane);
 
     // dPNP (dsacstar_derivative.h:131-190): lanes 0..17 each solve one perturbed P3P; the float += eps / -= 2 eps /
     // += eps sequence of the earlier columns is replayed so every solve sees the points the serial code would
@@ -831,8 +794,8 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
         const double prob = rec[0];
         if (prob < XLM_PROB_THRESH) continue;
         Pose init, ref;
-        load_pose(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, init);
-        load_pose(rec + 6, ref);
+        pose_load12(P.hypPoses + ((int64_t)b * P.nHyp + h) * 12, &init);
+        pose_load12(rec + 6, &ref);
         double gI[3] = { 0.0, 0.0, 0.0 };
         const unsigned long long m = P.masks[((int64_t)b * P.nHyp + h) * kThreads + mt];
         if (rec[3] >= 4.0 && rec[4] == 0.0 && ((m >> mj) & 1ull)) {

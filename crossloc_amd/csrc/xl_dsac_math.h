@@ -358,6 +358,23 @@ XL_MATH_FN void pose_identity(Pose *p)
     p->t[0] = 0.0; p->t[1] = 0.0; p->t[2] = 0.0;
 }
 
+/* a pose as 12 doubles: R row-major, then t */
+XL_MATH_FN void pose_load12(const double *src, Pose *p)
+{
+    XL_MATH_UNROLL
+    for (int i = 0; i < 9; ++i) p->R[i] = src[i];
+    XL_MATH_UNROLL
+    for (int i = 0; i < 3; ++i) p->t[i] = src[9 + i];
+}
+
+XL_MATH_FN void pose_store12(const Pose *p, double *dst)
+{
+    XL_MATH_UNROLL
+    for (int i = 0; i < 9; ++i) dst[i] = p->R[i];
+    XL_MATH_UNROLL
+    for (int i = 0; i < 3; ++i) dst[9 + i] = p->t[i];
+}
+
 /* cv::solvePnP(SOLVEPNP_P3P) call-site contract (dsacstar_util.h:185-193): object points P0..P2 and pixels uv[0..2]
  * solve (law-of-cosines quartic, Grunert form of the Gao et al. system), the candidate with the smallest error on the
  * 4th point wins.  Returns true and the world -> camera pose on success. */

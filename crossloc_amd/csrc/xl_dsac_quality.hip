@@ -9,7 +9,7 @@
 //              the pass has no cell limit of its own)
 //   cell       clamped reprojection error (cell_err), soft-inlier term over all cells; for inliers (e < thr, the float
 //              comparison the refinement makes) the 28 normal-equation sums, the count, sum e and sum e^2
-//   reduce     32 per-thread double partials in the solver's canonical order: xor butterfly per wave, waves added 0, 1, 2, 3
+//   reduce     32 per-thread double partials in the solver's canonical order (block_sum, xl_dsac_reduce.h)
 //   finish     thread 0: 6x6 Cholesky inverse, covariance of the pose and of the camera centre, the row
 //
 // Arithmetic contract as in xl_dsac.hip: -ffp-contract=off, fixed reduction order.  What one lane computes on its own is in
@@ -28,6 +28,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
 #include "xl_dsac_quality_math.h"
+#include "xl_dsac_reduce.h"
 
 static_assert(XLQ_ROW == XL_DSAC_QUALITY_DOUBLES, "row width of the shared arithmetic and of the C ABI");
 
@@ -77,24 +78,10 @@ void xl_dsac_quality_kernel(QualityParams P)
         }
     }
 
-    // canonical block sum: butterfly per wave, waves added in order (block_reduce28 of the solver, 32 values wide)
-#pragma unroll
-    for (int k = 0; k < XLQ_SUMS; ++k) {
-        double v = wave_butterfly(a[k]);
-        if (lane == 0) red[wave * XLQ_SUMS + k] = v;
-    }
-    __syncthreads();
+    block_sum(a, red, wave, lane);                              // the canonical order: xl_dsac_reduce.h
     if (tid != 0) return;
-    double s[XLQ_SUMS];
-#pragma unroll
-    for (int k = 0; k < XLQ_SUMS; ++k) {
-        double tot = red[k];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) tot = tot + red[w * XLQ_SUMS + k];
-        s[k] = tot;
-    }
     double row[XLQ_ROW];
-    quality_row(s, &pose, &cam, poseOk, row);
+    quality_row(a, &pose, &cam, poseOk, row);
     double *o = P.rows + (int64_t)b * XLQ_ROW;
     for (int i = 0; i < XLQ_ROW; ++i) o[i] = row[i];
 }

@@ -14,7 +14,7 @@
 //              the invalid cells all have the error maxDist and enter as one product (get3DDistErrs + getHypScores,
 //              dsacstar_util.h:457-507, 316-343); error maps never leave registers
 //   select     first maximum wins, across the 4 wavefronts through LDS
-//   refine     all 256 threads: inlier set, two block reductions (centroids, centred cross-covariance), Kabsch redundantly
+//   refine     all 256 threads: inlier set, two block sums (centroids, centred cross-covariance; order: xl_dsac_reduce.h), Kabsch redundantly
 //              in every thread so control flow stays uniform, while the inlier count grows (refineHypRGBD,
 //              dsacstar_util.h:611-677)
 //   write      inverse rigid transform as float 4x4 (pose2trans)
@@ -24,7 +24,7 @@
 // on its own is in xl_dsac_rgbd_math.h; tests/dsac_rgbd_ref.c compiles the same header with gcc and restates this file's
 // orchestration serially, and tests/test_dsac_rgbd_gpu.py compares every output bit for bit.  Staging, the sampling and scoring
 // of a hypothesis and the refinement loop are __device__ functions of xl_dsac_rgbd_dev.h, shared with the backward pass
-// (xl_dsac_rgbd_bwd.hip).
+// (xl_dsac_rgbd_bwd.hip); so are the input record (RgbdIn, rgbd_input), the LDS view (rgbd_lds_view) and the score constants.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>                    // memcpy in the host half of xl_dsac_math.h (bits_f64), as that header asks
@@ -49,9 +49,8 @@ __global__ __launch_bounds__(kThreads)
 void xl_dsac_rgbd_forward_kernel(RgbdParams P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    Smem &S = *reinterpret_cast<Smem *>(smem_raw);
-    float *sF = reinterpret_cast<float *>(smem_raw + kSmemBytes);
-    unsigned short *sCell = reinterpret_cast<unsigned short *>(sF + 6 * (size_t)P.Npad);
+    const Lds L = rgbd_lds_view(smem_raw, P.Npad);
+    Smem &S = L.S;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -60,15 +59,14 @@ void xl_dsac_rgbd_forward_kernel(RgbdParams P)
     int cntSel = 0;
 
     // ---- stage: valid list (x-major) and the valid cells' six floats
-    const int nValid = rgbd_stage(P, b, S, sF, sCell, cntSel, tid, lane, wave, nullptr);
-    const Cells ce{ sF, sF + P.Npad, sF + 2 * P.Npad, sF + 3 * P.Npad, sF + 4 * P.Npad, sF + 5 * P.Npad };
+    const int nValid = rgbd_stage(P, b, L.S, L.sF, L.sCell, cntSel, tid, lane, wave, nullptr);
+    const Cells ce{ L.sF, L.sF + P.Npad, L.sF + 2 * P.Npad, L.sF + 3 * P.Npad, L.sF + 4 * P.Npad, L.sF + 5 * P.Npad };
 
     const uint64_t imageIdx = P.image0 + (uint64_t)b * P.imageStride;
     const uint64_t imageKey = image_key(P.seed, imageIdx);
     const float thr = P.thr, maxDist = P.maxDist;
-    const float beta = 5.0f / thr;
-    const float fac = P.alpha / (float)P.Wo / (float)P.Ho;
-    const double invalidTerm = rgbd_soft_term(maxDist, beta, thr);
+    const ScoreConst sc(thr, P.alpha, P.Ho, P.Wo);
+    const double invalidTerm = sc.invalid_term(maxDist, thr);
 
     // ---- sample + score: this wave's hypotheses
     double bestScore = 0.0;
@@ -78,33 +76,23 @@ void xl_dsac_rgbd_forward_kernel(RgbdParams P)
         Pose pose;
         int k3[3];
         const int triesUsed = rgbd_sample_hyp(ce, nValid, thr, imageKey, h, P.maxTries, lane, pose, k3);
-        const double score = rgbd_score_hyp(ce, nValid, N, pose, maxDist, beta, thr, invalidTerm, fac, lane);
+        const double score = rgbd_score_hyp(ce, nValid, N, pose, maxDist, thr, sc, invalidTerm, lane);
 
         if (lane == 0) {
             if (P.cells) {
                 int32_t *o = P.cells + ((int64_t)b * P.nHyp + h) * 3;
 #pragma unroll
-                for (int j = 0; j < 3; ++j) o[j] = (k3[j] >= 0) ? (int32_t)sCell[k3[j]] : -1;
+                for (int j = 0; j < 3; ++j) o[j] = (k3[j] >= 0) ? (int32_t)L.sCell[k3[j]] : -1;
             }
             if (P.tries) P.tries[(int64_t)b * P.nHyp + h] = triesUsed;
             if (P.scores) P.scores[(int64_t)b * P.nHyp + h] = score;
         }
         if (score != score) anyNan = 1;
         const bool better = (bestIdx < 0) || (score > bestScore);
-        if (h == 0 && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) S.pose0[i] = pose.R[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) S.pose0[9 + i] = pose.t[i];
-        }
+        if (h == 0 && lane == 0) pose_store12(&pose, S.pose0);
         if (better) {
             bestScore = score; bestIdx = h;
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < 9; ++i) S.bestPose[wave][i] = pose.R[i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) S.bestPose[wave][9 + i] = pose.t[i];
-            }
+            if (lane == 0) pose_store12(&pose, S.bestPose[wave]);
         }
     }
     if (lane == 0) { S.bestScore[wave] = bestScore; S.bestIdx[wave] = bestIdx; S.anyNan[wave] = anyNan; }
@@ -124,13 +112,7 @@ void xl_dsac_rgbd_forward_kernel(RgbdParams P)
         if (nanAny) win = 0;
     }
     Pose pose;
-    {
-        const double *src = nanAny ? S.pose0 : S.bestPose[winWave];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pose.R[i] = src[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pose.t[i] = src[9 + i];
-    }
+    pose_load12(nanAny ? S.pose0 : S.bestPose[winWave], &pose);
 
     // ---- refine
     RefineOut ro;
@@ -152,8 +134,7 @@ void xl_dsac_rgbd_forward_kernel(RgbdParams P)
         if (P.dbg) {
             double *q = P.dbg + (int64_t)b * XL_DSAC_RGBD_DBG_DOUBLES;
             q[0] = (double)win; q[1] = (double)nValid; q[2] = (double)rounds; q[3] = (double)finalInl;
-            for (int i = 0; i < 9; ++i) q[4 + i] = pose.R[i];
-            for (int i = 0; i < 3; ++i) q[13 + i] = pose.t[i];
+            pose_store12(&pose, q + 4);
         }
     }
 }
@@ -170,32 +151,22 @@ extern "C" int xl_dsac_forward_rgbd_batch(const float *coords_dev, int64_t sb, i
                                           void *stream,
                                           int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
 {
-    if (!coords_dev || !out_poses_dev || (cam_dev == nullptr) == (depth_dev == nullptr) || B <= 0 || Ho <= 0 || Wo <= 0 ||
-        n_hyp <= 0 || max_tries == 0 || max_tries > XL_DSAC_RGBD_MAX_TRIES)
-        return XL_ERR_ARG;
-    if (depth_dev && sub <= 0) return XL_ERR_ARG;
-    if ((int64_t)Ho * (int64_t)Wo > (int64_t)kMaxCells) return XL_ERR_GRID;
-    const int N = Ho * Wo;
     RgbdParams P;
-    P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
-    P.cam = cam_dev; P.mb = mb; P.mc = mc; P.my = my; P.mx = mx;
-    P.depth = depth_dev; P.db = db; P.dy = dy; P.dx = dx;
-    P.outPoses = out_poses_dev; P.focals = focals_dev;
+    if (rgbd_input(P, coords_dev, sb, sc, sy, sx, cam_dev, mb, mc, my, mx, depth_dev, db, dy, dx, B, Ho, Wo, focal, ppx, ppy, sub,
+                   focals_dev) != XL_OK || !out_poses_dev || n_hyp <= 0 || max_tries == 0 || max_tries > XL_DSAC_RGBD_MAX_TRIES)
+        return XL_ERR_ARG;
+    if ((int64_t)Ho * (int64_t)Wo > (int64_t)kMaxCells) return XL_ERR_GRID;
+    P.Npad = (Ho * Wo + 3) & ~3;
+    P.outPoses = out_poses_dev;
     P.cells = cells_dev; P.tries = tries_dev; P.scores = scores_dev; P.dbg = dbg_dev;
     P.seed = seed; P.image0 = image0; P.imageStride = image_stride; P.maxTries = max_tries;
-    P.nHyp = n_hyp; P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = (N + 3) & ~3;
-    P.thr = thr; P.alpha = alpha; P.maxDist = max_dist; P.focal = focal; P.ppx = ppx; P.ppy = ppy;
+    P.nHyp = n_hyp; P.thr = thr; P.alpha = alpha; P.maxDist = max_dist;
 
     const size_t lds = rgbd_lds_bytes(P.Npad);
     if (lds > kMaxLds) return XL_ERR_GRID;
     static XlLdsLimit configured;
-    int cfgDev;
-    if (configured.needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_rgbd_forward_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return XL_ERR_HIP;
-        configured.done(lds, cfgDev);
-    }
+    const void *const kernels[] = { reinterpret_cast<const void *>(xl_dsac_rgbd_forward_kernel) };
+    if (!rgbd_raise_lds_limit(configured, kernels, lds)) return XL_ERR_HIP;
     hipLaunchKernelGGL(xl_dsac_rgbd_forward_kernel, dim3(B), dim3(kThreads), lds, (hipStream_t)stream, P);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }

@@ -16,7 +16,8 @@
 //                     of the support points (path-II guard) and the 3 x 3 support-point gradients
 //   K4 (N/256 x B)    per cell, hypotheses in ascending order, float accumulation: prob * path I + path II
 //
-// LDS of K0, K1, K3: the forward kernel's layout (26 bytes per cell behind Smem), 138 KiB at 60 x 90, one workgroup per CU.
+// LDS of K0, K1, K3: the forward kernel's layout (26 bytes per cell behind Smem; rgbd_lds_view), 138 KiB at 60 x 90, one workgroup
+// per CU.  The input record (RgbdIn, rgbd_input) is in xl_dsac_rgbd_dev.h, the order of the block sums in xl_dsac_reduce.h.
 // What one lane computes on its own is in xl_dsac_rgbd_bwd_math.h; tests/dsac_rgbd_bwd_ref.c compiles the same header with gcc
 // and restates this file's orchestration serially, and tests/test_dsac_rgbd_bwd_gpu.py compares every output bit for bit.
 #include <hip/hip_runtime.h>
@@ -45,48 +46,31 @@ struct RgbdBwdParams : RgbdIn {
     float thr, alpha, maxDist, wRot, wTrans, softClamp;
 };
 
-__device__ __forceinline__ void load_pose(const double *src, Pose &p)
-{
-#pragma unroll
-    for (int i = 0; i < 9; ++i) p.R[i] = src[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p.t[i] = src[9 + i];
-}
-
-#define XLB_LDS_VIEW()                                                                              \
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];                        \
-    Smem &S = *reinterpret_cast<Smem *>(smem_raw);                                                  \
-    float *sF = reinterpret_cast<float *>(smem_raw + kSmemBytes);                                   \
-    unsigned short *sCell = reinterpret_cast<unsigned short *>(sF + 6 * (size_t)P.Npad);            \
-    const int tid = threadIdx.x, lane = tid & 63;                                                   \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6)
-
 // K0 (grid S x B): sample and score
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_rgbd_bwd_sample_kernel(RgbdBwdParams P)
 {
-    XLB_LDS_VIEW();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const Lds L = rgbd_lds_view(smem_raw, P.Npad);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int split = blockIdx.x, b = blockIdx.y;
     const int N = P.Ho * P.Wo;
     int cntSel = 0;
-    const int nValid = rgbd_stage(P, b, S, sF, sCell, cntSel, tid, lane, wave, split == 0 ? P.placeOf + (int64_t)b * N : nullptr);
-    const Cells ce{ sF, sF + P.Npad, sF + 2 * P.Npad, sF + 3 * P.Npad, sF + 4 * P.Npad, sF + 5 * P.Npad };
+    const int nValid = rgbd_stage(P, b, L.S, L.sF, L.sCell, cntSel, tid, lane, wave, split == 0 ? P.placeOf + (int64_t)b * N : nullptr);
+    const Cells ce{ L.sF, L.sF + P.Npad, L.sF + 2 * P.Npad, L.sF + 3 * P.Npad, L.sF + 4 * P.Npad, L.sF + 5 * P.Npad };
     const uint64_t imageKey = image_key(P.seed, P.image0 + (uint64_t)b * P.imageStride);
     const float thr = P.thr, maxDist = P.maxDist;
-    const float beta = 5.0f / thr;
-    const float fac = P.alpha / (float)P.Wo / (float)P.Ho;
-    const double invalidTerm = rgbd_soft_term(maxDist, beta, thr);
+    const ScoreConst sc(thr, P.alpha, P.Ho, P.Wo);
+    const double invalidTerm = sc.invalid_term(maxDist, thr);
     for (int h = split * kWaves + wave; h < P.nHyp; h += P.S * kWaves) {
         Pose pose;
         int k3[3];
         (void)rgbd_sample_hyp(ce, nValid, thr, imageKey, h, P.maxTries, lane, pose, k3);
-        const double score = rgbd_score_hyp(ce, nValid, N, pose, maxDist, beta, thr, invalidTerm, fac, lane);
+        const double score = rgbd_score_hyp(ce, nValid, N, pose, maxDist, thr, sc, invalidTerm, lane);
         if (lane == 0) {
             const int64_t o = (int64_t)b * P.nHyp + h;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) P.hypPoses[o * 12 + i] = pose.R[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) P.hypPoses[o * 12 + 9 + i] = pose.t[i];
+            pose_store12(&pose, P.hypPoses + o * 12);
             P.scores[o] = score;
 #pragma unroll
             for (int j = 0; j < 3; ++j) P.places[o * 3 + j] = k3[j];
@@ -98,14 +82,17 @@ void xl_dsac_rgbd_bwd_sample_kernel(RgbdBwdParams P)
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_rgbd_bwd_hyp_kernel(RgbdBwdParams P)
 {
-    XLB_LDS_VIEW();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const Lds L = rgbd_lds_view(smem_raw, P.Npad);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
     const int64_t o = (int64_t)b * P.nHyp + h;
     const double prob = rgbd_softmax_prob(P.scores + (int64_t)b * P.nHyp, P.nHyp, h);
     const bool active = !(prob < XLM_PROB_THRESH);
     double *rec = P.rec + o * kRec;
     Pose pose;
-    load_pose(P.hypPoses + o * 12, pose);
+    pose_load12(P.hypPoses + o * 12, &pose);
     Gt gt;
     gt_from_pose16(P.gt + (int64_t)b * 16, &gt);
     if (!active) {                                           // (uniform over the workgroup: prob is computed alike by every thread)
@@ -114,10 +101,10 @@ void xl_dsac_rgbd_bwd_hyp_kernel(RgbdBwdParams P)
         return;
     }
     int cntSel = 0, redSel = 0;
-    const int nValid = rgbd_stage(P, b, S, sF, sCell, cntSel, tid, lane, wave, nullptr);
-    const Cells ce{ sF, sF + P.Npad, sF + 2 * P.Npad, sF + 3 * P.Npad, sF + 4 * P.Npad, sF + 5 * P.Npad };
+    const int nValid = rgbd_stage(P, b, L.S, L.sF, L.sCell, cntSel, tid, lane, wave, nullptr);
+    const Cells ce{ L.sF, L.sF + P.Npad, L.sF + 2 * P.Npad, L.sF + 3 * P.Npad, L.sF + 4 * P.Npad, L.sF + 5 * P.Npad };
     RefineOut ro;
-    rgbd_refine(ce, nValid, P.thr, P.maxDist, S, cntSel, redSel, tid, wave, lane, pose, ro);
+    rgbd_refine(ce, nValid, P.thr, P.maxDist, L.S, cntSel, redSel, tid, wave, lane, pose, ro);
     const double loss = pose_loss(&pose, &gt, (double)P.wRot, (double)P.wTrans, (double)P.softClamp);
     P.masks[o * kThreads + tid] = ro.inl;
 
@@ -140,8 +127,7 @@ void xl_dsac_rgbd_bwd_hyp_kernel(RgbdBwdParams P)
     }
     if (tid == 0) {
         rec[0] = prob; rec[1] = loss; rec[2] = 1.0; rec[3] = (double)ro.finalInl; rec[4] = (double)guardI; rec[5] = 0.0;
-        for (int i = 0; i < 9; ++i) rec[6 + i] = pose.R[i];
-        for (int i = 0; i < 3; ++i) rec[15 + i] = pose.t[i];
+        pose_store12(&pose, rec + 6);
         for (int i = 0; i < 9; ++i) rec[18 + i] = H[i];
         for (int i = 0; i < 3; ++i) { rec[27 + i] = v[i]; rec[30 + i] = ro.cp[i]; }
         for (int i = 33; i < kRec; ++i) rec[i] = 0.0;
@@ -173,19 +159,21 @@ void xl_dsac_rgbd_bwd_expect_kernel(RgbdBwdParams P)
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_rgbd_bwd_score_kernel(RgbdBwdParams P)
 {
-    XLB_LDS_VIEW();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const Lds L = rgbd_lds_view(smem_raw, P.Npad);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
     const int64_t o = (int64_t)b * P.nHyp + h;
     double *rec = P.rec + o * kRec;
     if (rec[0] < XLM_PROB_THRESH) return;                     // inactive: before staging, the whole workgroup alike
     int cntSel = 0;
-    const int nValid = rgbd_stage(P, b, S, sF, sCell, cntSel, tid, lane, wave, nullptr);
-    const Cells ce{ sF, sF + P.Npad, sF + 2 * P.Npad, sF + 3 * P.Npad, sF + 4 * P.Npad, sF + 5 * P.Npad };
+    const int nValid = rgbd_stage(P, b, L.S, L.sF, L.sCell, cntSel, tid, lane, wave, nullptr);
+    const Cells ce{ L.sF, L.sF + P.Npad, L.sF + 2 * P.Npad, L.sF + 3 * P.Npad, L.sF + 4 * P.Npad, L.sF + 5 * P.Npad };
     Pose init;
-    load_pose(P.hypPoses + o * 12, init);
+    pose_load12(P.hypPoses + o * 12, &init);
     const double sog = rec[5];
-    const float beta = 5.0f / P.thr;
-    const float facf = P.alpha / (float)P.Wo / (float)P.Ho;
+    const ScoreConst sc(P.thr, P.alpha, P.Ho, P.Wo);
 
     double sR[9], sT[3];
     {
@@ -195,8 +183,8 @@ void xl_dsac_rgbd_bwd_score_kernel(RgbdBwdParams P)
         for (int k = tid; k < nValid; k += kThreads) {
             double w, dhat[3];
             const double X = (double)ce.X[k], Y = (double)ce.Y[k], Z = (double)ce.Z[k];
-            if (rgbd_cell_weight(&init, X, Y, Z, (double)ce.px[k], (double)ce.py[k], (double)ce.pz[k], P.maxDist, beta, P.thr, sog,
-                                 facf, &w, dhat))
+            if (rgbd_cell_weight(&init, X, Y, Z, (double)ce.px[k], (double)ce.py[k], (double)ce.pz[k], P.maxDist, sc.beta, P.thr, sog,
+                                 sc.fac, &w, dhat))
                 rgbd_acc_score_sums(s, w, dhat, X, Y, Z);
         }
 #pragma unroll
@@ -204,8 +192,8 @@ void xl_dsac_rgbd_bwd_score_kernel(RgbdBwdParams P)
 #pragma unroll
         for (int i = 0; i < 3; ++i) sT[i] = s[9 + i];
     }
-    block_reduce<9>(sR, S.red[0], wave, lane);
-    block_reduce<3>(sT, S.red[1], wave, lane);
+    block_sum(sR, L.S.red[0], wave, lane);
+    block_sum(sT, L.S.red[1], wave, lane);
 
     // the minimal fit once more (the bits of K0's fit), with its eigen-decomposition
     const int32_t *pl = P.places + o * 3;
@@ -271,8 +259,7 @@ void xl_dsac_rgbd_bwd_assemble_kernel(RgbdBwdParams P)
     float *g = P.grad + (int64_t)b * P.gsb + (int64_t)y * P.gsy + (int64_t)x * P.gsx;
     if (place < 0) return;                                    // an invalid cell gets nothing
     float acc[3] = { g[0], g[P.gsc], g[2 * P.gsc] };
-    const float beta = 5.0f / P.thr;
-    const float facf = P.alpha / (float)P.Wo / (float)P.Ho;
+    const ScoreConst sc(P.thr, P.alpha, P.Ho, P.Wo);
     const int mt = place % kThreads, mj = place / kThreads;
     for (int h = 0; h < P.nHyp; ++h) {
         const int64_t o = (int64_t)b * P.nHyp + h;
@@ -285,9 +272,9 @@ void xl_dsac_rgbd_bwd_assemble_kernel(RgbdBwdParams P)
             gI[0] = gI[0] - rec[27]; gI[1] = gI[1] - rec[28]; gI[2] = gI[2] - rec[29];
         }
         Pose init;
-        load_pose(P.hypPoses + o * 12, init);
+        pose_load12(P.hypPoses + o * 12, &init);
         double jac[3] = { 0.0, 0.0, 0.0 }, w, dhat[3];
-        if (rgbd_cell_weight(&init, X, Y, Z, px, py, pz, P.maxDist, beta, P.thr, rec[5], facf, &w, dhat))
+        if (rgbd_cell_weight(&init, X, Y, Z, px, py, pz, P.maxDist, sc.beta, P.thr, rec[5], sc.fac, &w, dhat))
             rgbd_cell_direct(&init, w, dhat, jac);
         const int32_t *pl = P.places + o * 3;
         for (int j = 0; j < 3; ++j)
@@ -312,15 +299,16 @@ extern "C" int xl_dsac_backward_rgbd_batch(const float *coords_dev, int64_t sb, 
                                            uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
                                            void *stream, double *rec_dev)
 {
-    if (!coords_dev || !grad_dev || !gt_poses_dev || !out_loss_dev || (cam_dev == nullptr) == (depth_dev == nullptr) || B <= 0 ||
-        Ho <= 0 || Wo <= 0 || n_hyp <= 0 || max_tries == 0 || max_tries > XL_DSAC_RGBD_MAX_TRIES)
+    RgbdBwdParams P;
+    if (rgbd_input(P, coords_dev, sb, sc, sy, sx, cam_dev, mb, mc, my, mx, depth_dev, db, dy, dx, B, Ho, Wo, focal, ppx, ppy, sub,
+                   focals_dev) != XL_OK || !grad_dev || !gt_poses_dev || !out_loss_dev || n_hyp <= 0 || max_tries == 0 ||
+        max_tries > XL_DSAC_RGBD_MAX_TRIES)
         return XL_ERR_ARG;
-    if (depth_dev && sub <= 0) return XL_ERR_ARG;
     if ((int64_t)Ho * (int64_t)Wo > (int64_t)kMaxCells) return XL_ERR_GRID;
     if (B > 65535) return XL_ERR_GRID;                        // images ride on blockIdx.y
     const int N = Ho * Wo;
-    const int Npad = (N + 3) & ~3;
-    const size_t lds = rgbd_lds_bytes(Npad);
+    P.Npad = (N + 3) & ~3;
+    const size_t lds = rgbd_lds_bytes(P.Npad);
     if (lds > kMaxLds) return XL_ERR_GRID;
     hipStream_t st = (hipStream_t)stream;
     const size_t nh = (size_t)B * n_hyp;
@@ -337,18 +325,12 @@ extern "C" int xl_dsac_backward_rgbd_batch(const float *coords_dev, int64_t sb, 
     if (hipMallocAsync((void **)&ws, up(bPoses) + up(bScores) + up(bPlaces) + up(bPlaceOf) + up(bRec) + up(bMasks), st) != hipSuccess)
         return XL_ERR_HIP;
     unsigned char *cur = ws;
-    RgbdBwdParams P;
     P.hypPoses = (double *)cur; cur += up(bPoses);
     P.scores = (double *)cur; cur += up(bScores);
     P.places = (int32_t *)cur; cur += up(bPlaces);
     P.placeOf = (int32_t *)cur; cur += up(bPlaceOf);
     P.rec = rec_dev ? rec_dev : (double *)cur; cur += up(bRec);
     P.masks = (unsigned long long *)cur;
-    P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
-    P.cam = cam_dev; P.mb = mb; P.mc = mc; P.my = my; P.mx = mx;
-    P.depth = depth_dev; P.db = db; P.dy = dy; P.dx = dx;
-    P.focals = focals_dev; P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = Npad;
-    P.focal = focal; P.ppx = ppx; P.ppy = ppy;
     P.grad = grad_dev; P.gsb = gsb; P.gsc = gsc; P.gsy = gsy; P.gsx = gsx;
     P.gt = gt_poses_dev; P.outLoss = out_loss_dev;
     P.seed = seed; P.image0 = image0; P.imageStride = image_stride; P.maxTries = max_tries;
@@ -356,17 +338,12 @@ extern "C" int xl_dsac_backward_rgbd_batch(const float *coords_dev, int64_t sb, 
     P.thr = thr; P.alpha = alpha; P.maxDist = max_dist; P.wRot = w_rot; P.wTrans = w_trans; P.softClamp = soft_clamp;
 
     static XlLdsLimit configured;
-    int cfgDev;
-    if (configured.needs(lds, &cfgDev)) {
-        const void *ks[3] = { reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_sample_kernel),
-                              reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_hyp_kernel),
-                              reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_score_kernel) };
-        for (const void *k : ks)
-            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipFreeAsync(ws, st);
-                return XL_ERR_HIP;
-            }
-        configured.done(lds, cfgDev);
+    const void *const kernels[] = { reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_sample_kernel),
+                                    reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_hyp_kernel),
+                                    reinterpret_cast<const void *>(xl_dsac_rgbd_bwd_score_kernel) };
+    if (!rgbd_raise_lds_limit(configured, kernels, lds)) {
+        (void)hipFreeAsync(ws, st);
+        return XL_ERR_HIP;
     }
     hipLaunchKernelGGL(xl_dsac_rgbd_bwd_sample_kernel, dim3(S, B), dim3(kThreads), lds, st, P);
     hipLaunchKernelGGL(xl_dsac_rgbd_bwd_hyp_kernel, dim3(n_hyp, B), dim3(kThreads), lds, st, P);

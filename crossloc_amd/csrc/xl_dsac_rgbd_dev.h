@@ -1,6 +1,7 @@
-// xl_dsac_rgbd_dev.h — the workgroup-level pieces of the RGB-D DSAC* solver that the forward kernel (xl_dsac_rgbd.hip) and the
-// backward kernels (xl_dsac_rgbd_bwd.hip) share: staging of an image into LDS, the sampling of one hypothesis by a wave,
-// its scoring walk, and the refinement loop of the workgroup.  Written once; included inside the consumer's anonymous
+// xl_dsac_rgbd_dev.h — the pieces of the RGB-D DSAC* solver that the forward kernel (xl_dsac_rgbd.hip), the backward kernels
+// (xl_dsac_rgbd_bwd.hip) and the quality pass (xl_dsac_rgbd_quality.hip) share: the input record and its checks (RgbdIn, rgbd_input),
+// the LDS view, staging of an image into LDS, the sampling of one hypothesis by a wave, its scoring walk and score constants, and
+// the refinement loop of the workgroup.  The order of a block sum is stated in xl_dsac_reduce.h.  Written once; included inside the consumer's anonymous
 // namespace after <hip/hip_runtime.h>, crossloc_dsac.h and xl_common.h.  One 256-thread workgroup (4 wavefronts); arithmetic
 // contract as in xl_dsac_rgbd_math.h (-ffp-contract=off, fixed reduction order).
 #pragma once
@@ -11,6 +12,7 @@ constexpr int kMaxCells = XL_DSAC_RGBD_MAX_CELLS;
 constexpr size_t kMaxLds = 160 * 1024;
 
 #include "xl_dsac_rgbd_bwd_math.h"
+#include "xl_dsac_reduce.h"             // block_sum (the canonical order is stated there), wave_bcast_pose
 
 // where an image comes from: scene coordinates, and camera coordinates or depth
 struct RgbdIn {
@@ -21,6 +23,18 @@ struct RgbdIn {
     int Ho, Wo, sub, Npad;
     float focal, ppx, ppy;
 };
+
+// RgbdIn from the flat arguments of the C ABI, with the checks every entry point shares.  Npad stays 0: a pass that stages
+// sets it once its own grid check has passed.
+inline int rgbd_input(RgbdIn &in, const float *coords, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                      const float *cam, int64_t mb, int64_t mc, int64_t my, int64_t mx,
+                      const float *depth, int64_t db, int64_t dy, int64_t dx, int B, int Ho, int Wo,
+                      float focal, float ppx, float ppy, int sub, const float *focals)
+{
+    if (!coords || (cam == nullptr) == (depth == nullptr) || B <= 0 || Ho <= 0 || Wo <= 0 || (depth && sub <= 0)) return XL_ERR_ARG;
+    in = RgbdIn{ coords, sb, sc, sy, sx, cam, mb, mc, my, mx, depth, db, dy, dx, focals, Ho, Wo, sub, 0, focal, ppx, ppy };
+    return XL_OK;
+}
 
 struct Smem {
     double red[2][kWaves * XLR_SUMS_COV];
@@ -38,6 +52,18 @@ static_assert(kMaxCells <= 65536 && kMaxCells <= 64 * kThreads, "16-bit cell ind
 
 __host__ __device__ inline size_t rgbd_lds_bytes(int Npad) { return kSmemBytes + (size_t)26 * Npad; }
 
+// raises the dynamic LDS limit of `kernels` to `lds` bytes, once per device (`configured`: a static of the entry point)
+template <size_t NK>
+inline bool rgbd_raise_lds_limit(XlLdsLimit &configured, const void *const (&kernels)[NK], size_t lds)
+{
+    int dev;
+    if (!configured.needs(lds, &dev)) return true;
+    for (const void *k : kernels)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
+    configured.done(lds, dev);
+    return true;
+}
+
 // the staged image: planes in valid-list order
 struct Cells {
     const float *px, *py, *pz, *X, *Y, *Z;
@@ -45,6 +71,25 @@ struct Cells {
     {
         return rgbd_cell_err(&p, (double)X[k], (double)Y[k], (double)Z[k], (double)px[k], (double)py[k], (double)pz[k], maxDist);
     }
+};
+
+// the dynamic LDS of a staging kernel: Smem, then the six planes of Npad floats, then the 16-bit cell indices.  A kernel forms
+// its Cells from sF itself, after rgbd_stage, and hands rgbd_stage the three pieces: with a helper for the Cells (member,
+// constructor, free function) or the view passed whole, hipcc allocated the scalar registers of K0, K1, K3 and of the forward
+// kernel differently, and K1 ran 5 % slower
+struct Lds { Smem &S; float *sF; unsigned short *sCell; };
+
+__device__ __forceinline__ Lds rgbd_lds_view(unsigned char *smem_raw, int Npad)
+{
+    float *sF = reinterpret_cast<float *>(smem_raw + kSmemBytes);
+    return Lds{ *reinterpret_cast<Smem *>(smem_raw), sF, reinterpret_cast<unsigned short *>(sF + 6 * (size_t)Npad) };
+}
+
+// the constants of the soft-inlier score; the term of an invalid cell (error maxDist) is formed by the two kernels that score
+struct ScoreConst {
+    float beta, fac;
+    __device__ __forceinline__ ScoreConst(float thr, float alpha, int Ho, int Wo) : beta(5.0f / thr), fac(alpha / (float)Wo / (float)Ho) {}
+    __device__ __forceinline__ double invalid_term(float maxDist, float thr) const { return rgbd_soft_term(maxDist, beta, thr); }
 };
 
 // camera coordinate of cell (y, x) of image b, from the camera tensor or from depth
@@ -122,16 +167,6 @@ __device__ bool rgbd_sample_try(const Cells &ce, int nValid, float thr, uint64_t
     return rgbd_try_fit(pc, Xw, thr, &pose);
 }
 
-__device__ __forceinline__ Pose wave_bcast_pose(const Pose &p, int src)
-{
-    Pose o;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o.R[i] = __shfl(p.R[i], src);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o.t[i] = __shfl(p.t[i], src);
-    return o;
-}
-
 // sampling of hypothesis h by one wave: the 64 lanes evaluate 64 consecutive tries, __ballot picks the lowest accepted one.
 // Returns the tries used (negative: budget exhausted, the last try's fit is kept; 0: nothing sampled, identity pose, k3 = -1).
 __device__ __forceinline__ int rgbd_sample_hyp(const Cells &ce, int nValid, float thr, uint64_t imageKey, int h, uint32_t maxTries,
@@ -162,9 +197,10 @@ __device__ __forceinline__ int rgbd_sample_hyp(const Cells &ce, int nValid, floa
 }
 
 // soft-inlier score of a pose by one wave (lanes stride the valid list, xor butterfly; the invalid cells enter as one product)
-__device__ __forceinline__ double rgbd_score_hyp(const Cells &ce, int nValid, int N, const Pose &pose, float maxDist, float beta,
-                                                 float thr, double invalidTerm, float fac, int lane)
+__device__ __forceinline__ double rgbd_score_hyp(const Cells &ce, int nValid, int N, const Pose &pose, float maxDist, float thr,
+                                                 const ScoreConst &sc, double invalidTerm, int lane)
 {
+    const float beta = sc.beta;
     // four cells per lane and trip, added in the order of the one-cell loop: the same bits, four dependent chains (distance,
     // sqrt, exp, divide) in flight - the kernel runs at one wave per SIMD and is bound by their latency
     double acc = 0.0;
@@ -182,28 +218,7 @@ __device__ __forceinline__ double rgbd_score_hyp(const Cells &ce, int nValid, in
     for (; k < nValid; k += 64) acc += rgbd_soft_term(ce.err(pose, k, maxDist), beta, thr);
     double total = wave_butterfly(acc);
     total = total + (double)(N - nValid) * invalidTerm;
-    return total * (double)fac;
-}
-
-// canonical block sum of K per-thread values: butterfly per wave, waves added in order.  `red` is one of the two LDS buffers
-// the caller alternates; one barrier per call.
-template <int K>
-__device__ __forceinline__ void block_reduce(double (&a)[K], double *red, int wave, int lane)
-{
-    static_assert(K <= XLR_SUMS_COV, "Smem::red holds kWaves * XLR_SUMS_COV doubles per buffer");
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = wave_butterfly(a[k]);
-        if (lane == 0) red[wave * K + k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double tot = red[k];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) tot = tot + red[w * K + k];
-        a[k] = tot;
-    }
+    return total * (double)sc.fac;
 }
 
 // what the refinement leaves behind besides the pose.  inl, cp, cX, a: the inlier set of the last FITTED round (bit j of `inl`
@@ -253,7 +268,7 @@ __device__ __forceinline__ void rgbd_refine(const Cells &ce, int nValid, float t
                     rgbd_acc_centroid(s, (double)ce.px[k], (double)ce.py[k], (double)ce.pz[k],
                                       (double)ce.X[k], (double)ce.Y[k], (double)ce.Z[k]);
         }
-        block_reduce<XLR_SUMS_CENTROID>(s, S.red[redSel], wave, lane); redSel ^= 1;
+        block_sum(s, S.red[redSel], wave, lane); redSel ^= 1;
         rgbd_centroids(s, cp, cX);
 #pragma unroll
         for (int i = 0; i < XLR_SUMS_COV; ++i) a[i] = 0.0;
@@ -264,7 +279,7 @@ __device__ __forceinline__ void rgbd_refine(const Cells &ce, int nValid, float t
                     rgbd_acc_cov(a, cp, cX, (double)ce.px[k], (double)ce.py[k], (double)ce.pz[k],
                                  (double)ce.X[k], (double)ce.Y[k], (double)ce.Z[k]);
         }
-        block_reduce<XLR_SUMS_COV>(a, S.red[redSel], wave, lane); redSel ^= 1;
+        block_sum(a, S.red[redSel], wave, lane); redSel ^= 1;
         rgbd_kabsch_fit(cp, cX, a, &pose);
         ro.finalInl = cnt;
         ++ro.rounds;

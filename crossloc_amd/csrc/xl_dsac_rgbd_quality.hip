@@ -1,7 +1,8 @@
 // xl_dsac_rgbd_quality.hip — per-frame pose quality for the RGB-D DSAC* solver on MI355X (gfx950): inlier statistics of the metric
 // 3-D residuals, their JtJ over the inliers and the pose covariance at ONE given pose per image.
 //
-// A stand-alone pass behind xl_dsac_pose_quality_rgbd_batch (include/crossloc_dsac.h, row layout there), the sibling of
+// A stand-alone pass behind xl_dsac_pose_quality_rgbd_batch (include/crossloc_dsac.h, row layout there; the input record RgbdIn and
+// its shared checks, rgbd_input, are in xl_dsac_rgbd_dev.h), the sibling of
 // xl_dsac_quality.hip; the solver's kernels in xl_dsac_rgbd.hip are not involved.  One 256-thread workgroup (4 wavefronts) per
 // image, two walks over the cells:
 //
@@ -11,7 +12,7 @@
 //              re-reads what the first one left in the cache
 //   walk 1     valid cells (camera z != 0): distance error in cm (rgbd_cell_err), soft-inlier term; for inliers (e < thr, the
 //              float comparison the refinement makes) the count, sum m, sum e, sum e^2 and SSE
-//   reduce     9 per-thread double partials in the solver's canonical order: xor butterfly per wave, waves added 0, 1, 2, 3;
+//   reduce     9 per-thread double partials in the solver's canonical order (block_sum, xl_dsac_reduce.h);
 //              every thread forms the inlier centroid c from the LDS totals itself (uniform, no broadcast)
 //   walk 2     the same inlier decision with the same bits; about c: C = sum u u^T, sum u x r, sum r; reduced the same way
 //   finish     thread 0: 3x3 Cholesky inverse with a relative pivot test, the maps to the row's pose parameters, the row
@@ -28,7 +29,7 @@
 
 namespace {
 
-#include "xl_dsac_rgbd_dev.h"          // RgbdIn, rgbd_load_cam, kThreads, kWaves
+#include "xl_dsac_rgbd_dev.h"          // RgbdIn, rgbd_input, rgbd_load_cam, block_sum, kThreads, kWaves
 #include "xl_dsac_rgbd_quality_math.h"
 
 static_assert(XLQ_ROW == XL_DSAC_QUALITY_DOUBLES, "row width of the shared arithmetic and of the C ABI");
@@ -38,25 +39,6 @@ struct RgbdQualityParams : RgbdIn {
     double *rows;                     // [B][64]
     float thr, alpha, maxDist;
 };
-
-// canonical block sum of K per-thread values into s (every thread gets the totals): butterfly per wave, waves added in order
-template <int K>
-__device__ __forceinline__ void quality_block_sum(const double (&a)[K], double *red, int wave, int lane, double (&s)[K])
-{
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = wave_butterfly(a[k]);
-        if (lane == 0) red[wave * K + k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double tot = red[k];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) tot = tot + red[w * K + k];
-        s[k] = tot;
-    }
-}
 
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_rgbd_quality_kernel(RgbdQualityParams P)
@@ -84,35 +66,35 @@ void xl_dsac_rgbd_quality_kernel(RgbdQualityParams P)
     else pose_identity(&pose);
 
     const float *g = P.coords + (int64_t)b * P.sb;
-    double a1[XLQR_SUMS1], s1[XLQR_SUMS1];
+    double s1[XLQR_SUMS1];              // per-thread partials, then the totals
 #pragma unroll
-    for (int k = 0; k < XLQR_SUMS1; ++k) a1[k] = 0.0;
+    for (int k = 0; k < XLQR_SUMS1; ++k) s1[k] = 0.0;
     if (poseOk) {
         for (int i = tid; i < N; i += kThreads) {
             const int y = i / P.Wo, x = i - y * P.Wo;
             float cx, cy, cz;
             rgbd_load_cam(P, b, f, y, x, cx, cy, cz);
             const float *X = g + (int64_t)y * P.sy + (int64_t)x * P.sx;
-            rgbdq_cell1(&pose, (double)X[0], (double)X[P.sc], (double)X[2 * P.sc], cx, cy, cz, &q, beta, a1);
+            rgbdq_cell1(&pose, (double)X[0], (double)X[P.sc], (double)X[2 * P.sc], cx, cy, cz, &q, beta, s1);
         }
     }
-    quality_block_sum<XLQR_SUMS1>(a1, red1, wave, lane, s1);
+    block_sum(s1, red1, wave, lane);
     double c[3];
     rgbdq_centroid(s1, c);
 
-    double a2[XLQR_SUMS2], s2[XLQR_SUMS2];
+    double s2[XLQR_SUMS2];
 #pragma unroll
-    for (int k = 0; k < XLQR_SUMS2; ++k) a2[k] = 0.0;
+    for (int k = 0; k < XLQR_SUMS2; ++k) s2[k] = 0.0;
     if (poseOk) {
         for (int i = tid; i < N; i += kThreads) {
             const int y = i / P.Wo, x = i - y * P.Wo;
             float cx, cy, cz;
             rgbd_load_cam(P, b, f, y, x, cx, cy, cz);
             const float *X = g + (int64_t)y * P.sy + (int64_t)x * P.sx;
-            rgbdq_cell2(&pose, (double)X[0], (double)X[P.sc], (double)X[2 * P.sc], cx, cy, cz, &q, c, a2);
+            rgbdq_cell2(&pose, (double)X[0], (double)X[P.sc], (double)X[2 * P.sc], cx, cy, cz, &q, c, s2);
         }
     }
-    quality_block_sum<XLQR_SUMS2>(a2, red2, wave, lane, s2);
+    block_sum(s2, red2, wave, lane);
     if (tid != 0) return;
     double row[XLQ_ROW];
     rgbdq_row(s1, s2, c, &pose, &q, poseOk, row, nullptr);
@@ -130,17 +112,11 @@ extern "C" int xl_dsac_pose_quality_rgbd_batch(const float *coords_dev, int64_t 
                                                float focal, float ppx, float ppy, int sub, const float *focals_dev,
                                                double *rows_dev, void *stream)
 {
-    if (!coords_dev || !poses_dev || !rows_dev || (cam_dev == nullptr) == (depth_dev == nullptr)
-        || B <= 0 || Ho <= 0 || Wo <= 0 || sub <= 0)
+    RgbdQualityParams P;
+    if (rgbd_input(P, coords_dev, sb, sc, sy, sx, cam_dev, mb, mc, my, mx, depth_dev, db, dy, dx, B, Ho, Wo, focal, ppx, ppy, sub,
+                   focals_dev) != XL_OK || !poses_dev || !rows_dev || sub <= 0)
         return XL_ERR_ARG;
     if ((int64_t)Ho * (int64_t)Wo > (int64_t)INT32_MAX - kThreads) return XL_ERR_GRID;       // the cell index is an int
-    RgbdQualityParams P;
-    P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
-    P.cam = cam_dev; P.mb = mb; P.mc = mc; P.my = my; P.mx = mx;
-    P.depth = depth_dev; P.db = db; P.dy = dy; P.dx = dx;
-    P.focals = focals_dev;
-    P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = 0;
-    P.focal = focal; P.ppx = ppx; P.ppy = ppy;
     P.poses = poses_dev; P.rows = rows_dev;
     P.thr = thr; P.alpha = alpha; P.maxDist = max_dist;
     hipLaunchKernelGGL(xl_dsac_rgbd_quality_kernel, dim3(B), dim3(kThreads), 0, (hipStream_t)stream, P);

@@ -267,22 +267,15 @@ def camera_coordinates(depth, focal, image_h, image_w, sub):
     return torch.stack([rx[:, None, :] * depth, ry[:, :, None] * depth, depth], dim=1)
 
 
-def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypotheses, inlierThreshold, inlierAlpha,
-                       maxDistError, image0=0, image_stride=1, seed=None, max_tries=None, debug=False, depth=None,
-                       focalLength=None, ppointX=None, ppointY=None, subSampling=None, focals=None):
-    """RGB-D DSAC* (dsacstar_rgbd_forward, dsacstar.cpp:495-612) for B images in one launch: Kabsch hypotheses from three cells'
-    scene and camera coordinates.  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides); EXACTLY ONE of cameraCoordinates
-    [B,3,Ho,Wo] float32 CUDA (any strides) and depth [B,Ho,Wo] float32 CUDA (any strides).  With `depth` the camera coordinates
-    are formed in the kernel from focalLength (or per-image `focals`), ppointX, ppointY and subSampling, as camera_coordinates
-    does.  inlierThreshold and maxDistError are in centimetres.  A cell is valid iff its camera z is nonzero.  outPoses [B,4,4]
-    float32 CUDA contiguous, written in place (asynchronous on the current stream).  With debug=True returns a dict of device
-    tensors: cells [B,nHyp,3] int32, tries [B,nHyp] int32, scores [B,nHyp] float64, dbg [B,16] float64 (layout:
-    include/crossloc_dsac.h)."""
+def _rgbd_source(fn, sceneCoordinates, cameraCoordinates, depth, intr, max_cells=None):
+    """What the three RGB-D wrappers check alike about where an image comes from: exactly one of cameraCoordinates and depth, its
+    dtype and shape, the intrinsics depth needs (intr = focalLength, ppointX, ppointY, subSampling, focals) and the staging
+    kernels' cell limit - before any device check."""
+    focalLength, ppointX, ppointY, subSampling, focals = intr
     _check_coords(sceneCoordinates, True)
     if (cameraCoordinates is None) == (depth is None):
-        raise RuntimeError("forward_rgbd_batch takes exactly one of cameraCoordinates and depth")
+        raise RuntimeError("%s takes exactly one of cameraCoordinates and depth" % fn)
     B, _, Ho, Wo = sceneCoordinates.shape
-    dev = sceneCoordinates.device
     other = cameraCoordinates if depth is None else depth
     if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
         raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
@@ -295,23 +288,57 @@ def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypo
             raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
         if int(subSampling) <= 0:
             raise RuntimeError("subSampling must be positive")
-    if Ho * Wo > RGBD_MAX_CELLS:
-        raise RuntimeError("forward_rgbd_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
-                           % (Ho * Wo, RGBD_MAX_CELLS))
-    if not isinstance(outPoses, torch.Tensor) or not sceneCoordinates.is_cuda or not other.is_cuda or not outPoses.is_cuda:
-        raise RuntimeError("forward_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
-    if other.device != dev or outPoses.device != dev:
+    if max_cells is not None and Ho * Wo > max_cells:
+        raise RuntimeError("%s stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d" % (fn, Ho * Wo, max_cells))
+
+
+def _rgbd_on_device(fn, sceneCoordinates, cameraCoordinates, depth, mine):
+    """The device checks of a wrapper: sceneCoordinates, the camera tensor or depth and `mine`, the wrapper's own tensor."""
+    other = cameraCoordinates if depth is None else depth
+    if not isinstance(mine, torch.Tensor) or not sceneCoordinates.is_cuda or not other.is_cuda or not mine.is_cuda:
+        raise RuntimeError("%s needs CUDA(HIP) tensors; there is no CPU fallback" % fn)
+    if other.device != sceneCoordinates.device or mine.device != sceneCoordinates.device:
         raise RuntimeError("all tensors must be on the device of sceneCoordinates")
-    if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4) or not outPoses.is_contiguous():
-        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor")
-    if int(ransacHypotheses) <= 0:
-        raise RuntimeError("ransacHypotheses must be positive")
+
+
+def _rgbd_call_args(sceneCoordinates, cameraCoordinates, depth, intr):
+    """What a ctypes call needs of the RGB-D input, after the wrapper's own checks: the pointer/stride prefix up to B, Ho, Wo, the
+    intrinsics tail (focal, ppx, ppy, sub, focals), the device, and the converted per-image focals, which must outlive the call."""
+    focalLength, ppointX, ppointY, subSampling, focals = intr
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
     if focals is not None:
         focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
         if focals.numel() != B:
             raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
-        if focalLength is None:
-            focalLength = 0.0
+    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
+    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
+    prefix = (_ptr(sceneCoordinates), *sceneCoordinates.stride(), _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
+              B, Ho, Wo)
+    tail = (float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals))
+    return prefix, tail, dev, focals
+
+
+def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypotheses, inlierThreshold, inlierAlpha,
+                       maxDistError, image0=0, image_stride=1, seed=None, max_tries=None, debug=False, depth=None,
+                       focalLength=None, ppointX=None, ppointY=None, subSampling=None, focals=None):
+    """RGB-D DSAC* (dsacstar_rgbd_forward, dsacstar.cpp:495-612) for B images in one launch: Kabsch hypotheses from three cells'
+    scene and camera coordinates.  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides); EXACTLY ONE of cameraCoordinates
+    [B,3,Ho,Wo] float32 CUDA (any strides) and depth [B,Ho,Wo] float32 CUDA (any strides).  With `depth` the camera coordinates
+    are formed in the kernel from focalLength (or per-image `focals`), ppointX, ppointY and subSampling, as camera_coordinates
+    does.  inlierThreshold and maxDistError are in centimetres.  A cell is valid iff its camera z is nonzero.  outPoses [B,4,4]
+    float32 CUDA contiguous, written in place (asynchronous on the current stream).  With debug=True returns a dict of device
+    tensors: cells [B,nHyp,3] int32, tries [B,nHyp] int32, scores [B,nHyp] float64, dbg [B,16] float64 (layout:
+    include/crossloc_dsac.h)."""
+    intr = (focalLength, ppointX, ppointY, subSampling, focals)
+    _rgbd_source("forward_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, intr, RGBD_MAX_CELLS)
+    _rgbd_on_device("forward_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, outPoses)
+    B = sceneCoordinates.shape[0]
+    if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4) or not outPoses.is_contiguous():
+        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor")
+    if int(ransacHypotheses) <= 0:
+        raise RuntimeError("ransacHypotheses must be positive")
+    prefix, tail, dev, focals = _rgbd_call_args(sceneCoordinates, cameraCoordinates, depth, intr)
     out = None
     cells = tries = scores = dbg = None
     if debug:
@@ -320,15 +347,10 @@ def forward_rgbd_batch(sceneCoordinates, cameraCoordinates, outPoses, ransacHypo
         scores = torch.zeros((B, ransacHypotheses), dtype=torch.float64, device=dev)
         dbg = torch.zeros((B, RGBD_DBG_DOUBLES), dtype=torch.float64, device=dev)
         out = dict(cells=cells, tries=tries, scores=scores, dbg=dbg)
-    sb, sc, sy, sx = sceneCoordinates.stride()
-    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
-    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         rc = _lib.lib().xl_dsac_forward_rgbd_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
-            B, Ho, Wo, _ptr(outPoses), int(ransacHypotheses), float(inlierThreshold), float(inlierAlpha), float(maxDistError),
-            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            *prefix, _ptr(outPoses), int(ransacHypotheses), float(inlierThreshold), float(inlierAlpha), float(maxDistError), *tail,
             int(RANSAC_SEED if seed is None else seed), int(image0), int(image_stride),
             int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream),
             _ptr(cells), _ptr(tries), _ptr(scores), _ptr(dbg))
@@ -352,26 +374,9 @@ def backward_rgbd_batch(sceneCoordinates, cameraCoordinates, outSceneCoordinates
     seed and image keys of a forward_rgbd_batch call the hypotheses and scores are that call's, bit for bit.  Returns the expected
     losses as a float64 CUDA tensor [B] (asynchronous on the current stream); with debug=True also the per-hypothesis records
     [B,nHyp,RGBD_BWD_REC] (layout, deviations from the reference and the two guards: include/crossloc_dsac.h)."""
-    _check_coords(sceneCoordinates, True)
-    if (cameraCoordinates is None) == (depth is None):
-        raise RuntimeError("backward_rgbd_batch takes exactly one of cameraCoordinates and depth")
-    B, _, Ho, Wo = sceneCoordinates.shape
-    dev = sceneCoordinates.device
-    other = cameraCoordinates if depth is None else depth
-    if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
-        raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
-    if depth is None and tuple(other.shape) != (B, 3, Ho, Wo):
-        raise RuntimeError("cameraCoordinates must be [B,3,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
-    if depth is not None:
-        if tuple(other.shape) != (B, Ho, Wo):
-            raise RuntimeError("depth must be [B,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
-        if (focalLength is None and focals is None) or ppointX is None or ppointY is None or subSampling is None:
-            raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
-        if int(subSampling) <= 0:
-            raise RuntimeError("subSampling must be positive")
-    if Ho * Wo > RGBD_MAX_CELLS:
-        raise RuntimeError("backward_rgbd_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
-                           % (Ho * Wo, RGBD_MAX_CELLS))
+    intr = (focalLength, ppointX, ppointY, subSampling, focals)
+    _rgbd_source("backward_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, intr, RGBD_MAX_CELLS)
+    B = sceneCoordinates.shape[0]
     g = outSceneCoordinatesGrad
     if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != tuple(sceneCoordinates.shape):
         raise RuntimeError("outSceneCoordinatesGrad must be float32 with the shape of sceneCoordinates")
@@ -379,28 +384,16 @@ def backward_rgbd_batch(sceneCoordinates, cameraCoordinates, outSceneCoordinates
         raise RuntimeError("gtPoses must be a [B,4,4] tensor")
     if int(ransacHypotheses) <= 0:
         raise RuntimeError("ransacHypotheses must be positive")
-    if not sceneCoordinates.is_cuda or not other.is_cuda or not g.is_cuda:
-        raise RuntimeError("backward_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
-    if other.device != dev or g.device != dev:
-        raise RuntimeError("all tensors must be on the device of sceneCoordinates")
-    if focals is not None:
-        focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
-        if focals.numel() != B:
-            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    _rgbd_on_device("backward_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, g)
+    prefix, tail, dev, focals = _rgbd_call_args(sceneCoordinates, cameraCoordinates, depth, intr)
     gt = gtPoses.to(device=dev, dtype=torch.float32).reshape(B, 16).contiguous()
     loss = torch.zeros((B,), dtype=torch.float64, device=dev)
     rec = torch.zeros((B, int(ransacHypotheses), RGBD_BWD_REC), dtype=torch.float64, device=dev) if debug else None
-    sb, sc, sy, sx = sceneCoordinates.stride()
-    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
-    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
-    gb, gc, gy, gx = g.stride()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         rc = _lib.lib().xl_dsac_backward_rgbd_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
-            B, Ho, Wo, _ptr(g), gb, gc, gy, gx, _ptr(gt), _ptr(loss), int(ransacHypotheses), float(inlierThreshold),
-            float(inlierAlpha), float(maxDistError), float(wLossRot), float(wLossTrans), float(softClamp),
-            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            *prefix, _ptr(g), *g.stride(), _ptr(gt), _ptr(loss), int(ransacHypotheses), float(inlierThreshold),
+            float(inlierAlpha), float(maxDistError), float(wLossRot), float(wLossTrans), float(softClamp), *tail,
             int(randomSeed), int(image0), int(image_stride),
             int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream), _ptr(rec))
     _lib.check(rc)
@@ -425,43 +418,18 @@ def pose_quality_rgbd_batch(sceneCoordinates, cameraCoordinates, poses, inlierTh
     [B,3,Ho,Wo] and depth [B,Ho,Wo] (float32 CUDA, any strides; depth needs focalLength or focals, ppointX, ppointY, subSampling),
     thresholds in centimetres; poses [B,4,4] float32 CUDA contiguous cam->world.  Returns a float64 CUDA tensor [B,64]
     (RGBD_QUALITY_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
-    _check_coords(sceneCoordinates, True)
-    if (cameraCoordinates is None) == (depth is None):
-        raise RuntimeError("pose_quality_rgbd_batch takes exactly one of cameraCoordinates and depth")
-    B, _, Ho, Wo = sceneCoordinates.shape
-    dev = sceneCoordinates.device
-    other = cameraCoordinates if depth is None else depth
-    if not isinstance(other, torch.Tensor) or other.dtype != torch.float32:
-        raise RuntimeError("cameraCoordinates / depth must be a float32 torch.Tensor")
-    if depth is None and tuple(other.shape) != (B, 3, Ho, Wo):
-        raise RuntimeError("cameraCoordinates must be [B,3,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
-    if depth is not None:
-        if tuple(other.shape) != (B, Ho, Wo):
-            raise RuntimeError("depth must be [B,Ho,Wo] like sceneCoordinates, got %s" % (tuple(other.shape),))
-        if (focalLength is None and focals is None) or ppointX is None or ppointY is None or subSampling is None:
-            raise RuntimeError("depth needs focalLength (or focals), ppointX, ppointY and subSampling")
-        if int(subSampling) <= 0:
-            raise RuntimeError("subSampling must be positive")
-    if not isinstance(poses, torch.Tensor) or not sceneCoordinates.is_cuda or not other.is_cuda or not poses.is_cuda:
-        raise RuntimeError("pose_quality_rgbd_batch needs CUDA(HIP) tensors; there is no CPU fallback")
-    if other.device != dev or poses.device != dev:
-        raise RuntimeError("all tensors must be on the device of sceneCoordinates")
+    intr = (focalLength, ppointX, ppointY, subSampling, focals)
+    _rgbd_source("pose_quality_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, intr)
+    _rgbd_on_device("pose_quality_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, poses)
+    B = sceneCoordinates.shape[0]
     if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
         raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
-    if focals is not None:
-        focals = torch.as_tensor(focals).to(device=dev, dtype=torch.float32).contiguous()
-        if focals.numel() != B:
-            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    prefix, tail, dev, focals = _rgbd_call_args(sceneCoordinates, cameraCoordinates, depth, intr)
     rows = torch.empty((B, QUALITY_DOUBLES), dtype=torch.float64, device=dev)      # (the kernel writes all 64 of every row)
-    sb, sc, sy, sx = sceneCoordinates.stride()
-    mb, mc, my, mx = cameraCoordinates.stride() if depth is None else (0, 0, 0, 0)
-    db, dy, dx = depth.stride() if depth is not None else (0, 0, 0)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
         rc = _lib.lib().xl_dsac_pose_quality_rgbd_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(cameraCoordinates), mb, mc, my, mx, _ptr(depth), db, dy, dx,
-            B, Ho, Wo, _ptr(poses), float(inlierThreshold), float(inlierAlpha), float(maxDistError),
-            float(focalLength or 0.0), float(ppointX or 0.0), float(ppointY or 0.0), int(subSampling or 1), _ptr(focals),
+            *prefix, _ptr(poses), float(inlierThreshold), float(inlierAlpha), float(maxDistError), *tail,
             _ptr(rows), ctypes.c_void_p(stream))
     _lib.check(rc)
     return rows

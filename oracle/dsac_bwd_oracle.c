@@ -162,7 +162,7 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
                     for (int k = 0; k < 28; ++k) part[tdx].v[k] = a[k];
                 }
                 double ne[28], A[36], Ainv[36];
-                xo_reduce28(part, ne);
+                block_sum(part[0].v, 28, ne);
                 free(part);
                 int k = 0;
                 for (int r = 0; r < 6; ++r)
@@ -239,7 +239,7 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
             for (int k = 0; k < 28; ++k) part[tdx].v[k] = a[k];
         }
         double g28[28];
-        xo_reduce28(part, g28);
+        block_sum(part[0].v, 28, g28);
         free(part);
         float obj[4][3];
         double uv[4][2];
@@ -322,7 +322,7 @@ double xo_test_resid_row(const double *Rt12, const double *r3, const double *X3,
     const Cam cam = xo_test_cam(f, cx, cy, maxReproj);
     Pose p;
     double dR[27];
-    xo_pose_from12(Rt12, &p);
+    pose_load12(Rt12, &p);
     rodrigues_jac(r3, dR);
     return resid_row(&p, dR, X3[0], X3[1], X3[2], px, py, &cam, J6);
 }
@@ -331,14 +331,14 @@ void xo_test_dproject_dobj(const double *Rt12, const double *X3, float px, float
 {
     const Cam cam = xo_test_cam(f, cx, cy, maxReproj);
     Pose p;
-    xo_pose_from12(Rt12, &p);
+    pose_load12(Rt12, &p);
     dproject_dobj(&p, X3[0], X3[1], X3[2], px, py, &cam, out3);
 }
 double xo_test_pose_loss(const double *Rt12, const float *gt16, double wRot, double wTrans, double cut)
 {
     Pose p;
     Gt g;
-    xo_pose_from12(Rt12, &p);
+    pose_load12(Rt12, &p);
     gt_from_pose16(gt16, &g);
     return pose_loss(&p, &g, wRot, wTrans, cut);
 }
@@ -347,7 +347,7 @@ void xo_test_dloss(const double *Rt12, const double *r3, const float *gt16, doub
     Pose p;
     Gt g;
     double dR[27];
-    xo_pose_from12(Rt12, &p);
+    pose_load12(Rt12, &p);
     gt_from_pose16(gt16, &g);
     rodrigues_jac(r3, dR);
     dloss(&p, dR, &g, wRot, wTrans, cut, jac6);

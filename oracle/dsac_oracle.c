@@ -9,7 +9,7 @@
  * RNG, projection and cell error, quartic, P3P, Cholesky step, the backward pass's derivatives) is the product's
  * crossloc_amd/csrc/xl_dsac_math.h, compiled here by gcc as C99.  This file restates serially what the kernels do in
  * parallel around it: the try loop (first accepted try), the lane-strided partial sums and the xor-butterfly, the
- * 256-thread reduction of the normal equations, the LM state machine, refinement, both drivers.  So bitwise GPU == oracle
+ * 256-thread reduction of the normal equations (block_sum of xl_dsac_reduce.h, where the order is stated), the LM state machine, refinement, both drivers.  So bitwise GPU == oracle
  * checks that orchestration and that gcc and hipcc agree on the same IEEE operations; it does NOT check the shared
  * formulas.  Those are guarded by the known answers below, by the independent implementation (tests/indep_dsac.py) and,
  * against a change of rounding or expression order, by tests/test_oracle_dsac_pin.py.
@@ -64,6 +64,7 @@
 #endif
 
 #include "xl_dsac_math.h"             /* crossloc_amd/csrc: the lane-local arithmetic, shared with the kernels */
+#include "xl_dsac_reduce.h"           /* the canonical block sum and its order (plain-C half) */
 
 #define XO_MAX_REF_STEPS 100          /* dsacstar.cpp:47 */
 #define XO_LM_MAX_ITER 20             /* cv::solvePnP ITERATIVE term criteria */
@@ -99,12 +100,6 @@ static Cam xo_test_cam(double f, double cx, double cy, float maxReproj)
     Cam cam = xo_cam(0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, maxReproj, 0);
     cam.f = f; cam.cx = cx; cam.cy = cy;
     return cam;
-}
-
-static void xo_pose_from12(const double *Rt12, Pose *p)
-{
-    for (int i = 0; i < 9; ++i) p->R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) p->t[i] = Rt12[9 + i];
 }
 
 /* clamped reprojection error of cell i */
@@ -162,18 +157,6 @@ static int32_t xo_sample_hyp(const xo_coords *co, const Cam *cam, uint64_t image
     return -(int32_t)maxTries;
 }
 
-/* ------------------------------------------------------------------ fixed-order reductions */
-
-static double xo_butterfly64(double p[64])
-{
-    double q[64];
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ off];
-        memcpy(p, q, sizeof(q));
-    }
-    return p[0];
-}
-
 /* soft-inlier score of one pose (dsacstar_util.h:316-343 over the map of :356-446):
  * lane l accumulates cells l, l+64, ... in row-major cell order, then the butterfly. */
 static double xo_score(const xo_coords *co, const Pose *pose, const Cam *cam)
@@ -191,32 +174,17 @@ static double xo_score(const xo_coords *co, const Pose *pose, const Cam *cam)
         }
         part[l] = acc;
     }
-    double total = xo_butterfly64(part);
+    double total = butterfly64(part);
     float fac = cam->alpha / (float)cam->Wo / (float)cam->Ho;
     return total * (double)fac;
 }
 
 /* ------------------------------------------------------------------ LM refinement */
 
-#define XO_T 256   /* threads of the canonical reduction: 4 waves of 64 */
+#define XO_T XL_BLOCK_THREADS
 
-/* canonical sum over cells of per-cell 28-vectors: thread-strided partials, butterfly per wave,
- * waves added in order 0..3. */
+/* per-thread 28-vectors of the canonical block sum (block_sum, xl_dsac_reduce.h): [XO_T][28] contiguous */
 typedef struct { double v[28]; } xo_vec28;
-
-static void xo_reduce28(const xo_vec28 *part /*[XO_T]*/, double out[28])
-{
-    for (int k = 0; k < 28; ++k) {
-        double tot = 0.0;
-        for (int w = 0; w < XO_T / 64; ++w) {
-            double p[64];
-            for (int l = 0; l < 64; ++l) p[l] = part[w * 64 + l].v[k];
-            double ws = xo_butterfly64(p);
-            tot = (w == 0) ? ws : tot + ws;
-        }
-        out[k] = tot;
-    }
-}
 
 /* normal equations of the reprojection residuals over the inlier set at pose p:
  * out[0..20] upper triangle of JtJ (row-major), out[21..26] Jt r, out[27] sum r^2 */
@@ -258,7 +226,7 @@ static void xo_normal_eq(const xo_coords *co, const unsigned char *inl, const Po
         }
         for (int k = 0; k < 28; ++k) part[tdx].v[k] = a[k];
     }
-    xo_reduce28(part, out);
+    block_sum(part[0].v, 28, out);
     free(part);
 }
 
@@ -432,7 +400,7 @@ double xo_test_score(const float *coords, int64_t sc, int64_t sy, int64_t sx, in
     xo_coords co = { coords, sc, sy, sx, Ho, Wo };
     const Cam cam = xo_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     Pose p;
-    xo_pose_from12(Rt12, &p);
+    pose_load12(Rt12, &p);
     return xo_score(&co, &p, &cam);
 }
 

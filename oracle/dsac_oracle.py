@@ -19,8 +19,8 @@ _lib = None
 def build(force=False):
     """Compile the C restatement (gcc, seconds)."""
     src = os.path.join(_HERE, "dsac_oracle.c")
-    srcs = [src, os.path.join(_HERE, "dsac_bwd_oracle.c"),
-            os.path.join(os.path.dirname(_HERE), "crossloc_amd", "csrc", "xl_dsac_math.h")]     # shared with the kernels
+    csrc = os.path.join(os.path.dirname(_HERE), "crossloc_amd", "csrc")                          # shared with the kernels
+    srcs = [src, os.path.join(_HERE, "dsac_bwd_oracle.c"), os.path.join(csrc, "xl_dsac_math.h"), os.path.join(csrc, "xl_dsac_reduce.h")]
     if os.environ.get("XL_ORACLE_LIB"):
         return _LIB_PATH             # (built by whoever set the variable)
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(s) for s in srcs):

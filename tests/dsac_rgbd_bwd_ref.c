@@ -4,67 +4,17 @@
  * TEST INFRASTRUCTURE ONLY.  The lane-local arithmetic is the product's xl_dsac_rgbd_bwd_math.h, compiled here by gcc as C99
  * with -ffp-contract=off.  This file restates serially what kernels K0-K4 do in parallel around it, with their reduction
  * orders: K0 is the forward restatement's sampling and scoring (tests/dsac_rgbd_ref.c, included below), K1 the refinement's
- * walk of 256 virtual threads with the waves added in order, K2 the serial expectation, K3 the twelve sums per virtual thread
+ * walk of 256 virtual threads (xr_refine, rgbd_ref_common.h), K2 the serial expectation, K3 the twelve sums per virtual thread
  * and their block reduction, K4 the per-cell assembly over the hypotheses in ascending order with float accumulation.
  * Bitwise GPU == this file checks the kernels' orchestration; the formulas are checked against tests/indep_dsac_rgbd_bwd.py
  * (numpy SVD Kabsch and central differences), which shares no code with the header.
  *
  * With -DXB_MAIN the file is a program of its own (for the sanitizer run): see main() at the end.
  */
-#include "dsac_rgbd_ref.c"            /* staging, butterflies, block reduction, the forward restatement (K0) */
+#include "dsac_rgbd_ref.c"            /* rgbd_ref_common.h (staging, refinement, block sum) and the forward restatement (K0) */
 #include "xl_dsac_rgbd_bwd_math.h"    /* crossloc_amd/csrc: shared with the kernels */
 
 #define XB_REC XLR_BWD_REC
-
-typedef struct { unsigned finalInl; int rounds; double cp[3], cX[3], a[XLR_SUMS_COV]; } XbRefine;
-
-/* the refinement loop of the forward restatement for one hypothesis; inl [nValid] = the inlier set of the last FITTED round */
-static void xb_refine(const Staged *S, int nValid, float thr, float maxDist, Pose *pose, XbRefine *ro, uint8_t *inlOut,
-                      uint8_t *inl, double *part)
-{
-    unsigned best = 3;
-    memset(ro, 0, sizeof(*ro));
-    memset(inlOut, 0, (size_t)(nValid > 0 ? nValid : 1));
-    for (int step = 0; step < XR_MAX_REF_STEPS; ++step) {
-        unsigned cnt = 0;
-        for (int k = 0; k < nValid; ++k) {
-            inl[k] = xr_err(S, pose, k, maxDist) < thr;
-            cnt += inl[k];
-        }
-        if (cnt <= best) break;
-        best = cnt;
-        double s[XLR_SUMS_CENTROID], a[XLR_SUMS_COV], cp[3], cX[3];
-        for (int tid = 0; tid < XR_T; ++tid) {
-            double *v = part + tid * XLR_SUMS_CENTROID;
-            for (int k = 0; k < XLR_SUMS_CENTROID; ++k) v[k] = 0.0;
-            for (int k = tid; k < nValid; k += XR_T)
-                if (inl[k]) rgbd_acc_centroid(v, (double)S->p[0][k], (double)S->p[1][k], (double)S->p[2][k],
-                                              (double)S->X[0][k], (double)S->X[1][k], (double)S->X[2][k]);
-        }
-        xr_block_reduce(part, XLR_SUMS_CENTROID, s);
-        rgbd_centroids(s, cp, cX);
-        for (int tid = 0; tid < XR_T; ++tid) {
-            double *v = part + tid * XLR_SUMS_COV;
-            for (int k = 0; k < XLR_SUMS_COV; ++k) v[k] = 0.0;
-            for (int k = tid; k < nValid; k += XR_T)
-                if (inl[k]) rgbd_acc_cov(v, cp, cX, (double)S->p[0][k], (double)S->p[1][k], (double)S->p[2][k],
-                                         (double)S->X[0][k], (double)S->X[1][k], (double)S->X[2][k]);
-        }
-        xr_block_reduce(part, XLR_SUMS_COV, a);
-        rgbd_kabsch_fit(cp, cX, a, pose);
-        ro->finalInl = cnt;
-        ++ro->rounds;
-        memcpy(inlOut, inl, (size_t)nValid);
-        for (int i = 0; i < 3; ++i) { ro->cp[i] = cp[i]; ro->cX[i] = cX[i]; }
-        for (int i = 0; i < XLR_SUMS_COV; ++i) ro->a[i] = a[i];
-    }
-}
-
-static void xb_load_pose(const double *src, Pose *p)
-{
-    for (int i = 0; i < 9; ++i) p->R[i] = src[i];
-    for (int i = 0; i < 3; ++i) p->t[i] = src[9 + i];
-}
 
 /*
  * One image.  grad [3,Ho,Wo] float32 (strides gc, gy, gx) is ACCUMULATED.  rec [nHyp, 64] as the kernels write it.  Optional
@@ -93,8 +43,9 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     int st = xr_forward_rgbd(coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, nHyp, thr, alpha, maxDist, focal, ppx, ppy,
                              sub, seed, image, maxTries, pose16, cellOf, NULL, scores, NULL, hyp, NULL, NULL, NULL);
     if (st != 0) { free(hyp); free(scores); free(cellOf); return st; }
+    const RgbdSrc in = xr_src(coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, focal, ppx, ppy, sub);
     Staged S;
-    const int nValid = xr_stage(&S, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, focal, ppx, ppy, sub);
+    const int nValid = xr_stage(&S, &in, Ho, Wo);
     int32_t *placeOf = (int32_t *)malloc(sizeof(int32_t) * (size_t)N);
     for (int i = 0; i < N; ++i) placeOf[i] = -1;
     for (int k = 0; k < nValid; ++k) placeOf[S.cell[k]] = k;
@@ -106,7 +57,6 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     Gt gt;
     gt_from_pose16(gt16, &gt);
     uint8_t *masks = (uint8_t *)calloc((size_t)nHyp * (size_t)(nValid > 0 ? nValid : 1), 1);
-    uint8_t *inl = (uint8_t *)malloc((size_t)(nValid > 0 ? nValid : 1));
     double *part = (double *)malloc(sizeof(double) * XR_T * 12);
 
     /* ---- K1: probability, refinement, loss, path-I quantities */
@@ -115,14 +65,14 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
         for (int i = 0; i < XB_REC; ++i) r[i] = 0.0;
         const double prob = rgbd_softmax_prob(scores, nHyp, h);
         Pose pose;
-        xb_load_pose(hyp + 12 * h, &pose);
+        pose_load12(hyp + 12 * h, &pose);
         if (prob < XLM_PROB_THRESH) {
             r[0] = prob;
             r[1] = pose_loss(&pose, &gt, (double)wRot, (double)wTrans, (double)softClamp);
             continue;
         }
-        XbRefine ro;
-        xb_refine(&S, nValid, thr, maxDist, &pose, &ro, masks + (size_t)h * (size_t)(nValid > 0 ? nValid : 1), inl, part);
+        XrRefine ro;
+        xr_refine(&S, thr, maxDist, &pose, &ro, masks + (size_t)h * (size_t)(nValid > 0 ? nValid : 1), NULL, NULL, NULL, N);
         const double loss = pose_loss(&pose, &gt, (double)wRot, (double)wTrans, (double)softClamp);
         double H[9] = { 0 }, v[3] = { 0 }, gap = 0.0;
         int guardI = 0;
@@ -139,7 +89,7 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
             }
         }
         r[0] = prob; r[1] = loss; r[2] = 1.0; r[3] = (double)ro.finalInl; r[4] = (double)guardI;
-        xr_store12(&pose, r + 6);
+        pose_store12(&pose, r + 6);
         for (int i = 0; i < 9; ++i) r[18 + i] = H[i];
         for (int i = 0; i < 3; ++i) { r[27 + i] = v[i]; r[30 + i] = ro.cp[i]; }
         r[56] = gap;
@@ -164,7 +114,7 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
         double *r = rec + (size_t)h * XB_REC;
         if (r[0] < XLM_PROB_THRESH) continue;
         Pose init;
-        xb_load_pose(hyp + 12 * h, &init);
+        pose_load12(hyp + 12 * h, &init);
         const double sog = r[5];
         for (int tid = 0; tid < XR_T; ++tid) {
             double *s = part + tid * 12;
@@ -178,7 +128,7 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
             }
         }
         double sum[12];
-        xr_block_reduce(part, 12, sum);          /* (component-wise: the kernel's reductions of 9 and of 3 give the same bits) */
+        block_sum(part, 12, sum);          /* (component-wise: the kernel's reductions of 9 and of 3 give the same bits) */
         const double *sR = sum, *sT = sum + 9;
         const int32_t *pl = places + 3 * h;
         double sup[9] = { 0 }, maxW = 0.0, gap = 0.0;
@@ -231,7 +181,7 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
                 gI[0] = gI[0] - r[27]; gI[1] = gI[1] - r[28]; gI[2] = gI[2] - r[29];
             }
             Pose init;
-            xb_load_pose(hyp + 12 * h, &init);
+            pose_load12(hyp + 12 * h, &init);
             double jac[3] = { 0.0, 0.0, 0.0 }, w, dhat[3];
             if (rgbd_cell_weight(&init, X, Y, Z, px, py, pz, maxDist, beta, thr, r[5], facf, &w, dhat))
                 rgbd_cell_direct(&init, w, dhat, jac);
@@ -252,7 +202,7 @@ int xb_backward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
             for (int k = 0; k < nValid; ++k)
                 if (masks[(size_t)h * (size_t)nValid + (size_t)k]) masksOut[(size_t)h * (size_t)N + (size_t)S.cell[k]] = 1;
     }
-    free(part); free(inl); free(masks); free(places); free(placeOf);
+    free(part); free(masks); free(places); free(placeOf);
     xr_free(&S);
     free(hyp); free(scores); free(cellOf);
     return 0;
@@ -272,7 +222,7 @@ int xb_test_adjoint(int n, const double *p, const double *X, const double *GR, c
     Pose o;
     HornEig e;
     rgbd_kabsch_fit_eig(cp, cX, a, &o, &e);
-    xr_store12(&o, out12);
+    pose_store12(&o, out12);
     const int guard = rgbd_eig_gap(&e, relGap) ? 1 : 0;
     for (int i = 0; i < 3 * n; ++i) gradOut[i] = 0.0;
     if (guard) return 1;
@@ -297,7 +247,7 @@ double xb_test_pose_loss(const double *Rt12, const float *gt16, double wRot, dou
 {
     Pose p;
     Gt g;
-    xb_load_pose(Rt12, &p);
+    pose_load12(Rt12, &p);
     gt_from_pose16(gt16, &g);
     return pose_loss(&p, &g, wRot, wTrans, cut);
 }

@@ -6,11 +6,10 @@ fixture, so nothing is written into the repository tree.  `build_program(tmpdir,
 own main() as an executable, with AddressSanitizer and UBSan linked statically."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
-from dsac_rgbd_ref import CFLAGS, HERE, _el_strides, _ptr
+from rgbd_ref_common import HERE, INTR_ARGTYPES, SRC_ARGTYPES, _el_strides, _ptr, compile_lib, compile_program, source_args
 
 SRC = os.path.join(HERE, "dsac_rgbd_bwd_ref.c")
 REC = 64
@@ -26,8 +25,8 @@ class BwdRef:
         i64, ci, cf, cd, vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
         u64, u32 = ctypes.c_uint64, ctypes.c_uint32
         L.xb_backward_rgbd.restype = ci
-        L.xb_backward_rgbd.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, ci, ci, vp, i64, i64, i64, vp,
-                                       ci, cf, cf, cf, cf, cf, cf, cf, cf, cf, ci, u64, u64, u32, vp, vp, vp, vp, vp, vp]
+        L.xb_backward_rgbd.argtypes = SRC_ARGTYPES + [vp, i64, i64, i64, vp, ci, cf, cf, cf, cf, cf, cf] + INTR_ARGTYPES + [
+            u64, u64, u32] + [vp] * 6
         L.xb_test_adjoint.restype = ci
         L.xb_test_adjoint.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp]
         L.xb_test_softmax.restype = None
@@ -41,25 +40,11 @@ class BwdRef:
         """One image: coords float32 [3,Ho,Wo], cam float32 [3,Ho,Wo] or depth float32 [Ho,Wo] (any strides), gt_pose [4,4]
         cam->world.  `grad` (float32 [3,Ho,Wo], any strides) is accumulated in place; without it a zero tensor is made.  Returns a
         dict: loss, grad, rec [nHyp,64], cells [nHyp,3], scores [nHyp], hyp_poses [nHyp,12], masks [nHyp,Ho,Wo] bool."""
-        coords = np.asarray(coords)
-        assert coords.dtype == np.float32 and coords.ndim == 3 and coords.shape[0] == 3
-        _, Ho, Wo = coords.shape
-        sc, sy, sx = _el_strides(coords)
-        cc = cy = cx = dy = dx = 0
-        if cam is not None:
-            cam = np.asarray(cam)
-            assert cam.dtype == np.float32 and cam.shape == coords.shape
-            cc, cy, cx = _el_strides(cam)
-        if depth is not None:
-            depth = np.asarray(depth)
-            assert depth.dtype == np.float32 and depth.shape == (Ho, Wo)
-            dy, dx = _el_strides(depth)
-        ppx = Wo * sub / 2.0 if ppx is None else ppx
-        ppy = Ho * sub / 2.0 if ppy is None else ppy
+        prefix, intr, (coords, cam, depth) = source_args(coords, cam, depth, focal, ppx, ppy, sub)
+        Ho, Wo = coords.shape[1:]
         if grad is None:
             grad = np.zeros((3, Ho, Wo), np.float32)
         assert grad.dtype == np.float32 and grad.shape == coords.shape
-        gc, gy, gx = _el_strides(grad)
         gt16 = np.ascontiguousarray(np.asarray(gt_pose, np.float32).reshape(16))
         loss = np.zeros(1, np.float64)
         rec = np.zeros((n_hyp, REC), np.float64)
@@ -67,9 +52,8 @@ class BwdRef:
         scores = np.zeros(n_hyp, np.float64)
         hyp = np.zeros((n_hyp, 12), np.float64)
         masks = np.zeros((n_hyp, Ho, Wo), np.uint8)
-        rc = self.L.xb_backward_rgbd(_ptr(coords), sc, sy, sx, _ptr(cam), cc, cy, cx, _ptr(depth), dy, dx, Ho, Wo, _ptr(grad), gc, gy, gx,
-                                     _ptr(gt16), int(n_hyp), float(thr), float(alpha), float(max_dist), float(w_rot), float(w_trans),
-                                     float(soft_clamp), float(focal), float(ppx), float(ppy), int(sub), int(seed), int(image),
+        rc = self.L.xb_backward_rgbd(*prefix, _ptr(grad), *_el_strides(grad), _ptr(gt16), int(n_hyp), float(thr), float(alpha),
+                                     float(max_dist), float(w_rot), float(w_trans), float(soft_clamp), *intr, int(seed), int(image),
                                      int(max_tries), _ptr(loss), _ptr(rec), _ptr(cells), _ptr(scores), _ptr(hyp), _ptr(masks))
         if rc != 0:
             raise RuntimeError("dsac_rgbd_bwd_ref failed: %d" % rc)
@@ -100,16 +84,9 @@ class BwdRef:
 
 
 def load(tmpdir):
-    out = os.path.join(str(tmpdir), "libdsac_rgbd_bwd_ref.so")
-    subprocess.check_call(["gcc", "-O2", "-fPIC"] + CFLAGS + ["-I" + HERE, "-shared", "-o", out, SRC, "-lm"])
-    return BwdRef(out)
+    return BwdRef(compile_lib(tmpdir, SRC, "dsac_rgbd_bwd_ref"))
 
 
 def build_program(tmpdir, sanitize=True):
     """The restatement with its own main() as an executable; with `sanitize` under AddressSanitizer and UBSan."""
-    out = os.path.join(str(tmpdir), "dsac_rgbd_bwd_ref_san" if sanitize else "dsac_rgbd_bwd_ref_prog")
-    # the sanitizer runtimes are linked statically: the program then runs in whatever environment it inherits
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g",
-           "-static-libasan", "-static-libubsan"] if sanitize else []
-    subprocess.check_call(["gcc", "-O1", "-DXB_MAIN"] + san + CFLAGS + ["-I" + HERE, "-o", out, SRC, "-lm"])
-    return out
+    return compile_program(tmpdir, SRC, "dsac_rgbd_bwd_ref", "XB_MAIN", sanitize)

@@ -5,101 +5,16 @@
  * with -ffp-contract=off.  This file restates serially what the kernel does in parallel around it: the x-major list of
  * valid cells, the tries of a hypothesis in ascending order (the kernel's ballot picks the lowest accepted lane), the
  * 64-lane walk over the valid list with its xor butterfly, first-maximum-wins selection, and the refinement's walk of 256
- * virtual threads with the waves added in order 0, 1, 2, 3.  Bitwise GPU == this file checks the kernel's orchestration
+ * virtual threads (xr_refine, rgbd_ref_common.h; the order of its block sums: xl_dsac_reduce.h).  Bitwise GPU == this file checks the kernel's orchestration
  * and that gcc and hipcc agree on the same IEEE operations; the formulas themselves are checked against
  * tests/indep_dsac_rgbd.py (numpy, SVD Kabsch), which shares no code with the header.
  *
  * With -DXR_MAIN the file is a program of its own (for the sanitizer run): see main() at the end.
  */
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "rgbd_ref_common.h"          /* the input record, staging, the cell error, the refinement loop; xl_dsac_rgbd_math.h */
 
-#include "xl_dsac_rgbd_math.h"        /* crossloc_amd/csrc: shared with the kernel */
-
-#define XR_T 256                      /* threads of the kernel's workgroup: 4 waves of 64 */
-#define XR_WAVES (XR_T / 64)
-#define XR_MAX_REF_STEPS 100
 #define XR_DBG 16
 #define XR_MAX_CELLS 6144
-
-static double xr_butterfly64(double p[64])
-{
-    double q[64];
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ off];
-        memcpy(p, q, sizeof(q));
-    }
-    return p[0];
-}
-
-/* canonical block sum of K values per virtual thread: butterfly per wave, waves added in order */
-static void xr_block_reduce(const double *part /* [XR_T][K] */, int K, double *out)
-{
-    for (int k = 0; k < K; ++k) {
-        double tot = 0.0;
-        for (int w = 0; w < XR_WAVES; ++w) {
-            double p[64];
-            for (int l = 0; l < 64; ++l) p[l] = part[(w * 64 + l) * K + k];
-            const double ws = xr_butterfly64(p);
-            tot = (w == 0) ? ws : tot + ws;
-        }
-        out[k] = tot;
-    }
-}
-
-/* the staged image: six floats per valid cell in valid-list order, and the list itself (cell = y * Wo + x) */
-typedef struct { float *p[3], *X[3]; int *cell; int n; } Staged;
-
-static void xr_free(Staged *s)
-{
-    for (int c = 0; c < 3; ++c) { free(s->p[c]); free(s->X[c]); }
-    free(s->cell);
-}
-
-static int xr_stage(Staged *s, const float *coords, int64_t sc, int64_t sy, int64_t sx,
-                    const float *cam, int64_t cc, int64_t cy, int64_t cx, const float *depth, int64_t dy, int64_t dx,
-                    int Ho, int Wo, float f, float ppx, float ppy, int sub)
-{
-    const int N = Ho * Wo;
-    for (int c = 0; c < 3; ++c) {
-        s->p[c] = (float *)malloc(sizeof(float) * (size_t)N);
-        s->X[c] = (float *)malloc(sizeof(float) * (size_t)N);
-    }
-    s->cell = (int *)malloc(sizeof(int) * (size_t)N);
-    s->n = 0;
-    for (int x = 0; x < Wo; ++x)
-        for (int y = 0; y < Ho; ++y) {
-            float px, py, pz;
-            if (cam) {
-                const float *q = cam + (int64_t)y * cy + (int64_t)x * cx;
-                px = q[0]; py = q[cc]; pz = q[2 * cc];
-            } else {
-                rgbd_cam_from_depth(depth[(int64_t)y * dy + (int64_t)x * dx], y, x, f, ppx, ppy, sub, &px, &py, &pz);
-            }
-            if (!(pz != 0.0f)) continue;
-            const float *q = coords + (int64_t)y * sy + (int64_t)x * sx;
-            const int k = s->n++;
-            s->p[0][k] = px; s->p[1][k] = py; s->p[2][k] = pz;
-            s->X[0][k] = q[0]; s->X[1][k] = q[sc]; s->X[2][k] = q[2 * sc];
-            s->cell[k] = y * Wo + x;
-        }
-    return s->n;
-}
-
-static float xr_err(const Staged *s, const Pose *p, int k, float maxDist)
-{
-    return rgbd_cell_err(p, (double)s->X[0][k], (double)s->X[1][k], (double)s->X[2][k],
-                         (double)s->p[0][k], (double)s->p[1][k], (double)s->p[2][k], maxDist);
-}
-
-static void xr_store12(const Pose *p, double *o)
-{
-    for (int i = 0; i < 9; ++i) o[i] = p->R[i];
-    for (int i = 0; i < 3; ++i) o[9 + i] = p->t[i];
-}
 
 /*
  * One image.  Exactly one of cam ([3,Ho,Wo] strides cc, cy, cx) and depth ([Ho,Wo] strides dy, dx) is non-null.
@@ -119,8 +34,9 @@ int xr_forward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     if (!cam && sub <= 0) return -1;
     const int N = Ho * Wo;
     if (N > XR_MAX_CELLS) return -2;
+    const RgbdSrc in = xr_src(coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, focal, ppx, ppy, sub);
     Staged S;
-    const int nValid = xr_stage(&S, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, focal, ppx, ppy, sub);
+    const int nValid = xr_stage(&S, &in, Ho, Wo);
     const uint64_t imageKey = image_key(seed, image);
     const float beta = 5.0f / thr;
     const float fac = alpha / (float)Wo / (float)Ho;
@@ -155,13 +71,13 @@ int xr_forward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
             for (int k = l; k < nValid; k += 64) acc += rgbd_soft_term(xr_err(&S, &pose, k, maxDist), beta, thr);
             part[l] = acc;
         }
-        double total = xr_butterfly64(part);
+        double total = butterfly64(part);      /* the order: xl_dsac_reduce.h */
         total = total + (double)(N - nValid) * invalidTerm;
         const double score = total * (double)fac;
         if (cells) for (int j = 0; j < 3; ++j) cells[3 * h + j] = (ks[j] >= 0) ? S.cell[ks[j]] : -1;
         if (tries) tries[h] = triesUsed;
         if (scores) scores[h] = score;
-        if (hypPoses) xr_store12(&pose, hypPoses + 12 * h);
+        if (hypPoses) pose_store12(&pose, hypPoses + 12 * h);
         if (score != score) anyNan = 1;
         if (h == 0) pose0 = pose;
         if (win < 0 || score > winScore) { win = h; winScore = score; winPose = pose; }
@@ -170,50 +86,8 @@ int xr_forward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
 
     /* ---- refine (refineHypRGBD, dsacstar_util.h:611-677) */
     Pose pose = winPose;
-    unsigned best = 3, finalInl = 0;
-    int rounds = 0;
-    if (roundCounts) for (int r = 0; r < XR_MAX_REF_STEPS; ++r) roundCounts[r] = -1;
-    uint8_t *inl = (uint8_t *)malloc((size_t)(nValid > 0 ? nValid : 1));
-    double *part = (double *)malloc(sizeof(double) * XR_T * XLR_SUMS_COV);
-    for (int step = 0; step < XR_MAX_REF_STEPS; ++step) {
-        unsigned cnt = 0;
-        for (int k = 0; k < nValid; ++k) {
-            inl[k] = xr_err(&S, &pose, k, maxDist) < thr;
-            cnt += inl[k];
-        }
-        if (roundCounts) roundCounts[step] = (int32_t)cnt;
-        if (cnt <= best) break;
-        best = cnt;
-        double s[XLR_SUMS_CENTROID], a[XLR_SUMS_COV], cp[3], cX[3];
-        for (int tid = 0; tid < XR_T; ++tid) {
-            double *v = part + tid * XLR_SUMS_CENTROID;
-            for (int k = 0; k < XLR_SUMS_CENTROID; ++k) v[k] = 0.0;
-            for (int k = tid; k < nValid; k += XR_T)
-                if (inl[k]) rgbd_acc_centroid(v, (double)S.p[0][k], (double)S.p[1][k], (double)S.p[2][k],
-                                              (double)S.X[0][k], (double)S.X[1][k], (double)S.X[2][k]);
-        }
-        xr_block_reduce(part, XLR_SUMS_CENTROID, s);
-        rgbd_centroids(s, cp, cX);
-        for (int tid = 0; tid < XR_T; ++tid) {
-            double *v = part + tid * XLR_SUMS_COV;
-            for (int k = 0; k < XLR_SUMS_COV; ++k) v[k] = 0.0;
-            for (int k = tid; k < nValid; k += XR_T)
-                if (inl[k]) rgbd_acc_cov(v, cp, cX, (double)S.p[0][k], (double)S.p[1][k], (double)S.p[2][k],
-                                         (double)S.X[0][k], (double)S.X[1][k], (double)S.X[2][k]);
-        }
-        xr_block_reduce(part, XLR_SUMS_COV, a);
-        rgbd_kabsch_fit(cp, cX, a, &pose);
-        if (roundPoses) xr_store12(&pose, roundPoses + 12 * rounds);
-        if (roundMasks) {
-            uint8_t *m = roundMasks + (size_t)rounds * (size_t)N;
-            memset(m, 0, (size_t)N);
-            for (int k = 0; k < nValid; ++k) if (inl[k]) m[S.cell[k]] = 1;
-        }
-        finalInl = cnt;
-        ++rounds;
-    }
-    free(part);
-    free(inl);
+    XrRefine ro;
+    xr_refine(&S, thr, maxDist, &pose, &ro, NULL, roundCounts, roundPoses, roundMasks, N);
 
     /* ---- write (pose2trans): inverse rigid transform, float row-major */
     for (int i = 0; i < 3; ++i) {
@@ -222,8 +96,8 @@ int xr_forward_rgbd(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     }
     pose16[12] = 0.0f; pose16[13] = 0.0f; pose16[14] = 0.0f; pose16[15] = 1.0f;
     if (dbg) {
-        dbg[0] = (double)win; dbg[1] = (double)nValid; dbg[2] = (double)rounds; dbg[3] = (double)finalInl;
-        xr_store12(&pose, dbg + 4);
+        dbg[0] = (double)win; dbg[1] = (double)nValid; dbg[2] = (double)ro.rounds; dbg[3] = (double)ro.finalInl;
+        pose_store12(&pose, dbg + 4);
     }
     xr_free(&S);
     return 0;
@@ -240,7 +114,7 @@ void xr_test_kabsch(int n, const double *p, const double *X, double *out12)
     for (int i = 0; i < n; ++i) rgbd_acc_cov(a, cp, cX, p[3 * i], p[3 * i + 1], p[3 * i + 2], X[3 * i], X[3 * i + 1], X[3 * i + 2]);
     Pose o;
     rgbd_kabsch_fit(cp, cX, a, &o);
-    xr_store12(&o, out12);
+    pose_store12(&o, out12);
 }
 
 void xr_test_cam_from_depth(float d, int y, int x, float f, float ppx, float ppy, int sub, float *out3)

@@ -6,33 +6,22 @@ module-scoped fixture, so nothing is written into the repository tree.  `build_p
 same file with its own main() as an executable, with AddressSanitizer and UBSan."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "crossloc_amd", "csrc")
+from rgbd_ref_common import HERE, INTR_ARGTYPES, SRC_ARGTYPES, _ptr, compile_lib, compile_program, source_args
+
 SRC = os.path.join(HERE, "dsac_rgbd_ref.c")
 DBG = 16
 MAX_REF_STEPS = 100
-CFLAGS = ["-std=c99", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Wno-unused-function", "-I" + CSRC]
-
-
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-
-
-def _el_strides(a):
-    return [s // a.itemsize for s in a.strides]
 
 
 class Ref:
     def __init__(self, path):
         L = ctypes.CDLL(path)
-        i64, ci, cf, vp, u64, u32 = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
+        ci, cf, vp, u64, u32 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32
         L.xr_forward_rgbd.restype = ci
-        L.xr_forward_rgbd.argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, ci, ci, ci, cf, cf, cf, cf, cf, cf, ci,
-                                      u64, u64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.xr_forward_rgbd.argtypes = SRC_ARGTYPES + [ci, cf, cf, cf] + INTR_ARGTYPES + [u64, u64, u32] + [vp] * 9
         L.xr_test_kabsch.restype = None
         L.xr_test_kabsch.argtypes = [ci, vp, vp, vp]
         L.xr_test_cam_from_depth.restype = None
@@ -44,21 +33,8 @@ class Ref:
         """One image: coords float32 [3,Ho,Wo], and cam float32 [3,Ho,Wo] or depth float32 [Ho,Wo] (any strides).  Returns a dict:
         pose [4,4] float32, cells [nHyp,3], tries [nHyp], scores [nHyp], dbg [16], hyp_poses [nHyp,12]; with rounds=True also
         round_counts (the inlier count of every round entered), round_poses [r,12] and round_masks [r,Ho,Wo] of the r fitted rounds."""
-        coords = np.asarray(coords)
-        assert coords.dtype == np.float32 and coords.ndim == 3 and coords.shape[0] == 3
-        _, Ho, Wo = coords.shape
-        sc, sy, sx = _el_strides(coords)
-        cc = cy = cx = dy = dx = 0
-        if cam is not None:
-            cam = np.asarray(cam)
-            assert cam.dtype == np.float32 and cam.shape == coords.shape
-            cc, cy, cx = _el_strides(cam)
-        if depth is not None:
-            depth = np.asarray(depth)
-            assert depth.dtype == np.float32 and depth.shape == (Ho, Wo)
-            dy, dx = _el_strides(depth)
-        ppx = Wo * sub / 2.0 if ppx is None else ppx
-        ppy = Ho * sub / 2.0 if ppy is None else ppy
+        prefix, intr, (coords, cam, depth) = source_args(coords, cam, depth, focal, ppx, ppy, sub)
+        Ho, Wo = coords.shape[1:]
         pose = np.zeros(16, np.float32)
         cells = np.zeros((n_hyp, 3), np.int32)
         tries = np.zeros(n_hyp, np.int32)
@@ -70,8 +46,7 @@ class Ref:
             rcnt = np.zeros(MAX_REF_STEPS, np.int32)
             rpose = np.zeros((MAX_REF_STEPS, 12), np.float64)
             rmask = np.zeros((MAX_REF_STEPS, Ho, Wo), np.uint8)
-        rc = self.L.xr_forward_rgbd(_ptr(coords), sc, sy, sx, _ptr(cam), cc, cy, cx, _ptr(depth), dy, dx, Ho, Wo, int(n_hyp),
-                                    float(thr), float(alpha), float(max_dist), float(focal), float(ppx), float(ppy), int(sub),
+        rc = self.L.xr_forward_rgbd(*prefix, int(n_hyp), float(thr), float(alpha), float(max_dist), *intr,
                                     int(seed), int(image), int(max_tries), _ptr(pose), _ptr(cells), _ptr(tries), _ptr(scores),
                                     _ptr(dbg), _ptr(hyp), _ptr(rcnt), _ptr(rpose), _ptr(rmask))
         if rc != 0:
@@ -98,16 +73,9 @@ class Ref:
 
 
 def load(tmpdir):
-    out = os.path.join(str(tmpdir), "libdsac_rgbd_ref.so")
-    subprocess.check_call(["gcc", "-O2", "-fPIC"] + CFLAGS + ["-shared", "-o", out, SRC, "-lm"])
-    return Ref(out)
+    return Ref(compile_lib(tmpdir, SRC, "dsac_rgbd_ref"))
 
 
 def build_program(tmpdir, sanitize=True):
     """The restatement with its own main() as an executable; with `sanitize` under AddressSanitizer and UBSan."""
-    out = os.path.join(str(tmpdir), "dsac_rgbd_ref_san" if sanitize else "dsac_rgbd_ref_prog")
-    # the sanitizer runtimes are linked statically: the program then runs in whatever environment it inherits
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g",
-           "-static-libasan", "-static-libubsan"] if sanitize else []
-    subprocess.check_call(["gcc", "-O1", "-DXR_MAIN"] + san + CFLAGS + ["-o", out, SRC, "-lm"])
-    return out
+    return compile_program(tmpdir, SRC, "dsac_rgbd_ref", "XR_MAIN", sanitize)

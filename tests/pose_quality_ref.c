@@ -3,9 +3,8 @@
  *
  * TEST INFRASTRUCTURE ONLY.  The per-cell and per-image arithmetic is the product's xl_dsac_quality_math.h, compiled here
  * by gcc as C99 with -ffp-contract=off.  This file restates serially what the kernel does in parallel around it: the
- * walk of 256 virtual threads over the cells (thread t: cells t, t + 256, ... in ascending order), the xor butterfly of
- * each 64-lane wave and the waves added in order 0, 1, 2, 3 - the way oracle/dsac_oracle.c restates the solver's block
- * reductions (xo_reduce28).  Bitwise GPU == this file therefore checks the kernel's orchestration and that gcc and hipcc
+ * walk of 256 virtual threads over the cells (thread t: cells t, t + 256, ... in ascending order) and the canonical block
+ * sum (block_sum of xl_dsac_reduce.h, which states the order; oracle/dsac_oracle.c uses it too).  Bitwise GPU == this file therefore checks the kernel's orchestration and that gcc and hipcc
  * agree on the same IEEE operations; the formulas themselves are checked by tests/test_pose_quality_cpu.py (numeric
  * Jacobians, Monte-Carlo calibration, the oracle's score and per-cell error).
  */
@@ -15,18 +14,9 @@
 #include <string.h>
 
 #include "xl_dsac_quality_math.h"     /* crossloc_amd/csrc: shared with the kernel */
+#include "xl_dsac_reduce.h"           /* the canonical block sum and its order */
 
-#define XQ_T 256                      /* threads of the kernel's workgroup: 4 waves of 64 */
-
-static double xq_butterfly64(double p[64])
-{
-    double q[64];
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ off];
-        memcpy(p, q, sizeof(q));
-    }
-    return p[0];
-}
+#define XQ_T XL_BLOCK_THREADS         /* threads of the kernel's workgroup: 4 waves of 64 */
 
 static Cam xq_cam(int Ho, int Wo, float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub)
 {
@@ -53,16 +43,7 @@ static void xq_sums(const float *coords, int64_t sc, int64_t sy, int64_t sx, con
             quality_cell(pose, (double)q[0], (double)q[sc], (double)q[2 * sc], y, x, cam, beta, a);
         }
     }
-    for (int k = 0; k < XLQ_SUMS; ++k) {
-        double tot = 0.0;
-        for (int w = 0; w < XQ_T / 64; ++w) {
-            double p[64];
-            for (int l = 0; l < 64; ++l) p[l] = part[w * 64 + l][k];
-            const double ws = xq_butterfly64(p);
-            tot = (w == 0) ? ws : tot + ws;
-        }
-        s[k] = tot;
-    }
+    block_sum(&part[0][0], XLQ_SUMS, s);
     free(part);
 }
 
@@ -96,8 +77,7 @@ int xq_pose_quality_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     if (!coords || !Rt12 || !row || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
     const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     Pose pose;
-    for (int i = 0; i < 9; ++i) pose.R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) pose.t[i] = Rt12[9 + i];
+    pose_load12(Rt12, &pose);
     const bool poseOk = quality_pose_finite(&pose);
     if (!poseOk) pose_identity(&pose);
     xq_row(coords, sc, sy, sx, &cam, &pose, poseOk, row);
@@ -111,8 +91,7 @@ int xq_test_sums_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx, in
     if (!coords || !Rt12 || !sums32 || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
     const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     Pose pose;
-    for (int i = 0; i < 9; ++i) pose.R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) pose.t[i] = Rt12[9 + i];
+    pose_load12(Rt12, &pose);
     xq_sums(coords, sc, sy, sx, &cam, &pose, true, sums32);
     return 0;
 }
@@ -124,19 +103,16 @@ void xq_test_pose_from16(const float *pose16, double *Rt12)
 {
     Pose p;
     quality_pose_from16(pose16, &p);
-    for (int i = 0; i < 9; ++i) Rt12[i] = p.R[i];
-    for (int i = 0; i < 3; ++i) Rt12[9 + i] = p.t[i];
+    pose_store12(&p, Rt12);
 }
 
 /* apply_step: out = prev (-) d, i.e. R = Exp(-d_w) R_prev, t = t_prev - d_t */
 void xq_test_apply_step(const double *Rt12, const double *d6, double *out12)
 {
     Pose prev, out;
-    for (int i = 0; i < 9; ++i) prev.R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) prev.t[i] = Rt12[9 + i];
+    pose_load12(Rt12, &prev);
     apply_step(&prev, d6, &out);
-    for (int i = 0; i < 9; ++i) out12[i] = out.R[i];
-    for (int i = 0; i < 3; ++i) out12[9 + i] = out.t[i];
+    pose_store12(&out, out12);
 }
 
 int xq_test_inv6(const double *ut21, double *inv36) { return quality_inv6(ut21, inv36) ? 1 : 0; }

@@ -3,73 +3,22 @@
  *
  * TEST INFRASTRUCTURE ONLY.  The per-cell and per-image arithmetic is the product's xl_dsac_rgbd_quality_math.h, compiled
  * here by gcc as C99 with -ffp-contract=off.  This file restates serially what the kernel does in parallel around it: the
- * two walks of 256 virtual threads over the cells (thread t: cells t, t + 256, ... in ascending order), the xor butterfly
- * of each 64-lane wave and the waves added in order 0, 1, 2, 3, the centroid formed between the walks.  Bitwise GPU == this
+ * two walks of 256 virtual threads over the cells (thread t: cells t, t + 256, ... in ascending order), the canonical
+ * block sum (xl_dsac_reduce.h states its order), the centroid formed between the walks.  Bitwise GPU == this
  * file therefore checks the kernel's orchestration and that gcc and hipcc agree on the same IEEE operations; the formulas
  * themselves are checked by tests/test_rgbd_quality_cpu.py (an uncentred numpy restatement, numeric Jacobians, Monte-Carlo
  * calibration, the solver restatement's scores).
  *
  * With -DXRQ_MAIN the file is a program of its own (for the sanitizer run): see main() at the end.
  */
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
+#include "rgbd_ref_common.h"             /* the input record and the per-cell load; the block sum of xl_dsac_reduce.h */
 #include "xl_dsac_rgbd_quality_math.h"   /* crossloc_amd/csrc: shared with the kernel */
 
-#define XRQ_T 256                     /* threads of the kernel's workgroup: 4 waves of 64 */
+#define XRQ_T XR_T
 #define XRQ_SUMS (XLQR_SUMS1 + XLQR_SUMS2 + 4)   /* what xrq_test_sums exports: both walks, the centroid, the pivot ratio */
 
-static double xrq_butterfly64(double p[64])
-{
-    double q[64];
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int l = 0; l < 64; ++l) q[l] = p[l] + p[l ^ off];
-        memcpy(p, q, sizeof(q));
-    }
-    return p[0];
-}
-
-/* canonical block sum of K values per virtual thread: butterfly per wave, waves added in order */
-static void xrq_block_sum(const double *part /* [XRQ_T][K] */, int K, double *out)
-{
-    for (int k = 0; k < K; ++k) {
-        double tot = 0.0;
-        for (int w = 0; w < XRQ_T / 64; ++w) {
-            double p[64];
-            for (int l = 0; l < 64; ++l) p[l] = part[(w * 64 + l) * K + k];
-            const double ws = xrq_butterfly64(p);
-            tot = (w == 0) ? ws : tot + ws;
-        }
-        out[k] = tot;
-    }
-}
-
-/* where an image comes from: exactly one of cam and depth is non-null */
-typedef struct {
-    const float *coords; int64_t sc, sy, sx;
-    const float *cam; int64_t cc, cy, cx;
-    const float *depth; int64_t dy, dx;
-    float focal, ppx, ppy; int sub;
-} XrqIn;
-
-static void xrq_load(const XrqIn *in, int y, int x, double *X, float *p)
-{
-    const float *q = in->coords + (int64_t)y * in->sy + (int64_t)x * in->sx;
-    X[0] = (double)q[0]; X[1] = (double)q[in->sc]; X[2] = (double)q[2 * in->sc];
-    if (in->cam) {
-        const float *m = in->cam + (int64_t)y * in->cy + (int64_t)x * in->cx;
-        p[0] = m[0]; p[1] = m[in->cc]; p[2] = m[2 * in->cc];
-    } else {
-        rgbd_cam_from_depth(in->depth[(int64_t)y * in->dy + (int64_t)x * in->dx], y, x, in->focal, in->ppx, in->ppy, in->sub,
-                            p, p + 1, p + 2);
-    }
-}
-
 /* the kernel from its pose on: walk 1, reduction, centroid, walk 2, reduction, final step */
-static void xrq_run(const XrqIn *in, const RgbdQ *q, const Pose *pose, bool poseOk, double *row, double *sums)
+static void xrq_run(const RgbdSrc *in, const RgbdQ *q, const Pose *pose, bool poseOk, double *row, double *sums)
 {
     double *part = (double *)malloc(sizeof(double) * XRQ_T * XLQR_SUMS2);
     const float beta = 5.0f / q->thr;
@@ -80,13 +29,12 @@ static void xrq_run(const XrqIn *in, const RgbdQ *q, const Pose *pose, bool pose
         if (!poseOk) continue;
         for (int i = tid; i < q->N; i += XRQ_T) {
             const int y = i / q->Wo, x = i - y * q->Wo;
-            double X[3];
-            float p[3];
-            xrq_load(in, y, x, X, p);
-            rgbdq_cell1(pose, X[0], X[1], X[2], p[0], p[1], p[2], q, beta, a);
+            float X[3], p[3];
+            xr_load(in, y, x, X, p);
+            rgbdq_cell1(pose, (double)X[0], (double)X[1], (double)X[2], p[0], p[1], p[2], q, beta, a);
         }
     }
-    xrq_block_sum(part, XLQR_SUMS1, s1);
+    block_sum(part, XLQR_SUMS1, s1);
     rgbdq_centroid(s1, c);
     for (int tid = 0; tid < XRQ_T; ++tid) {
         double *a = part + tid * XLQR_SUMS2;
@@ -94,13 +42,12 @@ static void xrq_run(const XrqIn *in, const RgbdQ *q, const Pose *pose, bool pose
         if (!poseOk) continue;
         for (int i = tid; i < q->N; i += XRQ_T) {
             const int y = i / q->Wo, x = i - y * q->Wo;
-            double X[3];
-            float p[3];
-            xrq_load(in, y, x, X, p);
-            rgbdq_cell2(pose, X[0], X[1], X[2], p[0], p[1], p[2], q, c, a);
+            float X[3], p[3];
+            xr_load(in, y, x, X, p);
+            rgbdq_cell2(pose, (double)X[0], (double)X[1], (double)X[2], p[0], p[1], p[2], q, c, a);
         }
     }
-    xrq_block_sum(part, XLQR_SUMS2, s2);
+    block_sum(part, XLQR_SUMS2, s2);
     free(part);
     double tmp[XLQ_ROW];
     rgbdq_row(s1, s2, c, pose, q, poseOk, row ? row : tmp, &ratio);
@@ -112,15 +59,12 @@ static void xrq_run(const XrqIn *in, const RgbdQ *q, const Pose *pose, bool pose
     }
 }
 
-static int xrq_args(XrqIn *in, RgbdQ *q, const float *coords, int64_t sc, int64_t sy, int64_t sx,
+static int xrq_args(RgbdSrc *in, RgbdQ *q, const float *coords, int64_t sc, int64_t sy, int64_t sx,
                     const float *cam, int64_t cc, int64_t cy, int64_t cx, const float *depth, int64_t dy, int64_t dx,
                     int Ho, int Wo, float thr, float alpha, float maxDist, float focal, float ppx, float ppy, int sub)
 {
     if (!coords || (cam == NULL) == (depth == NULL) || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
-    in->coords = coords; in->sc = sc; in->sy = sy; in->sx = sx;
-    in->cam = cam; in->cc = cc; in->cy = cy; in->cx = cx;
-    in->depth = depth; in->dy = dy; in->dx = dx;
-    in->focal = focal; in->ppx = ppx; in->ppy = ppy; in->sub = sub;
+    *in = xr_src(coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, focal, ppx, ppy, sub);
     q->thr = thr; q->alpha = alpha; q->maxDist = maxDist; q->Ho = Ho; q->Wo = Wo; q->N = Ho * Wo;
     return 0;
 }
@@ -131,7 +75,7 @@ int xrq_pose_quality(const float *coords, int64_t sc, int64_t sy, int64_t sx,
                      int Ho, int Wo, const float *pose16, float thr, float alpha, float maxDist,
                      float focal, float ppx, float ppy, int sub, double *row)
 {
-    XrqIn in;
+    RgbdSrc in;
     RgbdQ q;
     if (!pose16 || !row) return -1;
     if (xrq_args(&in, &q, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, thr, alpha, maxDist, focal, ppx, ppy, sub)) return -1;
@@ -145,8 +89,7 @@ int xrq_pose_quality(const float *coords, int64_t sc, int64_t sy, int64_t sx,
 
 static bool xrq_pose12(const double *Rt12, Pose *pose)
 {
-    for (int i = 0; i < 9; ++i) pose->R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) pose->t[i] = Rt12[9 + i];
+    pose_load12(Rt12, pose);
     const bool ok = quality_pose_finite(pose);
     if (!ok) pose_identity(pose);
     return ok;
@@ -158,7 +101,7 @@ int xrq_pose_quality_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx
                          int Ho, int Wo, const double *Rt12, float thr, float alpha, float maxDist,
                          float focal, float ppx, float ppy, int sub, double *row)
 {
-    XrqIn in;
+    RgbdSrc in;
     RgbdQ q;
     if (!Rt12 || !row) return -1;
     if (xrq_args(&in, &q, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, thr, alpha, maxDist, focal, ppx, ppy, sub)) return -1;
@@ -176,7 +119,7 @@ int xrq_test_sums_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx,
                       int Ho, int Wo, const double *Rt12, float thr, float alpha, float maxDist,
                       float focal, float ppx, float ppy, int sub, double *sums)
 {
-    XrqIn in;
+    RgbdSrc in;
     RgbdQ q;
     if (!Rt12 || !sums) return -1;
     if (xrq_args(&in, &q, coords, sc, sy, sx, cam, cc, cy, cx, depth, dy, dx, Ho, Wo, thr, alpha, maxDist, focal, ppx, ppy, sub)) return -1;
@@ -193,19 +136,16 @@ void xrq_test_pose_from16(const float *pose16, double *Rt12)
 {
     Pose p;
     quality_pose_from16(pose16, &p);
-    for (int i = 0; i < 9; ++i) Rt12[i] = p.R[i];
-    for (int i = 0; i < 3; ++i) Rt12[9 + i] = p.t[i];
+    pose_store12(&p, Rt12);
 }
 
 /* apply_step: out = prev (-) d, i.e. R = Exp(-d_w) R_prev, t = t_prev - d_t */
 void xrq_test_apply_step(const double *Rt12, const double *d6, double *out12)
 {
     Pose prev, out;
-    for (int i = 0; i < 9; ++i) prev.R[i] = Rt12[i];
-    for (int i = 0; i < 3; ++i) prev.t[i] = Rt12[9 + i];
+    pose_load12(Rt12, &prev);
     apply_step(&prev, d6, &out);
-    for (int i = 0; i < 9; ++i) out12[i] = out.R[i];
-    for (int i = 0; i < 3; ++i) out12[9 + i] = out.t[i];
+    pose_store12(&out, out12);
 }
 
 int xrq_test_inv3(const double *ut6, double *inv9, double *minRatio) { return rgbdq_inv3(ut6, inv9, minRatio) ? 1 : 0; }

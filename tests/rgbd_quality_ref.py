@@ -6,24 +6,14 @@ module-scoped fixture, so nothing is written into the repository tree.  `build_p
 same file with its own main() as an executable, with AddressSanitizer and UBSan linked statically."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "crossloc_amd", "csrc")
+from rgbd_ref_common import HERE, INTR_ARGTYPES, SRC_ARGTYPES, _ptr, compile_lib, compile_program, source_args
+
 SRC = os.path.join(HERE, "rgbd_quality_ref.c")
 ROW = 64
 SUMS = 25
-CFLAGS = ["-std=c99", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Wno-unused-function", "-I" + CSRC]
-
-
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-
-
-def _el_strides(a):
-    return [s // a.itemsize for s in a.strides]
 
 
 def rt12(R, t):
@@ -33,10 +23,10 @@ def rt12(R, t):
 class Ref:
     def __init__(self, path):
         L = ctypes.CDLL(path)
-        i64, ci, cf, vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+        ci, cf, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
         for name in ("xrq_pose_quality", "xrq_pose_quality_w2c", "xrq_test_sums_w2c"):
             getattr(L, name).restype = ci
-            getattr(L, name).argtypes = [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, ci, ci, vp, cf, cf, cf, cf, cf, cf, ci, vp]
+            getattr(L, name).argtypes = SRC_ARGTYPES + [vp, cf, cf, cf] + INTR_ARGTYPES + [vp]
         L.xrq_test_pose_from16.restype = None
         L.xrq_test_pose_from16.argtypes = [vp, vp]
         L.xrq_test_apply_step.restype = None
@@ -46,24 +36,9 @@ class Ref:
         self.L = L
 
     def _call(self, fn, coords, pose, thr, alpha, max_dist, cam, depth, focal, ppx, ppy, sub, width):
-        coords = np.asarray(coords)
-        assert coords.dtype == np.float32 and coords.ndim == 3 and coords.shape[0] == 3
-        _, Ho, Wo = coords.shape
-        sc, sy, sx = _el_strides(coords)
-        cc = cy = cx = dy = dx = 0
-        if cam is not None:
-            cam = np.asarray(cam)
-            assert cam.dtype == np.float32 and cam.shape == coords.shape
-            cc, cy, cx = _el_strides(cam)
-        if depth is not None:
-            depth = np.asarray(depth)
-            assert depth.dtype == np.float32 and depth.shape == (Ho, Wo)
-            dy, dx = _el_strides(depth)
-        ppx = Wo * sub / 2.0 if ppx is None else ppx
-        ppy = Ho * sub / 2.0 if ppy is None else ppy
+        prefix, intr, _keep = source_args(coords, cam, depth, focal, ppx, ppy, sub)
         out = np.zeros(width, np.float64)
-        rc = fn(_ptr(coords), sc, sy, sx, _ptr(cam), cc, cy, cx, _ptr(depth), dy, dx, Ho, Wo, _ptr(pose), float(thr), float(alpha),
-                float(max_dist), float(focal), float(ppx), float(ppy), int(sub), _ptr(out))
+        rc = fn(*prefix, _ptr(pose), float(thr), float(alpha), float(max_dist), *intr, _ptr(out))
         if rc != 0:
             raise RuntimeError("rgbd_quality_ref failed: %d" % rc)
         return out
@@ -109,19 +84,12 @@ class Ref:
 
 
 def load(tmpdir):
-    out = os.path.join(str(tmpdir), "librgbd_quality_ref.so")
-    subprocess.check_call(["gcc", "-O2", "-fPIC"] + CFLAGS + ["-shared", "-o", out, SRC, "-lm"])
-    return Ref(out)
+    return Ref(compile_lib(tmpdir, SRC, "rgbd_quality_ref"))
 
 
 def build_program(tmpdir, sanitize=True):
     """The restatement with its own main() as an executable; with `sanitize` under AddressSanitizer and UBSan."""
-    out = os.path.join(str(tmpdir), "rgbd_quality_ref_san" if sanitize else "rgbd_quality_ref_prog")
-    # the sanitizer runtimes are linked statically: the program then runs in whatever environment it inherits
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g",
-           "-static-libasan", "-static-libubsan"] if sanitize else []
-    subprocess.check_call(["gcc", "-O1", "-DXRQ_MAIN"] + san + CFLAGS + ["-o", out, SRC, "-lm"])
-    return out
+    return compile_program(tmpdir, SRC, "rgbd_quality_ref", "XRQ_MAIN", sanitize)
 
 
 def sym(ut, n):

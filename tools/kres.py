@@ -19,9 +19,9 @@ for line in p.stderr.splitlines():
     if m and cur is not None:
         cur[m.group(1).split(" [")[0]] = int(m.group(2))
         if m.group(1).startswith("LDS"):
-            print("%-72s sgpr %3d vgpr %3d agpr %3d scratch %4d occ %d spill v%d lds %d" % (
+            print("%-72s sgpr %3d vgpr %3d agpr %3d scratch %4d occ %d spill v%d s%d lds %d" % (
                 cur["name"], cur.get("TotalSGPRs", -1), cur.get("VGPRs", -1), cur.get("AGPRs", -1), cur.get("ScratchSize", -1),
-                cur.get("Occupancy", -1), cur.get("VGPRs Spill", -1), cur.get("LDS Size", -1)))
+                cur.get("Occupancy", -1), cur.get("VGPRs Spill", -1), cur.get("SGPRs Spill", -1), cur.get("LDS Size", -1)))
             cur = None
 if p.returncode != 0:
     sys.stderr.write(p.stderr[-3000:])
