@@ -11,12 +11,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INC = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libcrossloc_hip.so")
-SOURCES = ["xl_dsac.hip", "xl_dsac_quality.hip", "xl_dsac_rgbd.hip", "xl_dsac_rgbd_bwd.hip", "xl_dsac_rgbd_quality.hip", "xl_cnn.hip", "xl_cnn_bwd.hip", "xl_gemm_split.hip", "xl_gemm_pair.hip", "xl_stem_split.hip", "xl_stem_pair.hip", "xl_stem_fused.hip", "xl_stem_dgrad.hip", "xl_wgrad_split.hip", "xl_wgrad_pair.hip", "xl_pack.hip", "xl_loss.hip", "xl_optim.hip", "xl_data.hip", "xl_metrics.hip"]
+SOURCES = ["xl_dsac.hip", "xl_dsac_quality.hip", "xl_dsac_rgbd.hip", "xl_dsac_rgbd_bwd.hip", "xl_dsac_rgbd_quality.hip", "xl_cnn.hip", "xl_conv1.hip", "xl_igemm.hip", "xl_wino.hip", "xl_gn.hip", "xl_cnn_bwd.hip", "xl_gemm_split.hip", "xl_gemm_pair.hip", "xl_stem_split.hip", "xl_stem_pair.hip", "xl_stem_fused.hip", "xl_stem_dgrad.hip", "xl_wgrad_split.hip", "xl_wgrad_pair.hip", "xl_pack.hip", "xl_loss.hip", "xl_optim.hip", "xl_data.hip", "xl_metrics.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-result"]
 
 
 def sources():
-    return [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    paths = [os.path.join(CSRC, s) for s in SOURCES]
+    missing = [p for p in paths if not os.path.exists(p)]
+    if missing:                                                  # a library without one of its translation units links, and fails later
+        raise FileNotFoundError("crossloc_amd/build.py lists sources that do not exist: " + ", ".join(missing))
+    return paths
 
 
 STAMP = LIB + ".srchash"

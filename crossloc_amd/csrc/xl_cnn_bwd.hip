@@ -1,7 +1,7 @@
 // xl_cnn_bwd.hip — backward kernels of the scene-coordinate CNN (what autograd + cuDNN dgrad/wgrad + native
 // GroupNorm backward did for `loss.backward()`, /root/reference/train_single_task.py:298).
 //
-//   data gradient      the forward implicit-GEMM kernel in MODE 1 (xl_cnn.hip): same MFMA core, mirrored tap offsets,
+//   data gradient      the forward implicit-GEMM kernel in MODE 1 (xl_igemm.hip): same MFMA core, mirrored tap offsets,
 //                      transposed weight operand, optional accumulate epilogue for gradients with two producers
 //   wgrad_kernel       dW[o][tap][c] = sum_m dY[m][o] * X[m @ tap][c]: implicit GEMM with the PIXEL dimension as K,
 //                      split-K over pixel ranges, fp32 MFMA 32x32x2 with operands read transposed from LDS
@@ -15,13 +15,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
-
-int xl_run_wgrad_split(const xl_op &op, hipStream_t st);   // xl_wgrad_split.hip
-int xl_run_wgrad_pair(const xl_op &op, hipStream_t st);    // xl_wgrad_pair.hip
 
 namespace {
 
@@ -296,9 +291,8 @@ int launch_wgrad(const xl_op &op, hipStream_t st)
     const int taps = op.ksize * op.ksize;
     hipLaunchKernelGGL((wgrad_kernel<BO, BC, WO, WC>), dim3(a.zCount * taps * a.nbo * a.nbc * a.splits), dim3(64 * WO * WC), 0, st, a);
     const long long total = (long long)taps * op.Cout * op.Cin;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, a.zCount), dim3(256), 0, st, (const float *)op.stats2,
+    const unsigned blocks = xl_grid(total, 256, 2048);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, a.zCount), dim3(256), 0, st, (const float *)op.stats2,
                        (float *)op.out, a.splits, taps, op.Cout, op.Cin);
     return XL_OK;
 }
@@ -878,7 +872,7 @@ void head_bwd_kernel(const float *__restrict__ x, const float *__restrict__ w, c
 }
 
 // Backward of the full-size (semantics) head for the pure pixel-shuffle case (H = 8 Hs, W = 8 Ws; duc_head_kernel in
-// xl_cnn.hip): one output pixel per thread.  dz = dout (x fout inside the clamp for exp channels); the gradient of the
+// xl_gn.hip): one output pixel per thread.  dz = dout (x fout inside the clamp for exp channels); the gradient of the
 // DUC activation goes back through the shuffle index map (every input element has exactly one output pixel: plain
 // stores, no atomics); d fc3.weight / d fc3.bias are accumulated per thread, reduced per block in a fixed order and
 // written as one partial vector [C*C + C] per block.
@@ -1251,9 +1245,8 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
                 const int rc = (op.flags & XL_CONV_PAIR_F16) ? xl_run_wgrad_pair(op, st) : xl_run_wgrad_split(op, st);
                 if (rc != XL_OK) return rc;
                 const long long total = (long long)op.Cout * op.Cin;
-                long long blocks = (total + 255) / 256;
-                if (blocks > 2048) blocks = 2048;
-                hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks, op.groups > 1 ? op.groups : 1), dim3(256), 0, st,
+                const unsigned blocks = xl_grid(total, 256, 2048);
+                hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks, op.groups > 1 ? op.groups : 1), dim3(256), 0, st,
                                    (const float *)op.stats2, (float *)op.out, op.nchunks2, 1, op.Cout, op.Cin);
                 return XL_OK;
             }
@@ -1323,7 +1316,7 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
             const int waves = (int)blocks * 4;
             float *pW = (float *)op.stats2;
             float *pB = pW + (long long)waves * op.Cout * op.Cin;
-            hipLaunchKernelGGL((head_bwd_kernel<4, 4>), dim3((unsigned)blocks), dim3(256), 0, st, (const float *)op.in,
+            hipLaunchKernelGGL((head_bwd_kernel<4, 4>), dim3(blocks), dim3(256), 0, st, (const float *)op.in,
                                (const float *)op.w, (const float *)op.aux, (const float *)op.aux2, (float *)op.out, pW, pB,
                                op.B, op.Hi * op.Wi, op.Cin, op.ld_in, op.ld_out, op.Cout, op.n_task, op.clamp_lo, op.clamp_hi);
             hipLaunchKernelGGL(partial_sum_kernel, dim3((op.Cout * op.Cin + 31) / 32), dim3(256), 0, st, (const float *)pW,
@@ -1337,21 +1330,19 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
             const int m = op.ksize == 6 ? 6 : 4;
             if (op.Cin % 2 != 0 || op.ld_in % 2 != 0 || op.Ho != (op.Hi + m - 1) / m || op.Wo != (op.Wi + m - 1) / m) return XL_ERR_ARG;
             const long long items = (long long)op.B * op.Ho * op.Wo * (op.Cin / 2);
-            long long blocks = (items + 255) / 256;
-            if (blocks > 262144) blocks = 262144;
+            const unsigned blocks = xl_grid(items, 256, 262144);
             if (m == 6)
-                hipLaunchKernelGGL(wino6_dy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)op.in, (float *)op.out,
+                hipLaunchKernelGGL(wino6_dy_kernel, dim3(blocks), dim3(256), 0, st, (const float *)op.in, (float *)op.out,
                                    op.B, op.Hi, op.Wi, op.Cin, op.ld_in, op.Ho, op.Wo, (unsigned *)op.scale);   // scale: max |dM| slot (optional)
             else
-                hipLaunchKernelGGL(wino4_dy_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)op.in, (float *)op.out,
+                hipLaunchKernelGGL(wino4_dy_kernel, dim3(blocks), dim3(256), 0, st, (const float *)op.in, (float *)op.out,
                                    op.B, op.Hi, op.Wi, op.Cin, op.ld_in, op.Ho, op.Wo);
             return XL_OK;
         }
         case XL_OP_WINO_WFINAL: {
             const long long total = (long long)op.Cout * op.Cin;
-            long long blocks = (total + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(op.ksize == 6 ? wino6_wfinal_kernel : wino4_wfinal_kernel, dim3((unsigned)blocks), dim3(256), 0, st,
+            const unsigned blocks = xl_grid(total, 256, 4096);
+            hipLaunchKernelGGL(op.ksize == 6 ? wino6_wfinal_kernel : wino4_wfinal_kernel, dim3(blocks), dim3(256), 0, st,
                                (const float *)op.in, (float *)op.out, op.Cout, op.Cin);
             return XL_OK;
         }
@@ -1361,23 +1352,21 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
             if (op.Cout < 1 || op.Cout > 8 || op.Cin != op.Cout * 64) return XL_ERR_ARG;
             const bool trim = (op.Ho != 8 * op.Hi || op.Wo != 8 * op.Wi);        // networks.py:344-349 bilinear trim
             const long long pix = (long long)op.B * op.Ho * op.Wo;
-            long long blocks = (pix + 255) / 256;
-            if (blocks > 1024) blocks = 1024;
+            const unsigned blocks = xl_grid(pix, 256, 1024);
             const int len = op.Cout * op.Cout + op.Cout;
             float *part = (float *)op.stats2;
             float *tot = part + blocks * len;                           // [len]: weights then bias
             float *dv = tot + len;                                      // trim: [B][Cout][Ho][Wo] behind the partials
             if (trim) {
-                hipLaunchKernelGGL((duc_head_bwd_kernel<8, 1>), dim3((unsigned)blocks), dim3(256), 0, st, (const float *)op.in,
+                hipLaunchKernelGGL((duc_head_bwd_kernel<8, 1>), dim3(blocks), dim3(256), 0, st, (const float *)op.in,
                                    (const float *)op.w, (const float *)op.aux, (const float *)op.aux2, (float *)op.out, part,
                                    op.B, op.Hi, op.Wi, op.Cout, op.ld_in, op.ld_out, op.n_task, op.clamp_lo, op.clamp_hi,
                                    op.Ho, op.Wo, dv);
-                long long ub = ((long long)op.B * 64 * op.Hi * op.Wi + 255) / 256;
-                if (ub > 65536) ub = 65536;
-                hipLaunchKernelGGL(duc_trim_bwd_kernel<8>, dim3((unsigned)ub), dim3(256), 0, st, (const float *)dv, (float *)op.out,
+                const unsigned ub = xl_grid((long long)op.B * 64 * op.Hi * op.Wi, 256, 65536);
+                hipLaunchKernelGGL(duc_trim_bwd_kernel<8>, dim3(ub), dim3(256), 0, st, (const float *)dv, (float *)op.out,
                                    op.B, op.Hi, op.Wi, op.Cout, op.ld_out, op.Ho, op.Wo);
             } else
-                hipLaunchKernelGGL((duc_head_bwd_kernel<8, 0>), dim3((unsigned)blocks), dim3(256), 0, st, (const float *)op.in,
+                hipLaunchKernelGGL((duc_head_bwd_kernel<8, 0>), dim3(blocks), dim3(256), 0, st, (const float *)op.in,
                                    (const float *)op.w, (const float *)op.aux, (const float *)op.aux2, (float *)op.out, part,
                                    op.B, op.Hi, op.Wi, op.Cout, op.ld_in, op.ld_out, op.n_task, op.clamp_lo, op.clamp_hi,
                                    op.Ho, op.Wo, (float *)nullptr);
@@ -1400,15 +1389,9 @@ int xl_run_bwd_op(const xl_op &op, hipStream_t st)
             if (lds > 160 * 1024) return XL_ERR_UNSUPPORTED;
             if (lds > 64 * 1024) {
                 static XlLdsLimit configured[2];     // per instantiation, tracked per device
-                const int fi = op.aux2 ? 1 : 0;
-                int cfgDev;
-                if (configured[fi].needs(lds, &cfgDev)) {
-                    const void *fn = op.aux2 ? reinterpret_cast<const void *>(conv1_wgrad_kernel<true>)
-                                             : reinterpret_cast<const void *>(conv1_wgrad_kernel<false>);
-                    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                        return XL_ERR_HIP;
-                    configured[fi].done(lds, cfgDev);
-                }
+                const void *fn = op.aux2 ? reinterpret_cast<const void *>(conv1_wgrad_kernel<true>)
+                                         : reinterpret_cast<const void *>(conv1_wgrad_kernel<false>);
+                if (configured[op.aux2 ? 1 : 0].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
             }
             if (op.aux2) {
                 // GroupNorm-backward apply on load: aux2 = conv1's raw output (ld_in), w = the layer's forward table (XL_OP_GN_FINAL

@@ -4,6 +4,8 @@
 #include <atomic>
 #include <stddef.h>
 
+#include "../../include/crossloc_dsac.h"   // status codes
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute of a kernel and a plan may be lowered for
 // any device of the node (one process driving several GPUs), from any thread: remember the largest size configured
 // per (call site, device) in atomics.  Racing threads may both set the attribute - it is idempotent and cheap.
@@ -22,6 +24,16 @@ struct XlLdsLimit {
         if (device < 0) return;
         size_t cur = bytes[device].load(std::memory_order_relaxed);
         while (cur < lds && !bytes[device].compare_exchange_weak(cur, lds, std::memory_order_release)) {}
+    }
+    // the whole sequence for one kernel: XL_OK, or XL_ERR_HIP with the runtime's answer in *why
+    int configure(const void *kernel, size_t lds, hipError_t *why = nullptr) {
+        int device;
+        if (!needs(lds, &device)) return XL_OK;
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (why) *why = e;
+        if (e != hipSuccess) return XL_ERR_HIP;
+        done(lds, device);
+        return XL_OK;
     }
 };
 

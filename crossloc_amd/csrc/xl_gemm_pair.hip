@@ -38,9 +38,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -864,12 +862,8 @@ static int xl_run_pair_gemm(const xl_op &op, hipStream_t st)
         kernel = dbg == 1 ? pair_gemm_kernel<512, 1> : dbg == 2 ? pair_gemm_kernel<512, 2> : dbg == 3 ? pair_gemm_kernel<512, 3> : dbg == 4 ? pair_gemm_kernel<512, 4>
                : dbg == 7 ? pair_gemm_kernel<512, 7> : dbg == 8 ? pair_gemm_kernel<512, 8> : dbg == 15 ? pair_gemm_kernel<512, 15> : pair_gemm_kernel<512, 5>;
     static XlLdsLimit configured[4];
-    int cfgDev;
     const int slot = pp ? 3 : dbg ? 2 : op.Cin == 512 ? 1 : 0;
-    if (configured[slot].needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[slot].done(lds, cfgDev);
-    }
+    if (configured[slot].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
     const int nwg = a.nbm * a.nbn * Z;
     int grid = pp ? 512 : 256;
     if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
@@ -916,12 +910,8 @@ static int launch_pair_conv1x1(const xl_op &op, PairConvArgs a, bool norm, int Z
                    : Z > 1 ? reinterpret_cast<const void *>(pair_conv1x1_kernel<false, false, NW, 1, BN>)
                            : reinterpret_cast<const void *>(pair_conv1x1_kernel<false, false, NW, 0, BN>);
     static XlLdsLimit configured[6];
-    int cfgDev;
     const int slot = accumulate ? 2 : (resid ? 5 : (norm ? 1 : (dominant ? 4 : (Z > 1 ? 3 : 0))));
-    if (configured[slot].needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[slot].done(lds, cfgDev);
-    }
+    if (configured[slot].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
     const int nwg = tileCount < 0 ? a.nbm * a.nbn * Z : tileCount;
     a.tile0 = tileFrom; a.ntiles = nwg;
     int grid = 256;                                   // persistent: one workgroup per CU

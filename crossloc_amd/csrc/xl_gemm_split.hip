@@ -21,9 +21,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -598,7 +596,7 @@ void split_gemm_persist4_kernel(SplitArgs2 a)
 //
 // out[m][n] = bias[n] + sum_c f(in[m][c]) * W[n][c],   m = pixel (B*H*W of them, NHWC), f = identity or the producer's
 // deferred GroupNorm(+ReLU) (XL_CONV_NORM_IN: per-(image, channel) {scale, shift}), plus the GroupNorm partial sums of the
-// OUTPUT (as the fp32 kernel's epilogue, csrc/xl_cnn.hip), so a 1x1 layer stays ONE launch.  The loop is the 256 x 256
+// OUTPUT (as the fp32 kernel's epilogue, csrc/xl_igemm.hip), so a 1x1 layer stays ONE launch.  The loop is the 256 x 256
 // persistent loop above with a different activation path: the weights W are split once on the host (interleaved planes,
 // LDS-DMA ring of 3 stages) but the activations arrive as fp32, so every thread
 //     loads 8 channels of one row (2 x dwordx4, two K-steps ahead of the multiplies),
@@ -1116,12 +1114,8 @@ static int launch_split_conv1x1(const xl_op &op, SplitConvArgs a, bool norm, int
                    : Z > 1 ? reinterpret_cast<const void *>(split_conv1x1_kernel<false, false, NW, 1, BN>)
                            : reinterpret_cast<const void *>(split_conv1x1_kernel<false, false, NW, 0, BN>);
     static XlLdsLimit configured[6];
-    int cfgDev;
     const int slot = accumulate ? 2 : (resid ? 5 : (norm ? 1 : (dominant ? 4 : (Z > 1 ? 3 : 0))));
-    if (configured[slot].needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[slot].done(lds, cfgDev);
-    }
+    if (configured[slot].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
     const int nwg = tileCount < 0 ? a.nbm * a.nbn * Z : tileCount;
     a.tile0 = tileFrom; a.ntiles = nwg;
     int grid = 256;                                   // persistent: one workgroup per CU
@@ -1189,8 +1183,6 @@ static int xl_run_split_conv1x1(const xl_op &op, hipStream_t st)
     return launch_split_conv1x1<8, 256>(op, a, norm, Z, st);
 }
 
-int xl_run_pair(const xl_op &op, hipStream_t st);       // csrc/xl_gemm_pair.hip
-
 int xl_run_split_gemm(const xl_op &op, hipStream_t st)
 {
     if (op.flags & XL_CONV_PAIR_F16) return xl_run_pair(op, st);
@@ -1215,13 +1207,8 @@ int xl_run_split_gemm(const xl_op &op, hipStream_t st)
         auto kernel = fourWaves ? (op.Cin == 512 ? split_gemm_persist4_kernel<512> : split_gemm_persist4_kernel<0>)
                                 : (op.Cin == 512 ? split_gemm_persist_kernel<512> : split_gemm_persist_kernel<0>);
         static XlLdsLimit configured[4];
-        int cfgDev;
         const int slot = (op.Cin == 512 ? 1 : 0) + (fourWaves ? 2 : 0);
-        if (configured[slot].needs(lds, &cfgDev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds) != hipSuccess) return XL_ERR_HIP;
-            configured[slot].done(lds, cfgDev);
-        }
+        if (configured[slot].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
         static const bool clkDbg = getenv("XL_SPLIT_CLK") != nullptr;
         const int nwg = a.nbm * a.nbn * Z;
         int grid = 256;

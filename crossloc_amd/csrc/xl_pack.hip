@@ -4,12 +4,41 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
+
+// the operands of the fp32 implicit GEMM (xl_igemm.hip)
+__global__ void pack_weight_kernel(const float *__restrict__ src, float *__restrict__ dst, int Cout, int Cin, int k)
+{
+    const long long total = (long long)Cout * Cin * k * k;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        // dst index i = ((o*(Cin/32) + chunk)*k*k + tap)*32 + cl   (chunk-major, tap, channel-in-chunk)
+        const int cl = (int)(i % 32);
+        long long t = i / 32;
+        const int tap = (int)(t % (k * k)); t /= (k * k);
+        const int chunk = (int)(t % (Cin / 32));
+        const int o = (int)(t / (Cin / 32));
+        const int c = chunk * 32 + cl, ky = tap / k, kx = tap - ky * k;
+        dst[i] = src[(((long long)o * Cin + c) * k + ky) * k + kx];
+    }
+}
+
+// dgrad operand: dst[((c*(Cout/32) + ochunk)*k*k + tap)*32 + ol] = src[o][c][ky][kx], o = ochunk*32 + ol
+__global__ void pack_weight_dgrad_kernel(const float *__restrict__ src, float *__restrict__ dst, int Cout, int Cin, int k)
+{
+    const long long total = (long long)Cout * Cin * k * k;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const int ol = (int)(i % 32);
+        long long t = i / 32;
+        const int tap = (int)(t % (k * k)); t /= (k * k);
+        const int ochunk = (int)(t % (Cout / 32));
+        const int c = (int)(t / (Cout / 32));
+        const int o = ochunk * 32 + ol, ky = tap / k, kx = tap - ky * k;
+        dst[i] = src[(((long long)o * Cin + c) * k + ky) * k + kx];
+    }
+}
 
 // G of F(m x m, 3x3): [(m+2)][3], the matrices of crossloc_amd/networks.py::_Plan._WINO_G
 template <int M> struct WinoG;
@@ -275,22 +304,41 @@ int launch_wino_pairs(const PairItem *items, const PairItem &one, int n, long lo
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(wino_weight_pair_kernel<M, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds0) != hipSuccess)
         return XL_ERR_HIP;
     hipLaunchKernelGGL((wino_weight_pair_kernel<M, 0>), dim3((unsigned)blocks0, n), dim3(256), lds0, st, items, one);
-    hipLaunchKernelGGL((wino_weight_pair_kernel<M, 1>), dim3((unsigned)blocks, n), dim3(256), 0, st, items, one);
+    hipLaunchKernelGGL((wino_weight_pair_kernel<M, 1>), dim3(blocks, n), dim3(256), 0, st, items, one);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 int launch_plain_pairs(const PairItem *items, const PairItem &one, int n, long long maxTotal, hipStream_t st)
 {
-    long long blocks = (maxTotal + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
+    const unsigned blocks = xl_grid(maxTotal, 256, 4096);
     // (the maxima pass on few workgroups: thousands of waves arriving at once would all find the slot still empty and serialise
     //  their atomics - 46 us for a 512 x 512 matrix against 5 for the split pass)
     hipLaunchKernelGGL(pair_weight_kernel<0>, dim3((unsigned)(blocks < 32 ? blocks : 32), n), dim3(256), 0, st, items, one);
-    hipLaunchKernelGGL(pair_weight_kernel<1>, dim3((unsigned)blocks, n), dim3(256), 0, st, items, one);
+    hipLaunchKernelGGL(pair_weight_kernel<1>, dim3(blocks, n), dim3(256), 0, st, items, one);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 }  // namespace
 
 extern "C" {
+
+int xl_cnn_pack_conv_weight(const float *w_oihw_dev, float *w_ohwi_dev, int Cout, int Cin, int k, void *stream)
+{
+    if (!w_oihw_dev || !w_ohwi_dev || Cout <= 0 || Cin <= 0 || k <= 0) return XL_ERR_ARG;
+    const long long total = (long long)Cout * Cin * k * k;
+    const unsigned blocks = xl_grid(total, 256, 4096);
+    hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw_dev,
+                       w_ohwi_dev, Cout, Cin, k);
+    return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
+
+int xl_cnn_pack_conv_weight_dgrad(const float *w_oihw_dev, float *w_dgrad_dev, int Cout, int Cin, int k, void *stream)
+{
+    if (!w_oihw_dev || !w_dgrad_dev || Cout <= 0 || Cin <= 0 || k <= 0 || Cout % 32 != 0) return XL_ERR_ARG;
+    const long long total = (long long)Cout * Cin * k * k;
+    const unsigned blocks = xl_grid(total, 256, 4096);
+    hipLaunchKernelGGL(pack_weight_dgrad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw_dev,
+                       w_dgrad_dev, Cout, Cin, k);
+    return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
 
 int xl_cnn_pack_wino_weight(const float *w, void *dst, int Cout, int Cin, int m, int dgrad, int form, void *stream)
 {
@@ -298,12 +346,11 @@ int xl_cnn_pack_wino_weight(const float *w, void *dst, int Cout, int Cin, int m,
     const int K = dgrad ? Cout : Cin;
     if (form == 2 && K % 16 != 0) return XL_ERR_ARG;
     const long long total = (long long)Cout * Cin;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
+    const unsigned blocks = xl_grid(total, 256, 8192);
     hipStream_t st = (hipStream_t)stream;
-    if (m == 2) hipLaunchKernelGGL(wino_weight_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
-    else if (m == 4) hipLaunchKernelGGL(wino_weight_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
-    else hipLaunchKernelGGL(wino_weight_kernel<6>, dim3((unsigned)blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
+    if (m == 2) hipLaunchKernelGGL(wino_weight_kernel<2>, dim3(blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
+    else if (m == 4) hipLaunchKernelGGL(wino_weight_kernel<4>, dim3(blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
+    else hipLaunchKernelGGL(wino_weight_kernel<6>, dim3(blocks), dim3(256), 0, st, w, dst, Cout, Cin, dgrad ? 1 : 0, form);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 
@@ -311,9 +358,8 @@ int xl_cnn_split_weight(const float *src, void *dst, int rows, int K, int taps, 
 {
     if (!src || !dst || rows < 1 || K < 16 || K % 16 != 0 || (taps != 0 && taps != 1 && taps != 9) || (taps > 0 && K % taps != 0)) return XL_ERR_ARG;
     const long long total = (long long)rows * K;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(split_weight_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (uint16_t *)dst, rows, K, taps);
+    const unsigned blocks = xl_grid(total, 256, 8192);
+    hipLaunchKernelGGL(split_weight_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (uint16_t *)dst, rows, K, taps);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 
@@ -363,9 +409,8 @@ int xl_cnn_repack_pairs(const xl_pair_item *items_dev, int n, int m, long long m
 int xl_cnn_pair_activation(const float *src, void *dst, long long rows, int K, const float *scale, void *stream)
 {
     if (!src || !dst || !scale || rows < 1 || K < 16 || K % 16 != 0) return XL_ERR_ARG;
-    long long blocks = (rows * K + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(pair_activation_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (uint16_t *)dst, rows, K, scale);
+    const unsigned blocks = xl_grid(rows * K, 256, 65536);
+    hipLaunchKernelGGL(pair_activation_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, (uint16_t *)dst, rows, K, scale);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 

@@ -17,9 +17,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -180,12 +178,7 @@ int launch_s2_dgrad(S2DgradArgs a, hipStream_t st)
 {
     const size_t lds = (size_t)kPR * kPC * (CO * 6 + 16) + 64;
     static XlLdsLimit configured;
-    int cfgDev;
-    if (configured.needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(s2_dgrad_kernel<CO, CI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return XL_ERR_HIP;
-        configured.done(lds, cfgDev);
-    }
+    if (configured.configure(reinterpret_cast<const void *>(s2_dgrad_kernel<CO, CI>), lds) != XL_OK) return XL_ERR_HIP;
     const long long total = (long long)a.B * a.tilesX * a.tilesY;
     int grid = lds * 2 <= 160 * 1024 ? 512 : 256;                      // two workgroups per CU where the patch allows
     if (grid > total) grid = (int)total;

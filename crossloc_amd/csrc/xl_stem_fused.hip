@@ -6,7 +6,7 @@
 // back, applying GroupNorm + ReLU and splitting every value into its three bf16 terms once per (output pixel, tap) that uses
 // it - 2.25 times per value - inside its K-loop: 7 VALU instructions per MFMA, the layer ran at a third of the matrix pipe.
 // Here the full-resolution tensor never exists.  The GroupNorm statistics of conv1 come from a statistics-only evaluation
-// (conv1_mfma_kernel<0>, csrc/xl_cnn.hip, then XL_OP_GN_FINAL); this kernel then walks tiles of 8 x 16 conv2 outputs:
+// (conv1_mfma_kernel<0>, csrc/xl_conv1.hip, then XL_OP_GN_FINAL); this kernel then walks tiles of 8 x 16 conv2 outputs:
 //   1. the 19 x 36 image halo of the tile is split into bf16 planes in LDS ({R, G, B, 0} words, as conv1_mfma_kernel);
 //   2. conv1 is evaluated on the 17 x 33 patch of its outputs the tile needs - 18 blocks of 32 pixels, 18 MFMAs each, the
 //      arithmetic of conv1_mfma_kernel term for term -, normalised with the {scale, shift} pairs (one fmaf, one v_med3_f32 that
@@ -27,9 +27,7 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -443,21 +441,14 @@ int xl_run_stem12(const xl_op &op, hipStream_t st)
     const void *fn = tileRows == 8 ? (pair ? reinterpret_cast<const void *>(stem12_kernel<8, true>) : reinterpret_cast<const void *>(stem12_kernel<8>))
                                    : (pair ? reinterpret_cast<const void *>(stem12_kernel<4, true>) : reinterpret_cast<const void *>(stem12_kernel<4>));
     static XlLdsLimit configured[4];
-    int cfgDev;
     const int cslot = (tileRows == 8 ? 1 : 0) + (pair ? 2 : 0);
-    if (configured[cslot].needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[cslot].done(lds, cfgDev);
-    }
+    if (configured[cslot].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
     // (XL_STEM12_WGS=3, pair form with 4-row tiles: three workgroups per CU - 53 KB of LDS and at most 168 registers each)
     static const bool wg3 = getenv("XL_STEM12_WGS") && atoi(getenv("XL_STEM12_WGS")) == 3;
     const bool three = wg3 && pair && tileRows == 4 && 3 * lds <= 160 * 1024;
     if (three) {
         static XlLdsLimit configured3;
-        if (configured3.needs(lds, &cfgDev)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(stem12_kernel<4, true, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-            configured3.done(lds, cfgDev);
-        }
+        if (configured3.configure(reinterpret_cast<const void *>(stem12_kernel<4, true, 3>), lds) != XL_OK) return XL_ERR_HIP;
     }
     int grid = tileRows == 8 ? 256 : three ? 768 : 512;               // persistent: one / two (three) workgroups per CU
     if (grid > total) grid = (int)total;

@@ -28,9 +28,7 @@
 #include <string.h>
 #include <type_traits>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -485,14 +483,10 @@ int launch_stem(StemArgs a, bool norm, hipStream_t st)
     constexpr int BM = 4 * NW * CPT;
     const size_t lds = 3 * NT * kUnit + 2 * BM * kUnit + 4096 + 1024 + 1024;
     static XlLdsLimit configured[2];
-    int cfgDev;
     constexpr int WPS = NW * PER_CU / 4 < 2 ? 2 : NW * PER_CU / 4;
     const void *fn = norm ? reinterpret_cast<const void *>(split_conv3x3s2_kernel<NT, true, NW, WPS, CPT>)
                           : reinterpret_cast<const void *>(split_conv3x3s2_kernel<NT, false, NW, WPS, CPT>);
-    if (configured[norm].needs(lds, &cfgDev)) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[norm].done(lds, cfgDev);
-    }
+    if (configured[norm].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
     a.nbm = (a.M + BM - 1) / BM;
     constexpr int WM = NW / (NT / 64);
     if (a.stats && (a.nchunks < ((a.Ho * a.Wo + BM - 1) / BM + 1) * WM || a.G * (NT == 64 ? 2 : NT == 256 || a.nbn == 2 ? 8 : 4) != a.nbn * NT)) return XL_ERR_ARG;

@@ -16,9 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/crossloc_cnn.h"
-#include "../../include/crossloc_dsac.h"   // status codes
-#include "xl_common.h"
+#include "xl_launch.h"
 #include "xl_operand_math.h"
 
 namespace {
@@ -236,12 +234,8 @@ int xl_run_wgrad_split(const xl_op &op, hipStream_t st)
     a.normLo = (op.flags & XL_CONV_NORM_RELU) ? 0.f : -__builtin_inff();
     const size_t lds = 4 * (size_t)kOperand;                          // two stages of two operands: 96 KB
     static XlLdsLimit configured[2];
-    int cfgDev;
-    if (configured[norm].needs(lds, &cfgDev)) {
-        const void *fn = norm ? reinterpret_cast<const void *>(wgrad_split_kernel<true>) : reinterpret_cast<const void *>(wgrad_split_kernel<false>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return XL_ERR_HIP;
-        configured[norm].done(lds, cfgDev);
-    }
+    const void *fn = norm ? reinterpret_cast<const void *>(wgrad_split_kernel<true>) : reinterpret_cast<const void *>(wgrad_split_kernel<false>);
+    if (configured[norm].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
     if (norm) hipLaunchKernelGGL(wgrad_split_kernel<true>, dim3(a.zCount * a.nbo * a.nbc * a.splits), dim3(512), lds, st, a);
     else hipLaunchKernelGGL(wgrad_split_kernel<false>, dim3(a.zCount * a.nbo * a.nbc * a.splits), dim3(512), lds, st, a);
     return XL_OK;

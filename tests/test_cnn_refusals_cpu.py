@@ -1,0 +1,259 @@
+"""The refusals of the forward CNN launchers, as a table.  No GPU.
+
+A launcher validates an op before it makes any HIP call and answers a malformed one with XL_ERR_ARG (-1) or XL_ERR_UNSUPPORTED
+(-4); xl_cnn_run then names the op ("op 0 refused (...)") behind whatever text the launcher left.  Every row below is one
+malformed op fed to xl_cnn_run alone, with null or dummy pointers (never dereferenced on the host) and stream = NULL, and
+pins the exact status - for a handful also a piece of xl_cnn_last_error().  There is one row per refusing statement of the
+launchers of XL_OP_CONV1, XL_OP_CONV (the fp32 implicit GEMM: dispatch and launcher), XL_OP_WINO_IN / XL_OP_WINO_OUT (m = 2,
+4, 6), XL_OP_GN_STATS / GN_APPLY / GN_FINAL, XL_OP_HEAD and XL_OP_DUC_HEAD that is reached before the first HIP call, and rows
+with two faults that pin which check comes first where the statuses differ.  The expected values were recorded from the
+library before the launchers were split over translation units.
+
+Not in the table, because a HIP call comes first: a failed hipFuncSetAttribute of the implicit GEMM ("hipFuncSetAttribute:
+..." with XL_ERR_HIP) and of the LDS-DMA F(6x6) output transform, the XL_CONV_CLK allocation and copies, and the launch
+errors xl_cnn_run collects with hipGetLastError() at the end of a list.  The launchers of other translation units (split and
+pair GEMMs, stem kernels, the backward ops) are outside this table, except that an unknown op type is refused."""
+import ctypes
+
+import pytest
+
+from crossloc_amd import ops
+
+ARG, UNSUPPORTED = -1, -4
+_BUF = ctypes.create_string_buffer(256)
+P = ctypes.addressof(_BUF)              # a dummy non-null pointer, and a second one that differs
+Q = P + 64
+
+CONV1, CONV, GN_STATS, GN_APPLY, HEAD = ops.XL_OP_CONV1, ops.XL_OP_CONV, ops.XL_OP_GN_STATS, ops.XL_OP_GN_APPLY, ops.XL_OP_HEAD
+GN_FINAL, WINO_IN, WINO_OUT, DUC_HEAD = ops.XL_OP_GN_FINAL, ops.XL_OP_WINO_IN, ops.XL_OP_WINO_OUT, ops.XL_OP_DUC_HEAD
+DGRAD, ACC, SPLIT, IL, PAIR = ops.CONV_DGRAD, ops.CONV_ACCUMULATE, ops.CONV_SPLIT_BF16, ops.CONV_SPLIT_IL, ops.CONV_PAIR_F16
+NORM_IN, TILE_MAJOR, GN_ADD = ops.CONV_NORM_IN, ops.CONV_M_TILE_MAJOR, ops.GN_ADD
+
+
+def _conv(**kw):
+    """a well-formed 3x3 stride-1 64 -> 64 convolution over 16 x 16 pixels, then the fault"""
+    d = dict(type=CONV, B=1, Hi=16, Wi=16, Cin=64, Ho=16, Wo=16, Cout=64, ksize=3, stride=1, ld_in=64, ld_out=64)
+    d.update(kw)
+    return d
+
+
+def _c1(**kw):
+    """the inference form of conv1 (3 -> 32) on a 16 x 64 image: one tile of the matrix-pipe form"""
+    d = dict(type=CONV1, B=1, Hi=16, Wi=64, Cin=3, Cout=32, ld_out=32, nchunks=1, groups=32, stats=P)
+    d.update(kw)
+    return d
+
+
+def _win(m, **kw):
+    d = dict(type=WINO_IN, B=1, Hi=12, Wi=12, Cin=128, Ho=12 // m, Wo=12 // m, ksize=m, ld_in=128, ld_out=128)
+    d.update(kw)
+    return d
+
+
+def _wout(m, **kw):
+    """12 x 12 output pixels, 4 tiles per workgroup"""
+    tiles = (12 // m) ** 2
+    d = dict(type=WINO_OUT, B=1, Hi=12, Wi=12, Cin=128, ksize=m, ld_out=128, reserved_i=4, nchunks=(tiles + 3) // 4)
+    d.update(kw)
+    return d
+
+
+def _head(**kw):
+    d = dict(type=HEAD, B=1, Hi=4, Wi=4, Cin=512, Cout=4, ld_in=512, n_task=3, n_pos=1)
+    d.update(kw)
+    return d
+
+
+def _duc(**kw):
+    d = dict(type=DUC_HEAD, B=1, Hi=2, Wi=2, Cin=384, Cout=6, Ho=16, Wo=16, ld_in=384)
+    d.update(kw)
+    return d
+
+
+def _gn(t, **kw):
+    d = dict(type=t, B=1, Hi=16, Wi=16, Cin=64, groups=32, nchunks=4, ld_in=64, ld_out=64)
+    d.update(kw)
+    return d
+
+
+# (name, op fields, status, piece of the error text or None)
+TABLE = [
+    # ---- XL_OP_CONV1: matrix-pipe inference form, VALU inference form, direct form
+    ("conv1-mfma-tile-count", _c1(nchunks=2), ARG, None),
+    ("conv1-mfma-groups", _c1(groups=16), ARG, None),
+    ("conv1-fused-cin", _c1(Cin=4, reserved_i=1), ARG, None),
+    ("conv1-fused-cout", _c1(Cout=64, reserved_i=4), ARG, None),
+    ("conv1-fused-ld", _c1(ld_out=64, reserved_i=4), ARG, None),
+    ("conv1-fused-negative-form", _c1(reserved_i=-1), ARG, None),
+    ("conv1-fused-too-few-chunks", _c1(reserved_i=1, nchunks=3), ARG, None),
+    ("conv1-fused-groups", _c1(reserved_i=4, groups=16), ARG, None),
+    ("conv1-fused-apply-cout", _c1(stats=0, aux2=P, Cout=16, reserved_i=4), ARG, None),
+    ("conv1-direct-cout-8", dict(type=CONV1, B=1, Hi=8, Wi=8, Cin=3, Cout=12, ld_out=12), ARG, None),
+    ("conv1-direct-cout-max", dict(type=CONV1, B=1, Hi=8, Wi=8, Cin=3, Cout=72, ld_out=72), ARG, None),
+    ("conv1-direct-threads-per-pixel", dict(type=CONV1, B=1, Hi=8, Wi=8, Cin=3, Cout=24, ld_out=24), ARG, None),
+    ("conv1-direct-ld", dict(type=CONV1, B=1, Hi=8, Wi=8, Cin=3, Cout=32, ld_out=34), ARG, None),
+    # ---- XL_OP_CONV: dispatch
+    ("conv-cin-32", _conv(Cin=48), ARG, None),
+    ("conv-cout-32", _conv(Cout=48), ARG, None),
+    ("conv-ld-in", _conv(ld_in=66), ARG, None),
+    ("conv-cin-before-ksize", _conv(Cin=48, ksize=5), ARG, None),
+    ("conv-ksize", _conv(ksize=5), UNSUPPORTED, None),
+    ("conv-ksize-before-ld-out", _conv(ksize=5, ld_out=66), UNSUPPORTED, None),
+    ("conv-1x1-stride-2", _conv(ksize=1, stride=2), UNSUPPORTED, None),
+    ("conv-3x3-stride-3", _conv(stride=3), UNSUPPORTED, None),
+    ("conv-dgrad-ksize", _conv(flags=DGRAD, ksize=5), UNSUPPORTED, None),
+    ("conv-dgrad-stride", _conv(flags=DGRAD, stride=3), UNSUPPORTED, None),
+    ("conv-dgrad-1x1-stride-2", _conv(flags=DGRAD, ksize=1, stride=2), UNSUPPORTED, None),
+    ("conv-wino-batch-narrow", _conv(ksize=1, nchunks2=16), UNSUPPORTED, None),
+    ("conv-wino-batch-narrow-before-stats", _conv(ksize=1, nchunks2=16, stats=P, groups=32), UNSUPPORTED, None),
+    ("conv-norm-narrow", _conv(ksize=1, flags=NORM_IN, aux2=P), UNSUPPORTED, None),
+    ("conv-norm-small-tiles", _conv(ksize=1, Cout=128, ld_out=128, flags=NORM_IN, aux2=P, reserved_i=64), UNSUPPORTED, None),
+    ("conv-norm-small-tiles-before-coefficients", _conv(ksize=1, Cout=128, ld_out=128, flags=NORM_IN, reserved_i=64), UNSUPPORTED, None),
+    # ---- XL_OP_CONV: the launcher
+    ("conv-norm-no-coefficients", _conv(ksize=1, Cout=128, ld_out=128, flags=NORM_IN), ARG, None),
+    ("conv-norm-image-below-tile", _conv(ksize=1, Cout=128, ld_out=128, flags=NORM_IN, aux2=P, Hi=8, Wi=8, Ho=8, Wo=8), ARG, None),
+    ("conv-wino-batch-stats", _conv(ksize=1, Cout=128, ld_out=128, nchunks2=16, stats=P, groups=32), ARG, None),
+    ("conv-wino-batch-stats-before-ld-out", _conv(ksize=1, Cout=128, ld_out=130, nchunks2=16, stats=P, groups=32), ARG, None),
+    ("conv-stats-image-below-tile", _conv(stats=P, groups=32, nchunks=8, Hi=8, Wi=8, Ho=8, Wo=8), ARG, None),
+    ("conv-stats-groups-divide", _conv(stats=P, groups=24, nchunks=8), ARG, None),
+    ("conv-stats-group-in-tile", _conv(Cout=96, ld_out=96, stats=P, groups=2, nchunks=8), ARG, None),
+    ("conv-stats-too-few-slots", _conv(stats=P, groups=32, nchunks=2), ARG, None),
+    ("conv-stats-piece", _conv(stats=P, groups=64, nchunks=8), ARG, None),
+    ("conv-weight-bytes", _conv(Cin=8192, Cout=8192, ld_in=8192, ld_out=8192), ARG, "conv weights of 2415919104 bytes"),
+    ("conv-weight-bytes-before-ld-out", _conv(Cin=8192, Cout=8192, ld_in=8192, ld_out=8194), ARG, "conv weights of"),
+    ("conv-2gib-one-image", _conv(Hi=4096, Wi=4096, Ho=4096, Wo=4096, Cin=32, ld_in=32), ARG, "exceed 32-bit buffer addressing"),
+    ("conv-2gib-dgrad-s2", _conv(flags=DGRAD, stride=2, B=64, Hi=512, Wi=512, Ho=1024, Wo=1024), ARG, "exceed 32-bit buffer addressing"),
+    ("conv-2gib-wino-batch", _conv(ksize=1, Cin=128, ld_in=128, Cout=128, ld_out=128, nchunks2=16, B=64, Hi=256, Wi=256, Ho=256, Wo=256),
+     ARG, "exceed 32-bit buffer addressing"),
+    ("conv-ld-out", _conv(ld_out=66), ARG, None),
+    ("conv-dgrad-bias", _conv(flags=DGRAD, bias=P), ARG, None),
+    ("conv-wino-batch-bias", _conv(ksize=1, Cout=128, ld_out=128, nchunks2=16, bias=P), ARG, None),
+    ("conv-accumulate-stats", _conv(flags=ACC, stats=P, groups=32, nchunks=8), ARG, None),
+    # ---- XL_OP_WINO_IN
+    ("wino6-in-cin", _win(6, Cin=126, ld_in=126), ARG, None),
+    ("wino6-in-ld", _win(6, ld_in=129), ARG, None),
+    ("wino6-in-tile-rows", _win(6, Hi=13), ARG, None),
+    ("wino6-in-tile-columns", _win(6, Wi=13), ARG, None),
+    ("wino6-in-interleaved-cin", _win(6, Cin=192, ld_in=192, flags=SPLIT | IL), ARG, None),
+    ("wino6-in-fold-no-coefficients", _win(6, out2=P), ARG, None),
+    ("wino6-in-fold-ld-side", _win(6, out2=P, aux2=Q, ld_out=129), ARG, None),
+    ("wino6-in-fold-no-residual", _win(6, out2=P, aux2=Q, flags=GN_ADD), ARG, None),
+    ("wino6-in-fold-ld-residual", _win(6, out2=P, aux2=Q, flags=GN_ADD, aux=Q, ld_aux=129), ARG, None),
+    ("wino6-in-fold-aliases-input", _win(6, out2=P, aux2=Q, **{"in_": P}), ARG, None),
+    ("wino6-in-fold-aliases-residual", _win(6, out2=P, aux2=Q, flags=GN_ADD, aux=P, ld_aux=128), ARG, None),
+    ("wino6-in-fold-bf16", _win(6, out2=P, aux2=Q, flags=SPLIT), UNSUPPORTED, None),
+    ("wino6-in-pair-no-scale", _win(6, flags=PAIR), ARG, None),
+    ("wino6-in-pair-cin", _win(6, Cin=72, ld_in=72, flags=PAIR, scale=P), ARG, None),
+    ("wino4-in-cin", _win(4, Cin=126, ld_in=126), ARG, None),
+    ("wino4-in-ld", _win(4, ld_in=129), ARG, None),
+    ("wino4-in-tile-rows", _win(4, Hi=13), ARG, None),
+    ("wino4-in-tile-columns", _win(4, Wi=13), ARG, None),
+    ("wino2-in-deferred-norm", _win(2, aux2=P), ARG, None),
+    ("wino2-in-cin", _win(2, Cin=126, ld_in=128), ARG, None),
+    ("wino2-in-ld", _win(2, ld_in=130), ARG, None),
+    ("wino2-in-rows", _win(2, Hi=13), ARG, None),
+    ("wino2-in-columns", _win(2, Wi=13), ARG, None),
+    # ---- XL_OP_WINO_OUT
+    ("wino6-out-cin-odd", _wout(6, Cin=127), ARG, None),
+    ("wino6-out-cin-block", _wout(6, Cin=384, ld_out=384), ARG, None),
+    ("wino6-out-threads", _wout(6, Cin=96, ld_out=96), ARG, None),
+    ("wino6-out-ld", _wout(6, ld_out=129), ARG, None),
+    ("wino6-out-tiles-per-block", _wout(6, reserved_i=0), ARG, None),
+    ("wino6-out-chunks", _wout(6, nchunks=2), ARG, None),
+    ("wino6-out-stats-no-groups", _wout(6, stats=P), ARG, None),
+    ("wino6-out-stats-groups-divide", _wout(6, stats=P, groups=24), ARG, None),
+    ("wino6-out-stats-group-in-block", _wout(6, Cin=768, ld_out=768, stats=P, groups=2), ARG, None),
+    ("wino4-out-tile-major", _wout(4, flags=TILE_MAJOR), UNSUPPORTED, None),
+    ("wino4-out-tile-major-before-cin", _wout(4, Cin=127, flags=TILE_MAJOR), UNSUPPORTED, None),
+    ("wino4-out-cin-odd", _wout(4, Cin=127), ARG, None),
+    ("wino4-out-cin-block", _wout(4, Cin=768, ld_out=768), ARG, None),
+    ("wino4-out-threads", _wout(4, Cin=96, ld_out=96), ARG, None),
+    ("wino4-out-ld", _wout(4, ld_out=129), ARG, None),
+    ("wino4-out-tiles-per-block", _wout(4, reserved_i=0), ARG, None),
+    ("wino4-out-chunks", _wout(4, nchunks=2), ARG, None),
+    ("wino4-out-stats-no-groups", _wout(4, stats=P), ARG, None),
+    ("wino4-out-stats-groups-divide", _wout(4, stats=P, groups=24), ARG, None),
+    ("wino4-out-stats-group-in-block", _wout(4, Cin=1536, ld_out=1536, stats=P, groups=2), ARG, None),
+    ("wino4-out-stats-writers", _wout(4, Cin=512, ld_out=512, stats=P, groups=512), ARG, None),
+    ("wino2-out-cin", _wout(2, Cin=126), ARG, None),
+    ("wino2-out-cin-max", _wout(2, Cin=2048, ld_out=2048), ARG, None),
+    ("wino2-out-threads", _wout(2, Cin=48, ld_out=48), ARG, None),
+    ("wino2-out-ld", _wout(2, ld_out=130), ARG, None),
+    ("wino2-out-tiles-per-block", _wout(2, reserved_i=0), ARG, None),
+    ("wino2-out-rows", _wout(2, Hi=13), ARG, None),
+    ("wino2-out-columns", _wout(2, Wi=13), ARG, None),
+    ("wino2-out-chunks", _wout(2, nchunks=8), ARG, None),
+    ("wino2-out-stats-no-groups", _wout(2, stats=P), ARG, None),
+    ("wino2-out-stats-groups-max", _wout(2, Cin=1024, ld_out=1024, stats=P, groups=512), ARG, None),
+    ("wino2-out-stats-groups-divide", _wout(2, stats=P, groups=24), ARG, None),
+    # ---- GroupNorm
+    ("gn-stats-cin", _gn(GN_STATS, Cin=66, groups=33), ARG, None),
+    ("gn-stats-groups-divide", _gn(GN_STATS, groups=24), ARG, None),
+    ("gn-stats-ld", _gn(GN_STATS, ld_in=66), ARG, None),
+    ("gn-stats-threads-max", _gn(GN_STATS, Cin=4100, ld_in=4100, groups=1), ARG, None),
+    ("gn-stats-whole-waves", _gn(GN_STATS, Cin=1040, ld_in=1040, groups=1), ARG, None),
+    ("gn-stats-groups-max", _gn(GN_STATS, Cin=1024, ld_in=1024, groups=1024), ARG, None),
+    ("gn-apply-cin", _gn(GN_APPLY, Cin=66), ARG, None),
+    ("gn-apply-ld-in", _gn(GN_APPLY, ld_in=66), ARG, None),
+    ("gn-apply-ld-out", _gn(GN_APPLY, ld_out=66), ARG, None),
+    ("gn-final-groups-max", _gn(GN_FINAL, groups=64), ARG, None),
+    ("gn-final-groups-divide", _gn(GN_FINAL, groups=24), ARG, None),
+    ("gn-final-slots", _gn(GN_FINAL, reserved_i=128, nchunks=2), ARG, None),
+    ("gn-final-slots-aligned-tiles", _gn(GN_FINAL, reserved_i=-128, nchunks=1), ARG, None),
+    ("gn-final-slots-per-tile", _gn(GN_FINAL, reserved_i=-128, stride=2, nchunks=3), ARG, None),
+    # ---- heads
+    ("head-cin-4", _head(Cin=6, ld_in=8), ARG, None),
+    ("head-cin-min", _head(Cin=0), ARG, None),
+    ("head-cin-max", _head(Cin=2052, ld_in=2052), ARG, None),
+    ("head-cout-max", _head(Cout=9), ARG, None),
+    ("head-cout-min", _head(Cout=0), ARG, None),
+    ("head-ld", _head(ld_in=514), ARG, None),
+    ("head-norm-cin", _head(Cin=256, ld_in=256, aux2=P), UNSUPPORTED, None),
+    ("head-norm-cout", _head(Cout=5, aux2=P), UNSUPPORTED, None),
+    ("head-cin-before-norm", _head(Cin=6, ld_in=8, aux2=P), ARG, "op 0 refused (type 4, k0 s0, 6 -> 4 channels, in 4x4 out 0x0, B 1, ld 8/0, flags 0x0, Z 0, form 0)"),
+    ("duc-head-cout-min", _duc(Cout=0, Cin=0), ARG, None),
+    ("duc-head-cout-max", _duc(Cout=9, Cin=576), ARG, None),
+    ("duc-head-cin", _duc(Cin=320), ARG, None),
+    ("duc-head-rows", _duc(Ho=0), ARG, None),
+    ("duc-head-columns", _duc(Wo=0), ARG, "op 0 refused (type 14"),
+    # ---- anything else goes to the backward dispatcher, which knows no such op
+    ("unknown-op-type", dict(type=99), UNSUPPORTED, "op 0 refused (type 99"),
+]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return ops._bind()
+
+
+def test_the_table_has_one_name_per_row():
+    names = [row[0] for row in TABLE]
+    assert len(set(names)) == len(names)
+
+
+@pytest.mark.parametrize("name,fields,status,text", TABLE, ids=[row[0] for row in TABLE])
+def test_a_malformed_op_is_refused_with_its_status(lib, name, fields, status, text):
+    op = ops.XlOp()
+    for k, v in fields.items():
+        assert hasattr(op, k), k
+        setattr(op, k, v)
+    rc = lib.xl_cnn_run(ctypes.byref(op), 1, None)
+    msg = lib.xl_cnn_last_error().decode()
+    assert rc == status, (name, rc, msg)
+    assert "op 0 refused (type %d" % fields["type"] in msg, msg
+    if text is not None:
+        assert text in msg, msg
+    if text is None or text.startswith("op 0"):
+        assert msg.startswith("op 0 refused"), msg                         # no launcher text in front
+
+
+def test_a_refusal_stops_the_list_and_names_the_index(lib):
+    arr = (ops.XlOp * 2)()
+    for op in arr:
+        for k, v in _head(Cin=6, ld_in=8).items():
+            setattr(op, k, v)
+    arr[0].Cin, arr[0].ld_in, arr[0].Cout = 512, 512, 9
+    assert lib.xl_cnn_run(arr, 2, None) == ARG
+    assert "op 0 refused" in lib.xl_cnn_last_error().decode() and "512 -> 9 channels" in lib.xl_cnn_last_error().decode()
+    assert lib.xl_cnn_run(None, 1, None) == ARG
+    assert lib.xl_cnn_run(arr, -1, None) == ARG
