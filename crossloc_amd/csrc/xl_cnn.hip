@@ -5,12 +5,13 @@
 //   XL_OP_CONV1                          xl_conv1.hip       3x3 s1 on the NCHW image -> NHWC: direct, fused and matrix-pipe forms
 //   XL_OP_CONV                           xl_igemm.hip       the dispatch; implicit GEMM on exact-fp32 MFMA (fallbacks, data gradients)
 //                                        xl_gemm_split.hip, xl_gemm_pair.hip      1x1 and Winograd GEMMs on the bf16 / fp16 matrix pipe
-//                                        xl_stem_split.hip, xl_stem_pair.hip      the 3x3 stride-2 stem convolutions on those pipes
+//                                        xl_stem_split.hip, xl_stem_pair.hip      the 3x3 stride-2 stem convolutions on those pipes:
+//                                                                                 one loop (xl_stem_s2.h, xl_stem_s2_body.h), two forms
 //   XL_OP_STEM12, XL_OP_S2_DGRAD         xl_stem_fused.hip, xl_stem_dgrad.hip
 //   XL_OP_WINO_IN, XL_OP_WINO_OUT        xl_wino.hip        Winograd F(2x2), F(4x4), F(6x6) input / output transforms
 //   XL_OP_GN_STATS, _FINAL, _APPLY       xl_gn.hip          GroupNorm: fp64 partial sums, per-channel scale / shift, apply
 //   XL_OP_HEAD, XL_OP_DUC_HEAD           xl_gn.hip          fc3 + mean offset + exp(hardtanh), NCHW out
-//   every other type (the backward ops)  xl_cnn_bwd.hip     with xl_wgrad_split.hip, xl_wgrad_pair.hip
+//   every other type (the backward ops)  xl_cnn_bwd.hip     with xl_wgrad_split.hip, xl_wgrad_pair.hip (one loop: xl_wgrad.h, xl_wgrad_body.h)
 //
 // The weight packs of all of them are in xl_pack.hip.  fp32 end to end: the MFMA forms are bitwise fmaf chains or exact
 // splits, so parity with the fp32 reference is at summation-order level.

@@ -37,6 +37,12 @@ struct XlLdsLimit {
     }
 };
 
+// The constant V, made to depend on the template parameter P of the function that uses it.  A kernel whose statements are
+// shared between two operand forms (xl_stem_s2_body.h, xl_wgrad_body.h) selects the form's pieces with `if constexpr`; the
+// pieces of the other form do not compile with this form's types, and the compiler leaves a discarded branch unchecked only
+// where the condition depends on a template parameter.
+template <auto P, bool V> inline constexpr bool xl_dependent = V;
+
 // bijective XCD remap: block b runs on XCD b%8; give each XCD a contiguous run of tiles / work items
 __device__ __forceinline__ int xcd_remap(int b, int nwg)
 {

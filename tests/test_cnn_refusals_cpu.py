@@ -7,12 +7,16 @@ pins the exact status - for a handful also a piece of xl_cnn_last_error().  Ther
 launchers of XL_OP_CONV1, XL_OP_CONV (the fp32 implicit GEMM: dispatch and launcher), XL_OP_WINO_IN / XL_OP_WINO_OUT (m = 2,
 4, 6), XL_OP_GN_STATS / GN_APPLY / GN_FINAL, XL_OP_HEAD and XL_OP_DUC_HEAD that is reached before the first HIP call, and rows
 with two faults that pin which check comes first where the statuses differ.  The expected values were recorded from the
-library before the launchers were split over translation units.
+library before the launchers were split over translation units.  The same for the stride-2 3x3 stem convolutions
+(XL_OP_CONV with XL_CONV_SPLIT_BF16, with and without XL_CONV_PAIR_F16) and the weight-gradient products on the matrix pipe
+(XL_OP_WGRAD with XL_CONV_SPLIT_BF16, with and without XL_CONV_PAIR_F16, one split and several): one row per clause of their
+refusing statements, recorded from the library while each operand form still had a launcher of its own.
 
 Not in the table, because a HIP call comes first: a failed hipFuncSetAttribute of the implicit GEMM ("hipFuncSetAttribute:
-..." with XL_ERR_HIP) and of the LDS-DMA F(6x6) output transform, the XL_CONV_CLK allocation and copies, and the launch
-errors xl_cnn_run collects with hipGetLastError() at the end of a list.  The launchers of other translation units (split and
-pair GEMMs, stem kernels, the backward ops) are outside this table, except that an unknown op type is refused."""
+..." with XL_ERR_HIP) and of the LDS-DMA F(6x6) output transform, the XL_CONV_CLK allocation and copies, the stem launchers'
+check of the statistics slots (nchunks, groups), which stands behind XlLdsLimit::configure, and the launch errors xl_cnn_run
+collects with hipGetLastError() at the end of a list.  The launchers of other translation units (split and pair GEMMs, the
+fused stem, the other backward ops) are outside this table, except that an unknown op type is refused."""
 import ctypes
 
 import pytest
@@ -23,7 +27,9 @@ ARG, UNSUPPORTED = -1, -4
 _BUF = ctypes.create_string_buffer(256)
 P = ctypes.addressof(_BUF)              # a dummy non-null pointer, and a second one that differs
 Q = P + 64
+A = (P + 15) & ~15                      # ... and one on a 16-byte boundary, for the launchers that check it (A + 64 is inside _BUF)
 
+WGRAD = ops.XL_OP_WGRAD
 CONV1, CONV, GN_STATS, GN_APPLY, HEAD = ops.XL_OP_CONV1, ops.XL_OP_CONV, ops.XL_OP_GN_STATS, ops.XL_OP_GN_APPLY, ops.XL_OP_HEAD
 GN_FINAL, WINO_IN, WINO_OUT, DUC_HEAD = ops.XL_OP_GN_FINAL, ops.XL_OP_WINO_IN, ops.XL_OP_WINO_OUT, ops.XL_OP_DUC_HEAD
 DGRAD, ACC, SPLIT, IL, PAIR = ops.CONV_DGRAD, ops.CONV_ACCUMULATE, ops.CONV_SPLIT_BF16, ops.CONV_SPLIT_IL, ops.CONV_PAIR_F16
@@ -74,6 +80,88 @@ def _gn(t, **kw):
     d = dict(type=t, B=1, Hi=16, Wi=16, Cin=64, groups=32, nchunks=4, ld_in=64, ld_out=64)
     d.update(kw)
     return d
+
+
+def _s2(pair, extra=0, **kw):
+    """a well-formed 3x3 stride-2 64 -> 128 stem convolution, 64 x 64 -> 32 x 32 pixels, in the six-pass or the pair form"""
+    d = dict(type=CONV, B=1, Hi=64, Wi=64, Cin=64, Ho=32, Wo=32, Cout=128, ksize=3, stride=2, ld_in=64, ld_out=128,
+             flags=SPLIT | IL | (PAIR if pair else 0) | extra, w=A, out=A, bias=A, scale=A if pair else 0, **{"in_": A})
+    d.update(kw)
+    return d
+
+
+def _s2_rows():
+    """every clause of the stem launchers' one refusing statement that xl_run_conv lets through, for both forms"""
+    rows = []
+    for pair, form in ((False, "s2-split-"), (True, "s2-pair-")):
+        rows += [(form + name, _s2(pair, **kw), ARG, None) for name, kw in (
+            ("cin", dict(Cin=96, ld_in=96)),
+            ("cout", dict(Cout=96, ld_out=96)),
+            ("rows", dict(Ho=31)),
+            ("columns", dict(Wo=31)),
+            ("image-below-tile", dict(Hi=30, Wi=30, Ho=15, Wo=15)),
+            ("ld-in-below-cin", dict(ld_in=32)),
+            ("ld-out-below-cout", dict(ld_out=64)),
+            ("ld-out-4", dict(ld_out=130)),
+            ("no-bias", dict(bias=0)),
+            ("accumulate", dict(extra=ACC)),
+            ("no-input", {"in_": 0}),
+            ("no-weights", dict(w=0)),
+            ("no-output", dict(out=0)),
+            ("stats-alignment", dict(stats=A + 8, groups=32, nchunks=64)),
+            ("input-alignment", {"in_": A + 4}),
+            ("weight-alignment", dict(w=A + 8)),
+            ("output-alignment", dict(out=A + 4)),
+            ("pixels-2gib", dict(B=1 << 21)),
+            ("two-images-2gib", dict(Hi=4096, Wi=4096, Ho=2048, Wo=2048)),
+            ("tile-rows-2gib", dict(ld_out=1 << 21)),
+            ("norm-no-coefficients", dict(extra=NORM_IN)),
+        )]
+    rows.append(("s2-pair-no-scale", _s2(True, scale=0), ARG, None))
+    # the pair flag alone chooses the pair launcher (xl_run_conv asks for it first), which then misses the scale
+    rows.append(("s2-pair-flag-before-split-flag", _s2(True, flags=PAIR, scale=0), ARG, None))
+    return rows
+
+
+def _wg(pair, splits, extra=0, **kw):
+    """a well-formed 64 -> 64 weight-gradient product over 16 x 16 pixels on the split (pair) pipe; with one split the result
+    goes to `out`, with more the partial tiles to `stats2`"""
+    d = dict(type=WGRAD, B=1, Hi=16, Wi=16, Cin=64, Ho=16, Wo=16, Cout=64, ksize=1, stride=1, ld_in=64, ld_aux=64,
+             nchunks2=splits, flags=SPLIT | (PAIR if pair else 0) | extra, aux=A, out=A, stats2=A,
+             scale=A if pair else 0, out2=A if pair else 0, **{"in_": A})
+    d.update(kw)
+    return d
+
+
+def _wg_rows():
+    """every refusing statement of the weight-gradient launchers behind the checks of xl_run_bwd_op, for both forms, with one
+    split (the launcher gets `out` as its partial tile) and with four"""
+    rows = []
+    for pair, form in ((False, "wgrad-split-"), (True, "wgrad-pair-")):
+        for splits in (1, 4):
+            tag = form + "%d-" % splits
+            rows += [(tag + name, _wg(pair, splits, **kw), ARG, None) for name, kw in (
+                ("ksize", dict(ksize=3)),
+                ("stride", dict(stride=2)),
+                ("cin-4", dict(Cin=66, ld_in=68)),
+                ("no-input", {"in_": 0}),
+                ("no-dy", dict(aux=0)),
+                ("no-partial", dict(out=0) if splits == 1 else dict(stats2=0)),
+                ("norm-no-coefficients", dict(extra=NORM_IN)),
+                ("norm-batched", dict(extra=NORM_IN, aux2=A, groups=4)),
+                ("norm-pixels-8", dict(extra=NORM_IN, aux2=A, Hi=15, Wi=15, Ho=15, Wo=15)),
+                ("batched-ld-in", dict(groups=4, ld_in=68)),
+                ("batched-ld-aux", dict(groups=4, ld_aux=68)),
+                ("x-2gib", dict(Hi=4096, Wi=4096, Ho=4096, Wo=4096, Cout=4, ld_aux=4)),
+                ("dy-2gib", dict(Hi=4096, Wi=4096, Ho=4096, Wo=4096, Cin=4, ld_in=4)),
+            )]
+            if pair:
+                rows += [(tag + "no-scale", _wg(True, splits, scale=0), ARG, None),
+                         (tag + "no-amax", _wg(True, splits, out2=0), ARG, None)]
+    # with the split flag the launcher's own check answers; without it the same shape has no fp32 kernel
+    rows.append(("wgrad-split-ksize-before-fp32-shapes", _wg(False, 4, ksize=3, Cin=48, ld_in=48, Cout=48, ld_aux=48), ARG, None))
+    rows.append(("wgrad-fp32-shapes", _wg(False, 4, flags=0, Cin=48, ld_in=48, Cout=48, ld_aux=48), UNSUPPORTED, None))
+    return rows
 
 
 # (name, op fields, status, piece of the error text or None)
@@ -216,6 +304,9 @@ TABLE = [
     ("duc-head-cin", _duc(Cin=320), ARG, None),
     ("duc-head-rows", _duc(Ho=0), ARG, None),
     ("duc-head-columns", _duc(Wo=0), ARG, "op 0 refused (type 14"),
+    # ---- XL_OP_CONV 3x3 stride 2 on the split / pair pipe, XL_OP_WGRAD on the split / pair pipe (one launcher per family)
+    *_s2_rows(),
+    *_wg_rows(),
     # ---- anything else goes to the backward dispatcher, which knows no such op
     ("unknown-op-type", dict(type=99), UNSUPPORTED, "op 0 refused (type 99"),
 ]
