@@ -353,11 +353,20 @@ struct PairConvArgs {
     int amaxShift;                                   // >= 0 (XL_CONV_PAIR_AMAX): aScale points at the float bits of max |operand source| and the
                                                      // scale is derived here: max 2^e in [2^(14 - shift), 2^(15 - shift))
     int var;                                         // measurement switches (unused)
+    long long *clk;                                  // diagnostics (XL_PAIR_CLK, the CLK instantiations only): per-wave tick sums of the epilogue's phases
 };
 
-template <bool NORM, bool ACC, int NW, int ZB, int BN, bool RES>               // ACC: out += result
+template <bool NORM, bool ACC, int NW, int ZB, int BN, bool RES, bool CLK = false>   // ACC: out += result; CLK: phase clocks (XL_PAIR_CLK)
 __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
 {
+    // Register budget of the 8-wave 256 x 256 forms: two waves per SIMD = 256 VGPRs per lane, no AGPRs (RI = 4).  Live per phase:
+    //   K-step    acc 128 | activation registers rA 16 (+ rR 16, residual form) | fragments fa 32, fb 16, fbs 8 | conversion: x 4,
+    //             coefficients 8, pairs 8 | per-lane offsets ~12 (gA, gR, gB, wOff, slot, frA, frB, cCoef, tid)       ~232 (248)
+    //   epilogue  acc 128 | rA 16 (+ rR 16) and fa[1] 16, fb[0][0] 4 of the next tile's first step | coefficient table 4 | statistics
+    //             chains s, ss 16, t, tt 2 | one block's exchanged quads 16 (+ 32 old values, accumulate form) | offsets ~10
+    //                                                                                                                  ~212 (244)
+    // The compiler reports 205-213 (plain, NORM), 227 (residual), 235 (accumulate) and no spill; tests/test_pair_gemm_resources.py
+    // holds it to that.  What does NOT fit is anything the epilogue could compute once per launch: see the epilogue's `tidE`.
     static_assert(!RES || NORM, "the residual form is a normalise-on-load form");
     constexpr int NLD = RES ? 4 : 2;                                          // activation loads per thread and K-step
     extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
@@ -527,11 +536,11 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
     const __amdgpu_buffer_rsrc_t srdCoef = __builtin_amdgcn_make_buffer_rsrc((void *)a.coef, 0, NORM ? a.B * a.C * 8 : 0, 0x00020000);
     constexpr int TPT = 512 / NTH;                                     // 16-byte table entries per thread (C <= 512)
     struct Tab { u32x4 v[TPT]; };
-    auto load_table = [&](int i) -> Tab {
+    auto load_table = [&](int i, int th) -> Tab {                      // th: the caller's tid
         Tab t;
 #pragma unroll
         for (int e = 0; e < TPT; ++e) {
-            const int idx = tid + e * NTH;
+            const int idx = th + e * NTH;
             unsigned off = OOB;
             if (i < myCount && idx < a.C) {
                 int m0, n0;
@@ -542,10 +551,10 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
         }
         return t;
     };
-    auto store_table = [&](int i, const Tab &t) {
+    auto store_table = [&](int i, const Tab &t, int th) {
 #pragma unroll
         for (int e = 0; e < TPT; ++e) {
-            const int idx = tid + e * NTH;
+            const int idx = th + e * NTH;
             if (idx < a.C) *reinterpret_cast<f32x4 *>(dsm + kCvCoef + (i & 1) * 8192 + idx * 16) = __builtin_bit_cast(f32x4, t.v[e]) * aS;
         }
     };
@@ -575,12 +584,12 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
     // accumulators start at the bias, in the scaled domain: bias * s * (weight scale) - powers of two, so the sum is s sW times
     // what the unscaled order of operations gives, to the bit
     const float biasMul = a.Z > 1 ? 0.f : aS * (1.f / a.uInv[0]);
-    auto init_acc = [&](int n0) {
+    auto init_acc = [&](int n0, int rh) {                               // rh: the caller's rhalf
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const f32x4 b = *reinterpret_cast<const f32x4 *>(dsm + kCvBias + (n0 + wn * 64 + j * 32 + rhalf + 8 * q) * 4);
+                const f32x4 b = *reinterpret_cast<const f32x4 *>(dsm + kCvBias + (n0 + wn * 64 + j * 32 + rh + 8 * q) * 4);
 #pragma unroll
                 for (int i = 0; i < RI; ++i)
 #pragma unroll
@@ -591,9 +600,9 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
     // ---- prologue: bias and the first two coefficient tables into LDS, steps 0 and 1 of the stream, step 0 converted
     for (int i = tid; i < a.nbn * BN; i += NTH) reinterpret_cast<float *>(dsm + kCvBias)[i] = (a.bias && i < a.N) ? a.bias[i] * biasMul : 0.f;
     if constexpr (NORM) {
-        const Tab t0 = load_table(0), t1 = load_table(1);
-        store_table(0, t0);
-        store_table(1, t1);
+        const Tab t0 = load_table(0, tid), t1 = load_table(1, tid);
+        store_table(0, t0, tid);
+        store_table(1, t1, tid);
     }
     set_w_tile(0);
     set_a_tile(0);
@@ -625,11 +634,25 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
     {
         int m0, n0;
         tile_at(0, m0, n0);
-        init_acc(n0);
+        init_acc(n0, rhalf);
     }
+    // CLK: [0] un-scale, per-lane statistics and store issue, block by block, [1] first statistics barrier, [2] fp64 sums over the
+    // staging entries, [3] second barrier, [4] the groups' writers + coefficient table of tile ti + 2, [5] bias of the next tile,
+    // [6] the counted wait of the first two K-steps behind an epilogue
+    long long cPh[7] = { 0, 0, 0, 0, 0, 0, 0 }, cT = 0;
+    auto mark = [&](int ph) __attribute__((always_inline)) {
+        if constexpr (CLK) {
+            __builtin_amdgcn_sched_barrier(0);
+            const long long t = clock64();
+            cPh[ph] += t - cT; cT = t;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
     // one K-step; FIRST: one of the first two steps of a tile that follows another one (NS stores of its epilogue are in flight).
     // The weights of step kk + 1 were issued in step kk - 2; younger at the barrier of step kk are the NLD loads and 2 DMAs of
-    // step kk - 1 and of step kk
+    // step kk - 1 and of step kk.  Behind an epilogue the NS stores lie between; of the epilogue's other memory operations the
+    // coefficient-table load is older than its stores and has landed (store_table waited for it), and the statistics' writers of
+    // wave 0, issued behind the stores, are one or two operations MORE in flight than counted: the wait is then stricter, never laxer
     auto step = [&](auto firstTag, auto parTag) __attribute__((always_inline)) {
         constexpr int sa = decltype(parTag)::value;                   // parity of the K-step
         const int next = (sc + 1) & (NWS - 1);
@@ -667,7 +690,9 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
         __builtin_amdgcn_sched_barrier(0);
         advance_conv();
         constexpr int YOUNG = 2 * NLD + 4 + (decltype(firstTag)::value ? NS : 0);
+        if constexpr (CLK && decltype(firstTag)::value) cT = clock64();
         __builtin_amdgcn_s_waitcnt(0x0070 | (YOUNG & 15) | ((YOUNG >> 4) << 14));     // + lgkmcnt(0): my activation writes are done
+        if constexpr (CLK && decltype(firstTag)::value) cPh[6] += clock64() - cT;
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         mma_col(fb[0][0], fa[0], 0);                                   // hi x hi, column block 0 ...
@@ -683,9 +708,18 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
     };
     auto epilogue = [&](int ti) __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);
+        // Everything the epilogue derives from the thread index (staging addresses, row and column offsets of the stores, the
+        // reduction's source) is the same for every tile, so the compiler used to compute it ONCE in front of the tile loop - some
+        // twenty registers that were then live across the K-loop, which has none to spare (budget: top of this function): they went to
+        // scratch and came back one by one between the output stores.  An opaque copy of the index keeps them in the epilogue,
+        // where the registers of the loop's fragments are free: a dozen integer instructions per tile.
+        int tidE = tid;
+        asm volatile("" : "+v"(tidE));
+        const int laneE = tidE & 63, frE = laneE & 31, rhalfE = (laneE >> 5) * 4;
         // ---- tile ti (swapped operands): row = lane & 31, channels (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
         int m0, n0;
         tile_at(ti, m0, n0);
+        if constexpr (CLK) cT = clock64();
         {
             const float inv = aInv * a.uInv[a.Z > 1 ? tile_z(ti) : 0];    // un-scale (exact)
 #pragma unroll
@@ -693,79 +727,54 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] *= inv;
         }
-        if (a.stats != nullptr) {
-            // GroupNorm partial sums of the output, as split_conv1x1_body: slot 0 = rows before `split`, slot 1 = the rest; per lane
-            // fp32 over its rows x 8 channels of a group, fp64 over the lanes holding the group; one writer per (image, tile, group)
-            const int nLo = m0 / a.HW;
-            const int split = (nLo + 1) * a.HW - m0;
-            f32x2 *sS = reinterpret_cast<f32x2 *>(dsm + kCvStage1);    // [4 pieces][2 slots][NTH threads]
+        // GroupNorm partial sums of the output, as split_conv1x1_body: slot 0 = rows before `split`, slot 1 = the rest; per lane fp32
+        // over its rows x 8 channels of a group, fp64 over the lanes holding the group; one writer per (image, tile, group).
+        // The per-lane sums of a 32-row block are formed right in front of the block's stores: the stores of a tile keep the CU's
+        // store path busy for some 8000 ticks in which the waves only wait to issue, the sums are ~100 VALU instructions per block
+        // and wave - so the sums of block i + 1 run while the stores of block i drain, and the two barriers and the fp64 sums
+        // behind the last block run under the drain of all of them (XL_PAIR_CLK).  Every sum keeps its order: the
+        // chain of a piece (j, gh) takes its rows' terms in the order i = 0 .. RI - 1, whether the loop over i is the outer one or not.
+        const bool doStats = a.stats != nullptr;
+        const int nLo = m0 / a.HW;
+        const int split = (nLo + 1) * a.HW - m0;
+        f32x2 *sS = reinterpret_cast<f32x2 *>(dsm + kCvStage1);        // [4 pieces][2 slots][NTH threads]
+        float s[4][2], ss[4][2];                                       // [piece j * 2 + gh][slot]
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+        for (int p = 0; p < 4; ++p)
 #pragma unroll
-                for (int gh = 0; gh < 2; ++gh) {
-                    float s[2] = { 0.f, 0.f }, ss[2] = { 0.f, 0.f };
-#pragma unroll
-                    for (int i = 0; i < RI; ++i) {
-                        const int row = wm * (32 * RI) + i * 32 + fr;
-                        float t = 0.f, tt = 0.f;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float v = acc[i][j][8 * gh + e];
-                            t += v;
-                            tt = fmaf(v, v, tt);
-                        }
-                        const bool hi = row >= split, live = m0 + row < a.M && !(a.tpi && hi);
-                        s[0] += (live && !hi) ? t : 0.f; ss[0] += (live && !hi) ? tt : 0.f;
-                        s[1] += (live && hi) ? t : 0.f;  ss[1] += (live && hi) ? tt : 0.f;
-                    }
-#pragma unroll
-                    for (int sl = 0; sl < 2; ++sl) sS[((j * 2 + gh) * 2 + sl) * NTH + tid] = f32x2{ s[sl], ss[sl] };
-                }
-            __builtin_amdgcn_s_waitcnt(0x0070 | 0xC00F);               // lgkmcnt(0)
-            __builtin_amdgcn_s_barrier();
-            {
-                const int gs = tid / PARTS, part = tid % PARTS;        // (group of the tile, slot) x PARTS parts (8 lane blocks x WM)
-                const int gt = gs >> 1, sl = gs & 1;
-                const int src = ((part >> 3) * WN + (gt >> 2)) * 64 + (part & 7) * 8;
-                const f32x2 *o = sS + ((gt & 3) * 2 + sl) * NTH + src;
-                double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s1 += (double)o[e][0]; s2 += (double)o[e][1]; }
-                double *sC = reinterpret_cast<double *>(dsm + kCvPart);
-                sC[tid * 2] = s1; sC[tid * 2 + 1] = s2;
-            }
-            __builtin_amdgcn_s_waitcnt(0x0070 | 0xC00F);
-            __builtin_amdgcn_s_barrier();
-            if (tid < 2 * (BN / 16)) {
-                const int gt = tid >> 1, sl = tid & 1;
-                const int n = nLo + sl;
-                const int firstRow = sl ? split : 0;
-                const int g = (n0 >> 4) + gt;
-                if (n < a.B && m0 + firstRow < a.M && (sl == 0 || (split < BM && !a.tpi)) && g < a.G) {
-                    const double *sC = reinterpret_cast<const double *>(dsm + kCvPart) + tid * (2 * PARTS);
-                    double s1 = 0.0, s2 = 0.0;
-                    for (int e = 0; e < PARTS; ++e) { s1 += sC[2 * e]; s2 += sC[2 * e + 1]; }
-                    const int k = a.tpi ? (m0 - n * a.HW) / BM                            // tile index within the image
-                                        : m0 / BM - (int)(((long long)n * a.HW) / BM);
-                    double *o = a.stats + (((long long)n * a.nchunks + k) * a.G + g) * 2;
-                    o[0] = s1; o[1] = s2;
-                }
-            }
-        }
-        if constexpr (NORM) {                                          // (waits for everything older than the table)
-            const Tab tab = load_table(ti + 2);
-            store_table(ti + 2, tab);
-        }
-        // (every wave issues exactly NS stores per tile - the vmcnt arithmetic of the next step counts them)
+            for (int sl = 0; sl < 2; ++sl) s[p][sl] = ss[p][sl] = 0.f;
+        Tab tab;
+        if constexpr (NORM) tab = load_table(ti + 2, tidE);            // (older than the stores: its wait does not wait for them)
+        // (every wave issues exactly NS stores per tile - the vmcnt arithmetic of the next step counts them; what else a wave issues
+        //  behind them - the statistics' writers in wave 0 - only makes that wait stricter)
         const __amdgpu_buffer_rsrc_t srdO = __builtin_amdgcn_make_buffer_rsrc((void *)(a.out + tile_z(ti) * a.zOut + (long long)m0 * a.ldOut), 0,
                                                                               tile_rows(m0) * a.ldOut * 4, 0x00020000);
         {
             // (lane_pair_exchange: 64-byte pieces, even rows then odd rows; rows past the tile fall outside the descriptor)
-            const bool odd = lane & 1;
-            const unsigned colL = (unsigned)(n0 + wn * 64 + 8 * (lane & 1) + rhalf) * 4u;
+            const bool odd = laneE & 1;
+            const unsigned colL = (unsigned)(n0 + wn * 64 + 8 * (laneE & 1) + rhalfE) * 4u;
 #pragma unroll
             for (int i = 0; i < RI; ++i) {
-                const unsigned rowOff0 = (unsigned)((wm * (32 * RI) + i * 32 + (fr & ~1)) * a.ldOut * 4) + colL;
+                if (doStats) {
+                    const int row = wm * (32 * RI) + i * 32 + frE;
+                    const bool hi = row >= split, live = m0 + row < a.M && !(a.tpi && hi);
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int gh = 0; gh < 2; ++gh) {
+                            float t = 0.f, tt = 0.f;
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) {
+                                const float v = acc[i][j][8 * gh + e];
+                                t += v;
+                                tt = fmaf(v, v, tt);
+                            }
+                            const int p = j * 2 + gh;
+                            s[p][0] += (live && !hi) ? t : 0.f; ss[p][0] += (live && !hi) ? tt : 0.f;
+                            s[p][1] += (live && hi) ? t : 0.f;  ss[p][1] += (live && hi) ? tt : 0.f;
+                        }
+                }
+                const unsigned rowOff0 = (unsigned)((wm * (32 * RI) + i * 32 + (frE & ~1)) * a.ldOut * 4) + colL;
                 const unsigned rowOff1 = rowOff0 + (unsigned)a.ldOut * 4u;
                 f32x4 old[2][4];
                 if constexpr (ACC) {                                   // (8 loads in flight per 32-row block; rows past the tile read 0)
@@ -789,12 +798,57 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
                                                                (int)(((q & 1) ? rowOff1 : rowOff0) + (unsigned)(j * 32 + (q >> 1) * 16) * 4u), 0, 0);
                     }
                 }
+                __builtin_amdgcn_sched_barrier(0);                     // (block by block: sums, then stores)
             }
         }
+        mark(0);
+        if (doStats) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int sl = 0; sl < 2; ++sl) sS[(p * 2 + sl) * NTH + tidE] = f32x2{ s[p][sl], ss[p][sl] };
+            __builtin_amdgcn_s_waitcnt(0x0070 | 0xC00F);               // lgkmcnt(0)
+            __builtin_amdgcn_s_barrier();
+            mark(1);
+            {
+                const int gs = tidE / PARTS, part = tidE % PARTS;        // (group of the tile, slot) x PARTS parts (8 lane blocks x WM)
+                const int gt = gs >> 1, sl = gs & 1;
+                const int src = ((part >> 3) * WN + (gt >> 2)) * 64 + (part & 7) * 8;
+                const f32x2 *o = sS + ((gt & 3) * 2 + sl) * NTH + src;
+                double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { s1 += (double)o[e][0]; s2 += (double)o[e][1]; }
+                double *sC = reinterpret_cast<double *>(dsm + kCvPart);
+                sC[tidE * 2] = s1; sC[tidE * 2 + 1] = s2;
+            }
+            mark(2);
+            __builtin_amdgcn_s_waitcnt(0x0070 | 0xC00F);
+            __builtin_amdgcn_s_barrier();
+            mark(3);
+            if (tidE < 2 * (BN / 16)) {
+                const int gt = tidE >> 1, sl = tidE & 1;
+                const int n = nLo + sl;
+                const int firstRow = sl ? split : 0;
+                const int g = (n0 >> 4) + gt;
+                if (n < a.B && m0 + firstRow < a.M && (sl == 0 || (split < BM && !a.tpi)) && g < a.G) {
+                    const double *sC = reinterpret_cast<const double *>(dsm + kCvPart) + tidE * (2 * PARTS);
+                    double s1 = 0.0, s2 = 0.0;
+#pragma unroll 4                                                   // (all PARTS reads at once are 64 registers)
+                    for (int e = 0; e < PARTS; ++e) { s1 += sC[2 * e]; s2 += sC[2 * e + 1]; }
+                    const int k = a.tpi ? (m0 - n * a.HW) / BM                            // tile index within the image
+                                        : m0 / BM - (int)(((long long)n * a.HW) / BM);
+                    double *o = a.stats + (((long long)n * a.nchunks + k) * a.G + g) * 2;
+                    o[0] = s1; o[1] = s2;
+                }
+            }
+        }
+        if constexpr (NORM) store_table(ti + 2, tab, tidE);
+        mark(4);
         if (ti + 1 < myCount) {
             tile_at(ti + 1, m0, n0);
-            init_acc(n0);
+            init_acc(n0, rhalfE);
         }
+        mark(5);
         __builtin_amdgcn_sched_barrier(0);
     };
     auto tile_steps = [&](auto firstTag) __attribute__((always_inline)) {
@@ -811,6 +865,14 @@ __device__ __forceinline__ void pair_conv1x1_body(const PairConvArgs &a)
         tile_steps(std::true_type{});
     }
     epilogue(myCount - 1);
+    if constexpr (CLK) {
+        if (a.clk && lane == 0) {
+            long long *c = a.clk + ((long long)blockIdx.x * NW + wave) * 8;
+#pragma unroll
+            for (int e = 0; e < 7; ++e) c[e] = cPh[e];
+            c[7] = myCount;
+        }
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);                             // vmcnt(0)
 }
 
@@ -826,6 +888,14 @@ __global__ __launch_bounds__(64 * NW)
 void pair_conv1x1_res_kernel(PairConvArgs a)
 {
     pair_conv1x1_body<true, false, NW, 0, BN, true>(a);
+}
+
+// XL_PAIR_CLK: the three forms of the flagship plan (plain, NORM, residual; 8 waves, 256 x 256) with the epilogue's phase clocks
+template <bool NORM, bool RES>
+__global__ __launch_bounds__(512)
+void pair_conv1x1_clk_kernel(PairConvArgs a)
+{
+    pair_conv1x1_body<NORM, false, 8, 0, 256, RES, true>(a);
 }
 
 }  // namespace
@@ -888,6 +958,39 @@ static int xl_run_pair_gemm(const xl_op &op, hipStream_t st)
 }
 
 
+// XL_PAIR_CLK (measurement only, synchronises the stream): one 256 x 256 launch with the phase clocks, then their means per wave
+// and tile on stderr - the counterpart of the [pair clk] line of xl_run_pair_gemm
+static int launch_pair_conv1x1_clk(const xl_op &op, PairConvArgs a, bool norm, bool resid, size_t lds, int grid, hipStream_t st)
+{
+    const void *fn = resid ? reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<true, true>)
+                   : norm ? reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<true, false>)
+                          : reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<false, false>);
+    static XlLdsLimit configured[3];
+    if (configured[resid ? 2 : norm ? 1 : 0].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
+    const size_t n = (size_t)64 * grid;
+    if (hipMalloc(&a.clk, sizeof(long long) * n) != hipSuccess) return XL_ERR_HIP;
+    if (hipMemsetAsync(a.clk, 0, sizeof(long long) * n, st) != hipSuccess) { (void)hipFree(a.clk); return XL_ERR_HIP; }
+    if (resid) hipLaunchKernelGGL((pair_conv1x1_clk_kernel<true, true>), dim3(grid), dim3(512), lds, st, a);
+    else if (norm) hipLaunchKernelGGL((pair_conv1x1_clk_kernel<true, false>), dim3(grid), dim3(512), lds, st, a);
+    else hipLaunchKernelGGL((pair_conv1x1_clk_kernel<false, false>), dim3(grid), dim3(512), lds, st, a);
+    std::vector<long long> h(n);
+    if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), a.clk, sizeof(long long) * n, hipMemcpyDeviceToHost) == hipSuccess) {
+        double ph[7] = { 0 }, tiles = 0, follow = 0;
+        for (size_t w = 0; w < n / 8; ++w) {
+            for (int c = 0; c < 7; ++c) ph[c] += (double)h[8 * w + c];
+            tiles += (double)h[8 * w + 7];
+            follow += h[8 * w + 7] > 0 ? (double)(h[8 * w + 7] - 1) : 0.0;
+        }
+        if (tiles > 0)
+            fprintf(stderr, "[pair1x1 clk] %s %d -> %d, M %d, ticks per wave and tile: un-scale + lane statistics + store issue %.0f, barrier 1 %.0f, fp64 staging sums %.0f, "
+                            "barrier 2 %.0f, writers + table %.0f, bias of the next tile %.0f (epilogue %.0f); wait of the first two K-steps behind it %.0f\n",
+                    resid ? "residual" : norm ? "NORM" : "plain", op.Cin, op.Cout, a.M, ph[0] / tiles, ph[1] / tiles, ph[2] / tiles, ph[3] / tiles, ph[4] / tiles,
+                    ph[5] / tiles, (ph[0] + ph[1] + ph[2] + ph[3] + ph[4] + ph[5]) / tiles, follow > 0 ? ph[6] / follow : 0.0);
+    }
+    (void)hipFree(a.clk);
+    return XL_OK;
+}
+
 // fp32 activations: the launcher of csrc/xl_gemm_split.hip's 1x1 / XL_CONV_SPLIT_ACT forms with the pair kernels (same tile forms,
 // same statistics rows: op.reserved_i as there)
 template <int NW, int BN>
@@ -916,6 +1019,10 @@ static int launch_pair_conv1x1(const xl_op &op, PairConvArgs a, bool norm, int Z
     a.tile0 = tileFrom; a.ntiles = nwg;
     int grid = 256;                                   // persistent: one workgroup per CU
     if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
+    if constexpr (NW == 8 && BN == 256) {
+        static const bool clkDbg = getenv("XL_PAIR_CLK") != nullptr;
+        if (clkDbg && !accumulate && Z == 1) return launch_pair_conv1x1_clk(op, a, norm, resid, lds, grid, st);
+    }
     if (accumulate) hipLaunchKernelGGL((pair_conv1x1_kernel<false, true, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
     else if (resid) hipLaunchKernelGGL((pair_conv1x1_res_kernel<NW, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
     else if (norm) hipLaunchKernelGGL((pair_conv1x1_kernel<true, false, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
@@ -954,6 +1061,7 @@ static int xl_run_pair_conv1x1(const xl_op &op, hipStream_t st)
     a.aScale = (const float *)op.scale;
     a.amaxShift = (op.flags & XL_CONV_PAIR_AMAX) ? (Z > 1 ? 8 : 0) : -1;
     a.var = 0;
+    a.clk = nullptr;
     if (op.flags & XL_CONV_NORM_ADD) {
         if (!norm || !(op.flags & XL_CONV_NORM_RELU) || !op.aux || op.ld_aux < op.Cin || (op.ld_aux & 3) || ((uintptr_t)op.aux & 15) || Z > 1 ||
             256LL * op.ld_aux * 4 >= 0x7fffffffLL) return XL_ERR_ARG;
