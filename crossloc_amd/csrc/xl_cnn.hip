@@ -4,14 +4,21 @@
 //
 //   XL_OP_CONV1                          xl_conv1.hip       3x3 s1 on the NCHW image -> NHWC: direct, fused and matrix-pipe forms
 //   XL_OP_CONV                           xl_igemm.hip       the dispatch; implicit GEMM on exact-fp32 MFMA (fallbacks, data gradients)
-//                                        xl_gemm_split.hip, xl_gemm_pair.hip      1x1 and Winograd GEMMs on the bf16 / fp16 matrix pipe
+//                                        xl_gemm_split.hip, xl_gemm_pair.hip      1x1 and Winograd GEMMs on the bf16 / fp16 matrix pipe;
+//                                                                                 one launcher of the 1x1 forms (xl_conv1x1.h)
 //                                        xl_stem_split.hip, xl_stem_pair.hip      the 3x3 stride-2 stem convolutions on those pipes:
 //                                                                                 one loop (xl_stem_s2.h, xl_stem_s2_body.h), two forms
 //   XL_OP_STEM12, XL_OP_S2_DGRAD         xl_stem_fused.hip, xl_stem_dgrad.hip
 //   XL_OP_WINO_IN, XL_OP_WINO_OUT        xl_wino.hip        Winograd F(2x2), F(4x4), F(6x6) input / output transforms
 //   XL_OP_GN_STATS, _FINAL, _APPLY       xl_gn.hip          GroupNorm: fp64 partial sums, per-channel scale / shift, apply
 //   XL_OP_HEAD, XL_OP_DUC_HEAD           xl_gn.hip          fc3 + mean offset + exp(hardtanh), NCHW out
-//   every other type (the backward ops)  xl_cnn_bwd.hip     with xl_wgrad_split.hip, xl_wgrad_pair.hip (one loop: xl_wgrad.h, xl_wgrad_body.h)
+//   XL_OP_WGRAD                          xl_wgrad_f32.hip   the dispatch; exact-fp32 split-K kernel and the reduce over the splits
+//                                        xl_wgrad_split.hip, xl_wgrad_pair.hip    the products on the matrix pipes (one loop: xl_wgrad.h, xl_wgrad_body.h)
+//   XL_OP_WINO_DY, XL_OP_WINO_WFINAL     xl_wgrad_f32.hip   the transforms around the batched weight-gradient products of a Winograd layer
+//   XL_OP_GNB_* (five)                   xl_gn_bwd.hip      GroupNorm backward fused with the forward epilogue; d gamma / d beta / d bias
+//   XL_OP_HEAD_BWD, XL_OP_DUC_HEAD_BWD   xl_head_bwd.hip
+//   XL_OP_CONV1_WGRAD                    xl_conv1.hip       behind the forward forms
+//   XL_OP_FILL0                          here: a hipMemsetAsync
 //
 // The weight packs of all of them are in xl_pack.hip.  fp32 end to end: the MFMA forms are bitwise fmaf chains or exact
 // splits, so parity with the fp32 reference is at summation-order level.
@@ -48,7 +55,21 @@ int run_op(const xl_op &op, hipStream_t st)
         case XL_OP_GN_FINAL: return xl_run_gn_final(op, st);
         case XL_OP_HEAD: return xl_run_head(op, st);
         case XL_OP_DUC_HEAD: return xl_run_duc_head(op, st);
-        default: return xl_run_bwd_op(op, st);
+        case XL_OP_FILL0:                                 // `Cin` bytes at `out` set to zero on the stream
+            if (!op.out || op.Cin < 1) return XL_ERR_ARG;
+            return hipMemsetAsync(op.out, 0, (size_t)op.Cin, st) == hipSuccess ? XL_OK : XL_ERR_HIP;
+        case XL_OP_WGRAD: return xl_run_wgrad(op, st);
+        case XL_OP_WINO_DY: return xl_run_wino_dy(op, st);
+        case XL_OP_WINO_WFINAL: return xl_run_wino_wfinal(op, st);
+        case XL_OP_GNB_STATS:
+        case XL_OP_GNB_FINAL:
+        case XL_OP_GNB_APPLY: return xl_run_gnb(op, st);
+        case XL_OP_GNB_PARAMS: return xl_run_gnb_params(op, st);
+        case XL_OP_GNB_PARAMS_LIST: return xl_run_gnb_params_list(op, st);
+        case XL_OP_HEAD_BWD: return xl_run_head_bwd(op, st);
+        case XL_OP_DUC_HEAD_BWD: return xl_run_duc_head_bwd(op, st);
+        case XL_OP_CONV1_WGRAD: return xl_run_conv1_wgrad(op, st);
+        default: return XL_ERR_UNSUPPORTED;
     }
 }
 

@@ -1,5 +1,6 @@
 // xl_conv1.hip — XL_OP_CONV1, the first layer: 3x3 s1 on the 3-channel NCHW image -> NHWC.  Three forms: the direct kernel
 // (raw output), and the two-pass inference form (statistics only / conv + GroupNorm + ReLU) on the VALU and on the bf16 matrix pipe.
+// Behind them XL_OP_CONV1_WGRAD, the layer's weight / bias gradient.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -367,3 +368,201 @@ int xl_run_conv1(const xl_op &op, hipStream_t st)
                        op.B, op.Cin, op.Hi, op.Wi, op.Cout, op.ld_out);
     return XL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- XL_OP_CONV1_WGRAD
+
+namespace {
+
+// dW[o][c][ky][kx] = sum dY[n,y,x,o] * img[n,c,y+ky-1,x+kx-1]; db[o] = sum dY.  Cout = 32.
+// Thread = (4 consecutive output channels og, pixel lane pl of 32): per pixel one 16-byte dY load (the 8 threads of a
+// pixel read its 128 contiguous bytes) and 9 ds_read_b128 of the image taps feed 108 FMAs - 12 per LDS read; with one
+// output channel per thread (3 per read) the kernel sat on the LDS pipe at 6x its HBM time.
+// A block walks `rowsPerBlock` output rows of one image two at a time; the 4 image rows (with halo, channels padded
+// to a float4) they touch are staged in LDS.  partial [gridDim.y * gridDim.x][28][32]
+// FOLD (round 5): `dy` is the gradient w.r.t. the GroupNorm(+ReLU) OUTPUT of conv1 and `x` conv1's raw output: the apply pass of
+// the GroupNorm backward (dx = k1 dv - k2 - xhat k3, the arithmetic of gnb_apply_kernel - same operations, same order, same bits)
+// runs on load, from the forward table `fco` and the coefficients `bco` XL_OP_GNB_FINAL left.  conv1 has no data gradient: its dx
+// had this kernel as only reader, and the apply pass read and wrote 2.1 GB for it at batch 16.
+template <bool FOLD>
+__global__ __launch_bounds__(256)
+void conv1_wgrad_kernel(const float *__restrict__ img, const float *__restrict__ dy, float *__restrict__ partial,
+                        int B, int Cin, int H, int W, int ldY, int rowsPerBlock,
+                        const float *__restrict__ x, int ldX, const float *__restrict__ fco, const float *__restrict__ bco, int reluIn)
+{
+    constexpr int R = 2, CO = 32;
+    extern __shared__ __attribute__((aligned(16))) float sDyn[];
+    f32x4 *sImg = reinterpret_cast<f32x4 *>(sDyn);                 // [(R+2)][W+2]
+    float *sRed = sDyn;                                            // [4 waves][32][28], reuses the tile after the loop
+    const int og = threadIdx.x & 7, pl = threadIdx.x >> 3;
+    const int n = blockIdx.y;
+    const long long HW = (long long)H * W;
+    const int yBeg = blockIdx.x * rowsPerBlock;
+    int yEnd = yBeg + rowsPerBlock; if (yEnd > H) yEnd = H;
+    f32x4 acc[28];                                                 // [tap*3 + c] (27: bias) x 4 output channels
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
+    f32x4 kMu, kRs, kSc, kSh, k1, k2, k3;                          // FOLD: this thread's four channels of image n
+    if constexpr (FOLD) {
+        const float *scsh = fco + ((long long)n * CO + 4 * og) * 2, *murs = fco + (((long long)B + n) * CO + 4 * og) * 2;
+        const float *bo = bco + ((long long)n * CO + 4 * og) * 3;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            kSc[j] = scsh[2 * j]; kSh[j] = scsh[2 * j + 1]; kMu[j] = murs[2 * j]; kRs[j] = murs[2 * j + 1];
+            k1[j] = bo[3 * j]; k2[j] = bo[3 * j + 1]; k3[j] = bo[3 * j + 2];
+        }
+    }
+    auto grad_of = [&](const f32x4 &d4, const f32x4 &xv) {
+        if constexpr (!FOLD) return d4;
+        f32x4 dx;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = xv[j] * kSc[j] + kSh[j];
+            const float xh = (xv[j] - kMu[j]) * kRs[j];
+            const float dv = (reluIn && !(v > 0.f)) ? 0.f : d4[j];
+            dx[j] = k1[j] * dv - k2[j] - xh * k3[j];
+        }
+        return dx;
+    };
+    const int W2 = W + 2;
+    for (int y0 = yBeg; y0 < yEnd; y0 += R) {
+        __syncthreads();
+        // staging in batches of 4 entries per thread: all loads of a batch are in flight before the first LDS write
+        // (clamped addresses + a select instead of a branch around the loads)
+        for (int base = threadIdx.x; base < (R + 2) * W2; base += 4 * 256) {
+            f32x4 v[4];
+            bool ok[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + u * 256;
+                const int r = idx / W2, xx = idx - r * W2 - 1;
+                const int iy = y0 - 1 + r;
+                ok[u] = (idx < (R + 2) * W2) & ((unsigned)iy < (unsigned)H) & ((unsigned)xx < (unsigned)W);
+                const int iyc = min(max(iy, 0), H - 1), xc = min(max(xx, 0), W - 1);
+                const float *q = img + (long long)n * Cin * HW + (long long)iyc * W + xc;
+                v[u] = f32x4{ q[0], Cin > 1 ? q[HW] : 0.f, Cin > 1 ? q[2 * HW] : 0.f, 0.f };
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int idx = base + u * 256;
+                if (idx < (R + 2) * W2) sImg[idx] = ok[u] ? v[u] : f32x4{ 0.f, 0.f, 0.f, 0.f };
+            }
+        }
+        __syncthreads();
+        const int rows = (yEnd - y0 < R) ? (yEnd - y0) : R;
+        // rows y0.. are consecutive in memory: pixel p of the step is dyRow + p*ldY.  The load of the next pixel is
+        // issued before the FMAs of the current one (one HBM round trip per iteration otherwise).
+        const float *dyRow = dy + ((long long)n * H + y0) * W * ldY + 4 * og;
+        const float *xRow = FOLD ? x + ((long long)n * H + y0) * W * ldX + 4 * og : nullptr;
+        const int np = rows * W;
+        f32x4 gNext = f32x4{ 0.f, 0.f, 0.f, 0.f }, xNext = f32x4{ 0.f, 0.f, 0.f, 0.f };
+        if (pl < np) {
+            gNext = *reinterpret_cast<const f32x4 *>(dyRow + (long long)pl * ldY);
+            if constexpr (FOLD) xNext = *reinterpret_cast<const f32x4 *>(xRow + (long long)pl * ldX);
+        }
+        for (int p = pl; p < np; p += 32) {
+            const int ry = p / W, xcol = p - ry * W;
+            const f32x4 g = grad_of(gNext, xNext);
+            if (p + 32 < np) {
+                gNext = *reinterpret_cast<const f32x4 *>(dyRow + (long long)(p + 32) * ldY);
+                if constexpr (FOLD) xNext = *reinterpret_cast<const f32x4 *>(xRow + (long long)(p + 32) * ldX);
+            }
+            acc[27] += g;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) {
+                const f32x4 *row = sImg + (ry + ky) * W2 + xcol;
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const f32x4 v = row[kx];
+                    acc[(ky * 3 + kx) * 3 + 0] += g * v.x;
+                    acc[(ky * 3 + kx) * 3 + 1] += g * v.y;
+                    acc[(ky * 3 + kx) * 3 + 2] += g * v.z;
+                }
+            }
+        }
+    }
+    // fixed-order reduction: the 8 pixel lanes of a wave (lane bits 3..5), then the 4 waves through LDS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 28; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float v = acc[k][e];
+            v += __shfl_xor(v, 8);
+            v += __shfl_xor(v, 16);
+            v += __shfl_xor(v, 32);
+            acc[k][e] = v;
+        }
+    __syncthreads();
+    if (lane < 8) {
+#pragma unroll
+        for (int k = 0; k < 28; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sRed[(wave * CO + 4 * og + e) * 28 + k] = acc[k][e];
+    }
+    __syncthreads();
+    const long long blk = (long long)blockIdx.y * gridDim.x + blockIdx.x;
+    for (int i = threadIdx.x; i < 28 * CO; i += 256) {
+        const int k = i / CO, o = i - k * CO;
+        float s = 0.f;
+        for (int w = 0; w < 4; ++w) s += sRed[(w * CO + o) * 28 + k];
+        partial[(blk * 28 + k) * CO + o] = s;
+    }
+}
+
+// out: dW OIHW [Cout][Cin][3][3] and db[Cout] from the block partials.  grid (28): one tap/channel slot k per block;
+// 256 threads = 32 output channels x 8 parts, each part sums a contiguous eighth of the blocks (4 loads in flight), the
+// eighths are added in order.  (One thread per output walking all partials serially was a 0.5 ms chain of loads.)
+__global__ __launch_bounds__(256)
+void conv1_wgrad_reduce_kernel(const float *__restrict__ partial, float *__restrict__ dw, float *__restrict__ db,
+                               int blocks, int Cin)
+{
+    constexpr int CO = 32;
+    __shared__ double sP[8 * CO];
+    const int k = blockIdx.x, o = threadIdx.x & 31, part = threadIdx.x >> 5;
+    const int per = (blocks + 7) >> 3;
+    const int b0 = part * per;
+    int b1 = b0 + per; if (b1 > blocks) b1 = blocks;
+    double s = 0.0;
+#pragma unroll 4
+    for (int b = b0; b < b1; ++b) s += (double)partial[((long long)b * 28 + k) * CO + o];
+    sP[part * CO + o] = s;
+    __syncthreads();
+    if (part != 0) return;
+    double t = 0.0;
+    for (int q = 0; q < 8; ++q) t += sP[q * CO + o];
+    if (k == 27) { db[o] = (float)t; return; }
+    const int tap = k / 3, c = k - tap * 3;
+    if (c < Cin) dw[((long long)o * Cin + c) * 9 + tap] = (float)t;
+}
+
+}  // namespace
+
+int xl_run_conv1_wgrad(const xl_op &op, hipStream_t st)
+{
+    if (op.Cout != 32 || op.Cin > 3) return XL_ERR_UNSUPPORTED;
+    const int rowsPerBlock = op.reserved_i > 0 ? op.reserved_i : 16;     // scratch: B*ceil(Hi/rows)*28*Cout floats
+    if (op.ld_aux % 4 != 0) return XL_ERR_ARG;
+    const int rb = (op.Hi + rowsPerBlock - 1) / rowsPerBlock;
+    const int blocks = rb * op.B;
+    size_t lds = sizeof(float) * (size_t)4 * (op.Wi + 2) * 4;
+    if (lds < sizeof(float) * (size_t)4 * op.Cout * 28) lds = sizeof(float) * (size_t)4 * op.Cout * 28;
+    // the staged rows take 64 * (Wi + 2) bytes: up to the 160 KiB of a CU (frames up to 2558 pixels wide; the training
+    // augmentation's largest scale, 3/2 of a 720-wide frame, needs 68 KiB)
+    if (lds > 160 * 1024) return XL_ERR_UNSUPPORTED;
+    // fold: GroupNorm-backward apply on load: aux2 = conv1's raw output (ld_in), w = the layer's forward table (XL_OP_GN_FINAL with
+    // out2), bias = the coefficients [B][Cout][3] of XL_OP_GNB_FINAL, flags = the GroupNorm's XL_GN_RELU_IN; the plain form gets zeros
+    const bool fold = op.aux2 != nullptr;
+    const auto kernel = fold ? conv1_wgrad_kernel<true> : conv1_wgrad_kernel<false>;
+    if (lds > 64 * 1024) {
+        static XlLdsLimit configured[2];     // per instantiation, tracked per device
+        if (configured[fold].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
+    }
+    if (fold && (!op.w || !op.bias || op.ld_in % 4 != 0)) return XL_ERR_ARG;
+    hipLaunchKernelGGL(kernel, dim3(rb, op.B), dim3(256), lds, st, (const float *)op.in, (const float *)op.aux, (float *)op.stats2, op.B, op.Cin,
+                       op.Hi, op.Wi, op.ld_aux, rowsPerBlock, (const float *)op.aux2, fold ? op.ld_in : 0, (const float *)(fold ? op.w : nullptr),
+                       (const float *)(fold ? op.bias : nullptr), (fold && (op.flags & XL_GN_RELU_IN)) ? 1 : 0);
+    hipLaunchKernelGGL(conv1_wgrad_reduce_kernel, dim3(28), dim3(256), 0, st,
+                       (const float *)op.stats2, (float *)op.out, (float *)op.out2, blocks, op.Cin);
+    return XL_OK;
+}
+

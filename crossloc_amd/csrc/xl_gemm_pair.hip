@@ -38,6 +38,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "xl_conv1x1.h"
 #include "xl_launch.h"
 #include "xl_operand_math.h"
 
@@ -934,9 +935,7 @@ static int xl_run_pair_gemm(const xl_op &op, hipStream_t st)
     static XlLdsLimit configured[4];
     const int slot = pp ? 3 : dbg ? 2 : op.Cin == 512 ? 1 : 0;
     if (configured[slot].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
-    const int nwg = a.nbm * a.nbn * Z;
-    int grid = pp ? 512 : 256;
-    if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
+    const int grid = xl_persistent_grid(a.nbm * a.nbn * Z, pp ? 512 : 256);
     static const bool clkDbg = getenv("XL_PAIR_CLK") != nullptr;
     if (clkDbg && hipMalloc(&a.clk, sizeof(long long) * 64 * grid) != hipSuccess) return XL_ERR_HIP;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(pp ? 256 : 512), lds, st, a);
@@ -962,17 +961,14 @@ static int xl_run_pair_gemm(const xl_op &op, hipStream_t st)
 // and tile on stderr - the counterpart of the [pair clk] line of xl_run_pair_gemm
 static int launch_pair_conv1x1_clk(const xl_op &op, PairConvArgs a, bool norm, bool resid, size_t lds, int grid, hipStream_t st)
 {
-    const void *fn = resid ? reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<true, true>)
-                   : norm ? reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<true, false>)
-                          : reinterpret_cast<const void *>(pair_conv1x1_clk_kernel<false, false>);
+    void (*const kernel)(PairConvArgs) = resid ? pair_conv1x1_clk_kernel<true, true> : norm ? pair_conv1x1_clk_kernel<true, false>
+                                                                                            : pair_conv1x1_clk_kernel<false, false>;
     static XlLdsLimit configured[3];
-    if (configured[resid ? 2 : norm ? 1 : 0].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
+    if (configured[resid ? 2 : norm ? 1 : 0].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
     const size_t n = (size_t)64 * grid;
     if (hipMalloc(&a.clk, sizeof(long long) * n) != hipSuccess) return XL_ERR_HIP;
     if (hipMemsetAsync(a.clk, 0, sizeof(long long) * n, st) != hipSuccess) { (void)hipFree(a.clk); return XL_ERR_HIP; }
-    if (resid) hipLaunchKernelGGL((pair_conv1x1_clk_kernel<true, true>), dim3(grid), dim3(512), lds, st, a);
-    else if (norm) hipLaunchKernelGGL((pair_conv1x1_clk_kernel<true, false>), dim3(grid), dim3(512), lds, st, a);
-    else hipLaunchKernelGGL((pair_conv1x1_clk_kernel<false, false>), dim3(grid), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, st, a);
     std::vector<long long> h(n);
     if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), a.clk, sizeof(long long) * n, hipMemcpyDeviceToHost) == hipSuccess) {
         double ph[7] = { 0 }, tiles = 0, follow = 0;
@@ -991,103 +987,34 @@ static int launch_pair_conv1x1_clk(const xl_op &op, PairConvArgs a, bool norm, b
     return XL_OK;
 }
 
-// fp32 activations: the launcher of csrc/xl_gemm_split.hip's 1x1 / XL_CONV_SPLIT_ACT forms with the pair kernels (same tile forms,
-// same statistics rows: op.reserved_i as there)
-template <int NW, int BN>
-static int launch_pair_conv1x1(const xl_op &op, PairConvArgs a, bool norm, int Z, hipStream_t st, int tileFrom = 0, int tileCount = -1)
-{
-    constexpr int BM = 32 * NW;
-    const long long M = a.M;
-    const bool perImage = op.reserved_i < 0;         // tiles start at image boundaries (reserved_i = -256 / -128)
-    a.tpi = perImage ? (a.HW + BM - 1) / BM : 0;
-    a.nbm = perImage ? op.B * a.tpi : (int)((M + BM - 1) / BM);
-    a.nbn = (op.Cout + BN - 1) / BN;
-    const size_t lds = 4 * BN * kPB + BM * kPA + 64 * (64 * NW) + 16 * (64 * NW) + 16384 + 4096 + 1024;
-    const bool accumulate = (op.flags & XL_CONV_ACCUMULATE) != 0;
-    const bool resid = norm && a.res != nullptr;
-    const bool dominant = Z > 1 && op.Cin == 512 && op.Cout == 512 && !accumulate && !norm;
-    const void *fn = accumulate ? reinterpret_cast<const void *>(pair_conv1x1_kernel<false, true, NW, 0, BN>)
-                   : resid ? reinterpret_cast<const void *>(pair_conv1x1_res_kernel<NW, BN>)
-                   : norm ? reinterpret_cast<const void *>(pair_conv1x1_kernel<true, false, NW, 0, BN>)
-                   : dominant ? reinterpret_cast<const void *>(pair_conv1x1_kernel<false, false, NW, 2, BN>)
-                   : Z > 1 ? reinterpret_cast<const void *>(pair_conv1x1_kernel<false, false, NW, 1, BN>)
-                           : reinterpret_cast<const void *>(pair_conv1x1_kernel<false, false, NW, 0, BN>);
-    static XlLdsLimit configured[6];
-    const int slot = accumulate ? 2 : (resid ? 5 : (norm ? 1 : (dominant ? 4 : (Z > 1 ? 3 : 0))));
-    if (configured[slot].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
-    const int nwg = tileCount < 0 ? a.nbm * a.nbn * Z : tileCount;
-    a.tile0 = tileFrom; a.ntiles = nwg;
-    int grid = 256;                                   // persistent: one workgroup per CU
-    if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
-    if constexpr (NW == 8 && BN == 256) {
-        static const bool clkDbg = getenv("XL_PAIR_CLK") != nullptr;
-        if (clkDbg && !accumulate && Z == 1) return launch_pair_conv1x1_clk(op, a, norm, resid, lds, grid, st);
-    }
-    if (accumulate) hipLaunchKernelGGL((pair_conv1x1_kernel<false, true, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (resid) hipLaunchKernelGGL((pair_conv1x1_res_kernel<NW, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (norm) hipLaunchKernelGGL((pair_conv1x1_kernel<true, false, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (dominant) hipLaunchKernelGGL((pair_conv1x1_kernel<false, false, NW, 2, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (Z > 1) hipLaunchKernelGGL((pair_conv1x1_kernel<false, false, NW, 1, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else hipLaunchKernelGGL((pair_conv1x1_kernel<false, false, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    return XL_OK;
-}
+// fp32 activations: the 1x1 / XL_CONV_SPLIT_ACT forms with the pair kernels, through the launcher of csrc/xl_conv1x1.h (same tile forms and
+// statistics rows as csrc/xl_gemm_split.hip).  w = [Z][Cout][Cin/16][2][16] fp16 + 2 Z floats, scale = {s, 1 / s} of the activations.
+namespace {
 
-static int xl_run_pair_conv1x1(const xl_op &op, hipStream_t st)
-{
-    const long long M = (long long)op.B * op.Ho * op.Wo;
-    const int HW = op.Ho * op.Wo;
-    const bool norm = (op.flags & XL_CONV_NORM_IN) != 0;
-    const bool small = op.reserved_i == 128 || op.reserved_i == -128;
-    const int BM = small ? 128 : 256;
-    const int Z = op.nchunks2 > 1 ? op.nchunks2 : 1;
-    if (Z > 1 && (op.bias || op.stats || norm || op.reserved_i < 0 || op.ld_in != op.Cin || op.ld_out != op.Cout)) return XL_ERR_ARG;
-    if (op.ksize != 1 || op.stride != 1 || op.Cin % 32 != 0 || op.Cout % 256 != 0 || op.Cout > 1024 || op.ld_in < op.Cin ||
-        op.ld_out < op.Cout || (op.ld_in & 3) || (op.ld_out & 3) || ((op.flags & XL_CONV_ACCUMULATE) && (norm || Z > 1 || op.stats)) || !op.in ||
-        !op.w || !op.out || !op.scale || (((uintptr_t)op.in | (uintptr_t)op.out | (uintptr_t)op.w) & 15) || M >= 0x7fffffffLL ||
-        (long long)op.Cout * op.Cin * 4 >= 0x7fffffffLL || 256LL * op.ld_in * 4 >= 0x7fffffffLL || 256LL * op.ld_out * 4 >= 0x7fffffffLL)
-        return XL_ERR_ARG;
-    if (norm && (!op.aux2 || op.Cin > 512 || HW < BM)) return XL_ERR_ARG;
-    if (op.stats && (op.groups <= 0 || op.Cout != 16 * op.groups || HW < BM || op.nchunks < (HW + BM - 1) / BM + 1)) return XL_ERR_ARG;
-    if (op.reserved_i < 0 && HW < BM) return XL_ERR_ARG;
-    PairConvArgs a;
-    a.in = (const float *)op.in; a.u = (const unsigned char *)op.w; a.bias = (const float *)op.bias; a.out = (float *)op.out;
-    a.coef = (const float *)op.aux2;
-    a.normLo = (op.flags & XL_CONV_NORM_RELU) ? 0.f : -__builtin_inff();
-    a.stats = (double *)op.stats; a.HW = HW; a.G = op.groups; a.nchunks = op.nchunks; a.B = op.B;
-    a.M = (int)M; a.C = op.Cin; a.N = op.Cout; a.ldIn = op.ld_in; a.ldOut = op.ld_out;
-    a.Z = Z; a.zIn = M * op.ld_in; a.zOut = M * op.ld_out;
-    a.res = nullptr; a.ldRes = 0;
-    a.uInv = reinterpret_cast<const float *>(a.u + (long long)Z * op.Cout * op.Cin * 4) + Z;
-    a.aScale = (const float *)op.scale;
-    a.amaxShift = (op.flags & XL_CONV_PAIR_AMAX) ? (Z > 1 ? 8 : 0) : -1;
-    a.var = 0;
-    a.clk = nullptr;
-    if (op.flags & XL_CONV_NORM_ADD) {
-        if (!norm || !(op.flags & XL_CONV_NORM_RELU) || !op.aux || op.ld_aux < op.Cin || (op.ld_aux & 3) || ((uintptr_t)op.aux & 15) || Z > 1 ||
-            256LL * op.ld_aux * 4 >= 0x7fffffffLL) return XL_ERR_ARG;
-        a.res = (const float *)op.aux; a.ldRes = op.ld_aux;
+struct PairConv1x1 {
+    using Args = PairConvArgs;
+    static constexpr int kWeightBytes = 4;
+    static constexpr bool kScale = true, kClk = true;
+    template <int NW, int BN> static constexpr size_t lds_bytes() { return 4 * BN * kPB + (32 * NW) * kPA + 64 * (64 * NW) + 16 * (64 * NW) + 16384 + 4096 + 1024; }
+    static void fill_extra(const xl_op &op, Args &a, int Z)
+    {
+        a.uInv = reinterpret_cast<const float *>(a.u + (long long)Z * op.Cout * op.Cin * 4) + Z;
+        a.aScale = (const float *)op.scale;
+        a.amaxShift = (op.flags & XL_CONV_PAIR_AMAX) ? (Z > 1 ? 8 : 0) : -1;
+        a.var = 0;
+        a.clk = nullptr;
     }
-    if (op.flags & XL_CONV_M_TILE_MAJOR) {
-        if (Z < 2 || op.ld_out != op.Cout || 256LL * Z * op.Cout * 4 >= 0x7fffffffLL) return XL_ERR_ARG;
-        a.zOut = op.Cout; a.ldOut = Z * op.Cout;
-    }
-    a.tpi = 0; a.nbm = 0; a.nbn = 0;
-    if (small) return launch_pair_conv1x1<4, 128>(op, a, norm, Z, st);
-    if (op.reserved_i == 192) return launch_pair_conv1x1<8, 128>(op, a, norm, Z, st);
-    if (op.reserved_i == 384) {
-        const int nbig = (int)((M + 255) / 256) * (op.Cout / 256) * Z, full = nbig / 256 * 256, rem = nbig - full;
-        if (full > 0 && rem > 0 && 2 * rem <= 256) {
-            const int rc = launch_pair_conv1x1<8, 256>(op, a, norm, Z, st, 0, full);
-            return rc != XL_OK ? rc : launch_pair_conv1x1<8, 128>(op, a, norm, Z, st, 2 * full, 2 * rem);
-        }
-        if (full == 0 && 2 * rem <= 256) return launch_pair_conv1x1<8, 128>(op, a, norm, Z, st);
-    }
-    return launch_pair_conv1x1<8, 256>(op, a, norm, Z, st);
-}
+    template <bool NORM, bool ACC, int NW, int ZB, int BN> static constexpr auto kernel = pair_conv1x1_kernel<NORM, ACC, NW, ZB, BN>;
+    template <int NW, int BN> static constexpr auto res_kernel = pair_conv1x1_res_kernel<NW, BN>;
+    static bool clk_wanted() { static const bool clkDbg = getenv("XL_PAIR_CLK") != nullptr; return clkDbg; }
+    static constexpr auto launch_clk = launch_pair_conv1x1_clk;
+};
+
+}  // namespace
 
 int xl_run_pair(const xl_op &op, hipStream_t st)
 {
     if (!(op.flags & XL_CONV_SPLIT_IL)) return XL_ERR_ARG;
     if (op.nchunks2 > 1 && !(op.flags & XL_CONV_SPLIT_ACT)) return xl_run_pair_gemm(op, st);
-    return xl_run_pair_conv1x1(op, st);
+    return xl_conv1x1_run<PairConv1x1>(op, st);
 }

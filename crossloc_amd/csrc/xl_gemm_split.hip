@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "xl_conv1x1.h"
 #include "xl_launch.h"
 #include "xl_operand_math.h"
 
@@ -1089,104 +1090,26 @@ void split_conv1x1_res_kernel(SplitConvArgs a)
 //   + XL_CONV_SPLIT_IL: in = V [Z][T][Cin/16][3][16] bf16, w = U [Z][Cout][Cin/16][3][16] bf16 (256 x 256 persistent kernel);
 //   else              : in = plane 0 of V ([Z][T][Cin] bf16, planes Z*T*Cin elements apart), w = plane 0 of U
 //                       ([Z][Cout][Cin] bf16, planes Z*Cout*Cin apart) (128 x 128 kernel, the first form).
-// XL_OP_CONV with XL_CONV_SPLIT_BF16 | XL_CONV_SPLIT_IL and nchunks2 <= 1: a 1x1 stride-1 convolution, fp32 NHWC in / out
-// (ld_in / ld_out), w = [Cout][Cin/16][3][16] bf16, bias, optionally XL_CONV_NORM_IN (aux2 = [B][Cin][2] coefficients) and the
-// statistics epilogue (stats / groups / nchunks with 256-row tiles: nchunks >= ceil(HW / 256) + 1, 16 channels per group).
-// tileFrom / tileCount: this launch covers the tiles [tileFrom, tileFrom + tileCount) of the form's own (z, m-tile, n-tile)
-// numbering (tileCount < 0: all of them).  A 256 x 256 tile t is the 256 x 128 tiles 2t and 2t + 1.
-template <int NW, int BN>
-static int launch_split_conv1x1(const xl_op &op, SplitConvArgs a, bool norm, int Z, hipStream_t st, int tileFrom = 0, int tileCount = -1)
-{
-    constexpr int BM = 32 * NW;
-    const long long M = a.M;
-    const bool perImage = op.reserved_i < 0;         // tiles start at image boundaries (reserved_i = -256 / -128)
-    a.tpi = perImage ? (a.HW + BM - 1) / BM : 0;
-    a.nbm = perImage ? op.B * a.tpi : (int)((M + BM - 1) / BM);
-    a.nbn = (op.Cout + BN - 1) / BN;
-    const size_t lds = 3 * BN * kIUnit + 2 * BM * kIUnit + 2 * 16 * (64 * NW) + 16384 + 4096 + 1024;
-    const bool accumulate = (op.flags & XL_CONV_ACCUMULATE) != 0;
-    const bool resid = norm && a.res != nullptr;
-    const bool dominant = Z > 1 && op.Cin == 512 && op.Cout == 512 && !accumulate && !norm;     // the 512 -> 512 Winograd layers
-    const void *fn = accumulate ? reinterpret_cast<const void *>(split_conv1x1_kernel<false, true, NW, 0, BN>)
-                   : resid ? reinterpret_cast<const void *>(split_conv1x1_res_kernel<NW, BN>)
-                   : norm ? reinterpret_cast<const void *>(split_conv1x1_kernel<true, false, NW, 0, BN>)
-                   : dominant ? reinterpret_cast<const void *>(split_conv1x1_kernel<false, false, NW, 2, BN>)
-                   : Z > 1 ? reinterpret_cast<const void *>(split_conv1x1_kernel<false, false, NW, 1, BN>)
-                           : reinterpret_cast<const void *>(split_conv1x1_kernel<false, false, NW, 0, BN>);
-    static XlLdsLimit configured[6];
-    const int slot = accumulate ? 2 : (resid ? 5 : (norm ? 1 : (dominant ? 4 : (Z > 1 ? 3 : 0))));
-    if (configured[slot].configure(fn, lds) != XL_OK) return XL_ERR_HIP;
-    const int nwg = tileCount < 0 ? a.nbm * a.nbn * Z : tileCount;
-    a.tile0 = tileFrom; a.ntiles = nwg;
-    int grid = 256;                                   // persistent: one workgroup per CU
-    if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
-    if (accumulate) hipLaunchKernelGGL((split_conv1x1_kernel<false, true, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (resid) hipLaunchKernelGGL((split_conv1x1_res_kernel<NW, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (norm) hipLaunchKernelGGL((split_conv1x1_kernel<true, false, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (dominant) hipLaunchKernelGGL((split_conv1x1_kernel<false, false, NW, 2, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else if (Z > 1) hipLaunchKernelGGL((split_conv1x1_kernel<false, false, NW, 1, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    else hipLaunchKernelGGL((split_conv1x1_kernel<false, false, NW, 0, BN>), dim3(grid), dim3(64 * NW), lds, st, a);
-    return XL_OK;
-}
+// XL_OP_CONV with XL_CONV_SPLIT_BF16 | XL_CONV_SPLIT_IL and nchunks2 <= 1 or XL_CONV_SPLIT_ACT: the 1x1 forms, whose launcher
+// (csrc/xl_conv1x1.h, which describes the op) this pipe shares with the pair pipe.  w = [Cout][Cin/16][3][16] bf16.
+namespace {
 
-// reserved_i selects the tile form: +-256 (or 0 / 64, what the fp32 path passes): 256 x 256 tiles; 192: 256 rows x 128 columns;
-// 384: 256 x 256 tiles for the full rounds of the 256 CUs and 256 x 128 tiles for a last partial round (same statistics rows);
-// +-128: 128 x 128 tiles (the statistics epilogue then writes one entry per 128-row tile: nchunks >= ceil(HW / 128) + 1,
-// GN_FINAL / GN_APPLY take 128); negative: tiles start at image boundaries.
-static int xl_run_split_conv1x1(const xl_op &op, hipStream_t st)
-{
-    const long long M = (long long)op.B * op.Ho * op.Wo;
-    const int HW = op.Ho * op.Wo;
-    const bool norm = (op.flags & XL_CONV_NORM_IN) != 0;
-    const bool small = op.reserved_i == 128 || op.reserved_i == -128;
-    const int BM = small ? 128 : 256;
-    const int Z = op.nchunks2 > 1 ? op.nchunks2 : 1;            // Z > 1: XL_CONV_SPLIT_ACT, the batched GEMMs of a Winograd layer
-    if (Z > 1 && (op.bias || op.stats || norm || op.reserved_i < 0 || op.ld_in != op.Cin || op.ld_out != op.Cout)) return XL_ERR_ARG;
-    if (op.ksize != 1 || op.stride != 1 || op.Cin % 32 != 0 || op.Cout % 256 != 0 || op.Cout > 1024 || op.ld_in < op.Cin ||
-        op.ld_out < op.Cout || (op.ld_in & 3) || (op.ld_out & 3) || ((op.flags & XL_CONV_ACCUMULATE) && (norm || Z > 1 || op.stats)) || !op.in ||
-        !op.w || !op.out || (((uintptr_t)op.in | (uintptr_t)op.out | (uintptr_t)op.w) & 15) || M >= 0x7fffffffLL ||
-        (long long)op.Cout * op.Cin * 6 >= 0x7fffffffLL || 256LL * op.ld_in * 4 >= 0x7fffffffLL || 256LL * op.ld_out * 4 >= 0x7fffffffLL)
-        return XL_ERR_ARG;
-    if (norm && (!op.aux2 || op.Cin > 512 || HW < BM)) return XL_ERR_ARG;
-    if (op.stats && (op.groups <= 0 || op.Cout != 16 * op.groups || HW < BM || op.nchunks < (HW + BM - 1) / BM + 1)) return XL_ERR_ARG;
-    if (op.reserved_i < 0 && HW < BM) return XL_ERR_ARG;
-    SplitConvArgs a;
-    a.in = (const float *)op.in; a.u = (const uint16_t *)op.w; a.bias = (const float *)op.bias; a.out = (float *)op.out;
-    a.coef = (const float *)op.aux2;
-    a.normLo = (op.flags & XL_CONV_NORM_RELU) ? 0.f : -__builtin_inff();
-    a.stats = (double *)op.stats; a.HW = HW; a.G = op.groups; a.nchunks = op.nchunks; a.B = op.B;
-    a.M = (int)M; a.C = op.Cin; a.N = op.Cout; a.ldIn = op.ld_in; a.ldOut = op.ld_out;
-    a.Z = Z; a.zIn = M * op.ld_in; a.zOut = M * op.ld_out;
-    a.res = nullptr; a.ldRes = 0;
-    if (op.flags & XL_CONV_NORM_ADD) {                // the producer's GroupNorm + ReLU + residual (aux, ld_aux) + ReLU applied on load
-        if (!norm || !(op.flags & XL_CONV_NORM_RELU) || !op.aux || op.ld_aux < op.Cin || (op.ld_aux & 3) || ((uintptr_t)op.aux & 15) || Z > 1 ||
-            256LL * op.ld_aux * 4 >= 0x7fffffffLL) return XL_ERR_ARG;
-        a.res = (const float *)op.aux; a.ldRes = op.ld_aux;
-    }
-    if (op.flags & XL_CONV_M_TILE_MAJOR) {            // result [row][Z][Cout]: a row of product z starts Z*Cout floats after the one before
-        if (Z < 2 || op.ld_out != op.Cout || 256LL * Z * op.Cout * 4 >= 0x7fffffffLL) return XL_ERR_ARG;
-        a.zOut = op.Cout; a.ldOut = Z * op.Cout;
-    }
-    a.tpi = 0; a.nbm = 0; a.nbn = 0;
-    if (small) return launch_split_conv1x1<4, 128>(op, a, norm, Z, st);
-    if (op.reserved_i == 192) return launch_split_conv1x1<8, 128>(op, a, norm, Z, st);
-    if (op.reserved_i == 384) {
-        // full rounds of 256 x 256 tiles on the 256 CUs, then the rest as 256 x 128 tiles when those fit in ONE round (0.65 of
-        // the time of a round of large tiles): two launches over disjoint tile ranges of the same output
-        const int nbig = (int)((M + 255) / 256) * (op.Cout / 256) * Z, full = nbig / 256 * 256, rem = nbig - full;
-        if (full > 0 && rem > 0 && 2 * rem <= 256) {
-            const int rc = launch_split_conv1x1<8, 256>(op, a, norm, Z, st, 0, full);
-            return rc != XL_OK ? rc : launch_split_conv1x1<8, 128>(op, a, norm, Z, st, 2 * full, 2 * rem);
-        }
-        if (full == 0 && 2 * rem <= 256) return launch_split_conv1x1<8, 128>(op, a, norm, Z, st);
-    }
-    return launch_split_conv1x1<8, 256>(op, a, norm, Z, st);
-}
+struct SplitConv1x1 {
+    using Args = SplitConvArgs;
+    static constexpr int kWeightBytes = 6;
+    static constexpr bool kScale = false, kClk = false;
+    template <int NW, int BN> static constexpr size_t lds_bytes() { return 3 * BN * kIUnit + 2 * (32 * NW) * kIUnit + 2 * 16 * (64 * NW) + 16384 + 4096 + 1024; }
+    static void fill_extra(const xl_op &, Args &, int) {}
+    template <bool NORM, bool ACC, int NW, int ZB, int BN> static constexpr auto kernel = split_conv1x1_kernel<NORM, ACC, NW, ZB, BN>;
+    template <int NW, int BN> static constexpr auto res_kernel = split_conv1x1_res_kernel<NW, BN>;
+};
+
+}  // namespace
 
 int xl_run_split_gemm(const xl_op &op, hipStream_t st)
 {
     if (op.flags & XL_CONV_PAIR_F16) return xl_run_pair(op, st);
-    if ((op.flags & XL_CONV_SPLIT_IL) && (op.nchunks2 <= 1 || (op.flags & XL_CONV_SPLIT_ACT))) return xl_run_split_conv1x1(op, st);
+    if ((op.flags & XL_CONV_SPLIT_IL) && (op.nchunks2 <= 1 || (op.flags & XL_CONV_SPLIT_ACT))) return xl_conv1x1_run<SplitConv1x1>(op, st);
     const int T = op.B * op.Ho * op.Wo, Z = op.nchunks2;
     if (op.ksize != 1 || op.stride != 1 || Z < 1 || op.Cin % kBK != 0 || op.Cout % 4 != 0 || op.ld_in != op.Cin ||
         op.ld_out != op.Cout || op.bias || op.stats || (op.flags & XL_CONV_ACCUMULATE) || !op.in || !op.w || !op.out)
@@ -1210,9 +1133,7 @@ int xl_run_split_gemm(const xl_op &op, hipStream_t st)
         const int slot = (op.Cin == 512 ? 1 : 0) + (fourWaves ? 2 : 0);
         if (configured[slot].configure(reinterpret_cast<const void *>(kernel), lds) != XL_OK) return XL_ERR_HIP;
         static const bool clkDbg = getenv("XL_SPLIT_CLK") != nullptr;
-        const int nwg = a.nbm * a.nbn * Z;
-        int grid = 256;
-        if (grid > ((nwg + 7) & ~7)) grid = (nwg + 7) & ~7;
+        const int grid = xl_persistent_grid(a.nbm * a.nbn * Z);
         if (clkDbg && hipMalloc(&a.clk, sizeof(long long) * 64 * grid) != hipSuccess) return XL_ERR_HIP;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(fourWaves ? 256 : 512), lds, st, a);
         if (clkDbg) {

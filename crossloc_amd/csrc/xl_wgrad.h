@@ -4,7 +4,7 @@
 //
 // for a 1x1 layer (Z = 1, t = the B*H*W pixels, split-K over `splits` workgroups per tile) and for the batched products of a
 // Winograd layer (Z = (m+2)^2 frequencies, t = the tiles, dY = dM = A dY A^T, X = V = B^T x B); the fixed-order reduce over the
-// splits and the layout / transform of the result stay with wgrad_reduce_kernel / XL_OP_WINO_WFINAL (csrc/xl_cnn_bwd.hip).
+// splits and the layout / transform of the result stay with wgrad_reduce_kernel / XL_OP_WINO_WFINAL (csrc/xl_wgrad_f32.hip).
 //
 // Both operands arrive as fp32 with the K dimension (t) OUTERMOST in memory - rows of channels.  The MFMA wants 8
 // consecutive k per lane and row, so a thread owns ONE channel (row of the operand tile) and 8 consecutive t: 8 dword loads
@@ -24,7 +24,7 @@
 //       - X - the layer's (normalised) input, or V = B^T x B for a Winograd layer - is a GroupNorm output: it takes the PLAN's
 //         power-of-two scale (a bound, loose by construction) and the form that does not mind: {hi, lo' = (x - hi) 2^11};
 //       - dY - a gradient (or dM = A dY A^T) - has no static bound: its scale comes from the DATA, the maximum magnitude the pass that
-//         wrote it recorded (xl_amax_commit in csrc/xl_cnn_bwd.hip; max |dY| 2^e in [2^14, 2^15)), which makes it tight - so dY takes
+//         wrote it recorded (xl_wave_max_commit in csrc/xl_gn_bwd.hip, csrc/xl_wgrad_f32.hip; max |dY| 2^e in [2^14, 2^15)), which makes it tight - so dY takes
 //         the weight-like form {hi, lo = dY - hi} and its hs = hi 2^-11 is derived in registers.
 //     Products hs x lo', lo x hi, hi x hi on v_mfma_f32_32x32x16_f16, fp32 accumulation, exact un-scaling of the partial tile.
 // A form's K-step - fragment reads, term order, scheduling groups - is one schedule and stays one piece of text per form.

@@ -1,4 +1,4 @@
-"""The refusals of the forward CNN launchers, as a table.  No GPU.
+"""The refusals of the CNN launchers, forward and backward, as a table.  No GPU.
 
 A launcher validates an op before it makes any HIP call and answers a malformed one with XL_ERR_ARG (-1) or XL_ERR_UNSUPPORTED
 (-4); xl_cnn_run then names the op ("op 0 refused (...)") behind whatever text the launcher left.  Every row below is one
@@ -10,13 +10,19 @@ with two faults that pin which check comes first where the statuses differ.  The
 library before the launchers were split over translation units.  The same for the stride-2 3x3 stem convolutions
 (XL_OP_CONV with XL_CONV_SPLIT_BF16, with and without XL_CONV_PAIR_F16) and the weight-gradient products on the matrix pipe
 (XL_OP_WGRAD with XL_CONV_SPLIT_BF16, with and without XL_CONV_PAIR_F16, one split and several): one row per clause of their
-refusing statements, recorded from the library while each operand form still had a launcher of its own.
+refusing statements, recorded from the library while each operand form still had a launcher of its own.  And the same, one
+row per clause, for the 1x1 / XL_CONV_SPLIT_ACT GEMMs of both operand forms (_g1_rows), the persistent batched GEMMs
+(_gb_rows) and every backward op (_bwd_rows): recorded from the library while the 1x1 launcher existed once per form and all
+backward ops were cases of one switch.  The rows of _gnb_new_rows are the exception: the library they would have been
+recorded from divides by zero on them.
 
 Not in the table, because a HIP call comes first: a failed hipFuncSetAttribute of the implicit GEMM ("hipFuncSetAttribute:
 ..." with XL_ERR_HIP) and of the LDS-DMA F(6x6) output transform, the XL_CONV_CLK allocation and copies, the stem launchers'
 check of the statistics slots (nchunks, groups), which stands behind XlLdsLimit::configure, and the launch errors xl_cnn_run
-collects with hipGetLastError() at the end of a list.  The launchers of other translation units (split and pair GEMMs, the
-fused stem, the other backward ops) are outside this table, except that an unknown op type is refused."""
+collects with hipGetLastError() at the end of a list.  Likewise everything behind XlLdsLimit::configure in the 1x1 and the
+persistent launchers (they have no refusal there), the missing pointers of XL_OP_CONV1_WGRAD's fold form on frames wide enough
+to need more than 64 KiB of LDS, the hipMemsetAsync of XL_OP_FILL0 and the copies of XL_OP_DUC_HEAD_BWD; XL_OP_GNB_PARAMS and
+XL_OP_WINO_WFINAL refuse nothing.  XL_OP_STEM12 and XL_OP_S2_DGRAD have no rows yet."""
 import ctypes
 
 import pytest
@@ -34,6 +40,10 @@ CONV1, CONV, GN_STATS, GN_APPLY, HEAD = ops.XL_OP_CONV1, ops.XL_OP_CONV, ops.XL_
 GN_FINAL, WINO_IN, WINO_OUT, DUC_HEAD = ops.XL_OP_GN_FINAL, ops.XL_OP_WINO_IN, ops.XL_OP_WINO_OUT, ops.XL_OP_DUC_HEAD
 DGRAD, ACC, SPLIT, IL, PAIR = ops.CONV_DGRAD, ops.CONV_ACCUMULATE, ops.CONV_SPLIT_BF16, ops.CONV_SPLIT_IL, ops.CONV_PAIR_F16
 NORM_IN, TILE_MAJOR, GN_ADD = ops.CONV_NORM_IN, ops.CONV_M_TILE_MAJOR, ops.GN_ADD
+NORM_RELU, NORM_ADD, ACT, AMAX = ops.CONV_NORM_RELU, ops.CONV_NORM_ADD, ops.CONV_SPLIT_ACT, ops.CONV_PAIR_AMAX
+FILL0, GNB_STATS, GNB_FINAL, GNB_APPLY = ops.XL_OP_FILL0, ops.XL_OP_GNB_STATS, ops.XL_OP_GNB_FINAL, ops.XL_OP_GNB_APPLY
+GNB_PARAMS_LIST, HEAD_BWD, DUC_HEAD_BWD = ops.XL_OP_GNB_PARAMS_LIST, ops.XL_OP_HEAD_BWD, ops.XL_OP_DUC_HEAD_BWD
+WINO_DY, CONV1_WGRAD = ops.XL_OP_WINO_DY, ops.XL_OP_CONV1_WGRAD
 
 
 def _conv(**kw):
@@ -134,7 +144,7 @@ def _wg(pair, splits, extra=0, **kw):
 
 
 def _wg_rows():
-    """every refusing statement of the weight-gradient launchers behind the checks of xl_run_bwd_op, for both forms, with one
+    """every refusing statement of the weight-gradient launchers behind the checks of xl_run_wgrad, for both forms, with one
     split (the launcher gets `out` as its partial tile) and with four"""
     rows = []
     for pair, form in ((False, "wgrad-split-"), (True, "wgrad-pair-")):
@@ -161,6 +171,237 @@ def _wg_rows():
     # with the split flag the launcher's own check answers; without it the same shape has no fp32 kernel
     rows.append(("wgrad-split-ksize-before-fp32-shapes", _wg(False, 4, ksize=3, Cin=48, ld_in=48, Cout=48, ld_aux=48), ARG, None))
     rows.append(("wgrad-fp32-shapes", _wg(False, 4, flags=0, Cin=48, ld_in=48, Cout=48, ld_aux=48), UNSUPPORTED, None))
+    return rows
+
+
+def _g1(pair, extra=0, **kw):
+    """a well-formed 1x1 32 -> 256 convolution over 16 x 16 pixels (one 256-row tile) on the split (pair) pipe"""
+    d = dict(type=CONV, B=1, Hi=16, Wi=16, Cin=32, Ho=16, Wo=16, Cout=256, ksize=1, stride=1, ld_in=32, ld_out=256,
+             flags=SPLIT | IL | (PAIR if pair else 0) | extra, w=A, out=A, scale=A if pair else 0, **{"in_": A})
+    d.update(kw)
+    return d
+
+
+def _g1_rows():
+    """every clause of the refusing statements of the 1x1 / XL_CONV_SPLIT_ACT launcher (csrc/xl_conv1x1.h) that xl_run_conv lets
+    through, for both operand forms.  `half` (`quarter`) is an image below one 256-row (128-row) tile; Z = 4 stands for the
+    batched products of a Winograd layer.  Two clauses have no row because an earlier statement answers the same op with the
+    same status: the Z > 1 of XL_CONV_NORM_ADD (it needs XL_CONV_NORM_IN, which the first statement refuses for Z > 1) and the
+    ld_out of XL_CONV_M_TILE_MAJOR (the first statement's, for Z > 1)."""
+    half = dict(Hi=8, Wi=16, Ho=8, Wo=16)
+    quarter = dict(Hi=8, Wi=8, Ho=8, Wo=8)
+    z4 = dict(nchunks2=4, extra=ACT)
+    add = dict(extra=NORM_IN | NORM_RELU | NORM_ADD, aux2=A, aux=A, ld_aux=32)
+    rows = []
+    for pair, form in ((False, "1x1-split-"), (True, "1x1-pair-")):
+        wide = 524288 if pair else 349536                          # 1024 x Cin weights of 4 (6) bytes reach 2^31 bytes
+        rows += [(form + name, _g1(pair, **kw), ARG, None) for name, kw in (
+            ("ksize", dict(ksize=5)),
+            ("stride", dict(stride=2)),
+            ("cin-32", dict(Cin=48, ld_in=48)),
+            ("cout-256", dict(Cout=128, ld_out=128)),
+            ("cout-max", dict(Cout=1280, ld_out=1280)),
+            ("ld-in-below-cin", dict(Cin=64)),
+            ("ld-out-below-cout", dict(ld_out=128)),
+            ("ld-in-4", dict(ld_in=34)),
+            ("ld-out-4", dict(ld_out=258)),
+            ("accumulate-norm", dict(extra=ACC | NORM_IN, aux2=A)),
+            ("accumulate-batched", dict(nchunks2=4, extra=ACT | ACC)),
+            ("accumulate-stats", dict(extra=ACC, stats=A, groups=16, nchunks=2)),
+            ("no-input", {"in_": 0}),
+            ("no-weights", dict(w=0)),
+            ("no-output", dict(out=0)),
+            ("input-alignment", {"in_": A + 4}),
+            ("weight-alignment", dict(w=A + 8)),
+            ("output-alignment", dict(out=A + 4)),
+            ("pixels-2gib", dict(B=1 << 23)),
+            ("weights-2gib", dict(Cin=wide, ld_in=wide, Cout=1024, ld_out=1024)),
+            ("tile-rows-in-2gib", dict(ld_in=1 << 21)),
+            ("tile-rows-out-2gib", dict(ld_out=1 << 21)),
+            ("batched-bias", dict(bias=A, **z4)),
+            ("batched-stats", dict(stats=A, groups=16, nchunks=2, **z4)),
+            ("batched-norm", dict(nchunks2=4, extra=ACT | NORM_IN, aux2=A)),
+            ("batched-per-image-tiles", dict(reserved_i=-256, **z4)),
+            ("batched-ld-in", dict(ld_in=64, **z4)),
+            ("batched-ld-out", dict(ld_out=512, **z4)),
+            ("norm-no-coefficients", dict(extra=NORM_IN)),
+            ("norm-cin-max", dict(extra=NORM_IN, aux2=A, Cin=544, ld_in=544)),
+            ("norm-image-below-256", dict(extra=NORM_IN, aux2=A, **half)),
+            ("norm-image-below-128", dict(extra=NORM_IN, aux2=A, reserved_i=128, **quarter)),
+            ("stats-no-groups", dict(stats=A, groups=0, nchunks=2)),
+            ("stats-16-per-group", dict(stats=A, groups=8, nchunks=2)),
+            ("stats-image-below-256", dict(stats=A, groups=16, nchunks=2, **half)),
+            ("stats-image-below-128", dict(stats=A, groups=16, nchunks=2, reserved_i=128, **quarter)),
+            ("stats-slots-256", dict(stats=A, groups=16, nchunks=1)),
+            ("stats-slots-128", dict(stats=A, groups=16, nchunks=2, reserved_i=128)),
+            ("per-image-below-256", dict(reserved_i=-256, **half)),
+            ("per-image-below-128", dict(reserved_i=-128, **quarter)),
+            ("add-no-norm", dict(add, extra=NORM_RELU | NORM_ADD)),
+            ("add-no-relu", dict(add, extra=NORM_IN | NORM_ADD)),
+            ("add-no-residual", dict(add, aux=0)),
+            ("add-ld-below-cin", dict(add, Cin=64, ld_in=64)),
+            ("add-ld-4", dict(add, ld_aux=34)),
+            ("add-alignment", dict(add, aux=A + 4)),
+            ("add-tile-rows-2gib", dict(add, ld_aux=1 << 21)),
+            ("tile-major-one-product", dict(extra=TILE_MAJOR)),
+            ("tile-major-tile-rows-2gib", dict(nchunks2=2048, extra=ACT | TILE_MAJOR, Cout=1024, ld_out=1024)),
+        )]
+    rows.append(("1x1-pair-no-scale", _g1(True, scale=0), ARG, None))
+    rows.append(("pair-not-interleaved", _g1(True, flags=SPLIT | PAIR), ARG, None))
+    return rows
+
+
+def _gb(form, extra=0, **kw):
+    """four well-formed batched 32 -> 256 products over 256 rows for a persistent launcher: the split pipe's first form
+    ("planes"), its interleaved form ("il") and the pair pipe's ("pair")"""
+    d = dict(type=CONV, B=1, Hi=16, Wi=16, Cin=32, Ho=16, Wo=16, Cout=256, ksize=1, stride=1, ld_in=32, ld_out=256, nchunks2=4,
+             flags=SPLIT | {"planes": 0, "il": IL, "pair": IL | PAIR}[form] | extra, w=A, out=A, scale=A if form == "pair" else 0,
+             **{"in_": A})
+    d.update(kw)
+    return d
+
+
+def _gb_rows():
+    """every clause of the refusing statements of xl_run_split_gemm (both forms) and xl_run_pair_gemm that xl_run_conv lets
+    through; the 32-bit bounds are reached with many images or channels, each shape chosen so that the clauses in front of the
+    named one hold.  (Z < 1 reaches only the first form: the interleaved ones go to the 1x1 launcher with nchunks2 <= 1.)"""
+    one = dict(Hi=1, Wi=1, Ho=1, Wo=1)
+    rows = []
+    for form in ("planes", "il", "pair"):
+        tag = "batched-%s-" % form
+        rows += [(tag + name, _gb(form, **kw), ARG, None) for name, kw in (
+            ("ksize", dict(ksize=5)),
+            ("stride", dict(stride=2)),
+            ("ld-in", dict(ld_in=64)),
+            ("ld-out", dict(ld_out=512)),
+            ("bias", dict(bias=A)),
+            ("stats", dict(stats=A)),
+            ("accumulate", dict(extra=ACC)),
+            ("no-input", {"in_": 0}),
+            ("no-weights", dict(w=0)),
+            ("no-output", dict(out=0)),
+        )]
+        if form != "planes":
+            k = 4 if form == "pair" else 6                            # operand bytes per element
+            acts, wts = 2048 // k // 32 * 32 + 32, (1 << 23) // k // 32 * 32 + 32      # 2^20 rows (256 rows) of them reach 2^31 bytes
+            rows += [(tag + name, _gb(form, **kw), ARG, None) for name, kw in (
+                ("cout-256", dict(Cout=128, ld_out=128)),
+                ("result-rows-4gib", dict(Cout=1 << 22, ld_out=1 << 22, **one)),
+                ("activations-2gib", dict(B=4096, Cin=acts, ld_in=acts)),
+                ("weights-2gib", dict(Cin=wts, ld_in=wts, **one)),
+                ("result-2gib", dict(B=8192)),
+            )]
+    rows += [("batched-planes-" + name, _gb("planes", **kw), ARG, None) for name, kw in (
+        ("no-products", dict(nchunks2=0)),
+        ("cin-32", dict(Cin=48, ld_in=48)),
+        ("activations-2gib", dict(B=1 << 15)),
+        ("weights-2gib", dict(Cin=8192, ld_in=8192, Cout=32768, ld_out=32768)),
+        ("result-2gib", dict(B=2048)),
+    )]
+    rows += [("batched-pair-" + name, _gb("pair", **kw), ARG, None) for name, kw in (
+        ("norm", dict(extra=NORM_IN)),
+        ("tile-major", dict(extra=TILE_MAJOR)),
+        ("amax", dict(extra=AMAX)),
+        ("no-scale", dict(scale=0)),
+        ("input-alignment", {"in_": A + 4}),
+        ("weight-alignment", dict(w=A + 8)),
+        ("output-alignment", dict(out=A + 4)),
+    )]
+    return rows
+
+
+def _gnb(t, **kw):
+    d = dict(type=t, B=1, Hi=16, Wi=16, Cin=64, groups=32, nchunks2=4, ld_in=64, ld_aux=64, ld_out=64, stats=P, stats2=P)
+    d.update(kw)
+    return d
+
+
+def _wdy(m, **kw):
+    d = dict(type=WINO_DY, B=1, Hi=12, Wi=12, Cin=64, Ho=12 // m, Wo=12 // m, ksize=m, ld_in=64)
+    d.update(kw)
+    return d
+
+
+def _c1w(**kw):
+    """the weight gradient of conv1 (3 -> 32) on a 16 x 64 image"""
+    d = dict(type=CONV1_WGRAD, B=1, Hi=16, Wi=64, Cin=3, Cout=32, ld_aux=32, ld_in=32)
+    d.update(kw)
+    return d
+
+
+def _bwd_rows():
+    """every refusing statement of the backward launchers that is reached before the first HIP call (the weight-gradient
+    products on the matrix pipe are in _wg_rows)"""
+    fp32 = dict(flags=0)                                                  # XL_OP_WGRAD on the exact-fp32 kernel, 64 -> 64
+    rows = [
+        ("fill0-no-output", dict(type=FILL0, Cin=8), ARG, None),
+        ("fill0-no-bytes", dict(type=FILL0, out=P), ARG, None),
+        ("wgrad-no-splits", _wg(False, 0, **fp32), ARG, None),
+        ("wgrad-ld-in-4", _wg(False, 4, ld_in=66, **fp32), ARG, None),
+        ("wgrad-ld-aux-4", _wg(False, 4, ld_aux=66, **fp32), ARG, None),
+        ("wgrad-no-splits-before-fp32-shapes", _wg(False, 0, Cin=48, ld_in=48, Cout=48, ld_aux=48, **fp32), ARG, None),
+        ("wgrad-fp32-batched-ksize", _wg(False, 4, groups=4, ksize=3, **fp32), ARG, None),
+        ("wgrad-fp32-batched-ld-in", _wg(False, 4, groups=4, ld_in=68, **fp32), ARG, None),
+        ("wgrad-fp32-batched-ld-aux", _wg(False, 4, groups=4, ld_aux=68, **fp32), ARG, None),
+        ("wgrad-fp32-x-2gib", _wg(False, 4, Hi=4096, Wi=4096, **fp32), ARG, None),
+        ("wgrad-fp32-dy-2gib", _wg(False, 4, Ho=4096, Wo=4096, **fp32), ARG, None),
+        ("wgrad-fp32-image-below-k-step", _wg(False, 4, Hi=4, Wi=4, Ho=4, Wo=4, **fp32), UNSUPPORTED, None),
+        ("wgrad-fp32-x-2gib-before-image", _wg(False, 4, Hi=4096, Wi=4096, Ho=4, Wo=4, **fp32), ARG, None),
+    ]
+    for t, tag in ((GNB_STATS, "gnb-stats-"), (GNB_FINAL, "gnb-final-"), (GNB_APPLY, "gnb-apply-")):
+        rows += [(tag + name, _gnb(t, **kw), ARG, None) for name, kw in (
+            ("cin-4", dict(Cin=66, groups=33)),
+            ("groups-divide", dict(groups=24)),
+            ("groups-max", dict(Cin=128, groups=128)),
+            ("no-chunks", dict(nchunks2=0)),
+            ("no-forward-table", dict(stats=0)),
+            ("no-scratch", dict(stats2=0)),
+        )]
+    rows += [
+        # 17 channel quads: the first multiple of 17 threads that is whole waves is 17 * 64 = 1088 > 1024
+        ("gnb-stats-no-thread-count", _gnb(GNB_STATS, Cin=68, groups=4), ARG, None),
+        ("gnb-stats-threads-max", _gnb(GNB_STATS, Cin=4112, groups=16), ARG, None),
+        ("gnb-params-list-no-layers", dict(type=GNB_PARAMS_LIST, Cin=0, Cout=64, **{"in_": P}), ARG, None),
+        ("gnb-params-list-layers-max", dict(type=GNB_PARAMS_LIST, Cin=65536, Cout=64, **{"in_": P}), ARG, None),
+        ("gnb-params-list-no-items", dict(type=GNB_PARAMS_LIST, Cin=4, Cout=64), ARG, None),
+        ("gnb-params-list-no-channels", dict(type=GNB_PARAMS_LIST, Cin=4, Cout=0, **{"in_": P}), ARG, None),
+        ("head-bwd-cin-4", _head(type=HEAD_BWD, Cin=6, ld_in=8), ARG, None),
+        ("head-bwd-cin-min", _head(type=HEAD_BWD, Cin=0), ARG, None),
+        ("head-bwd-cin-max", _head(type=HEAD_BWD, Cin=1028, ld_in=1028), ARG, None),
+        ("head-bwd-cout-max", _head(type=HEAD_BWD, Cout=5), ARG, None),
+        ("head-bwd-cout-min", _head(type=HEAD_BWD, Cout=0), ARG, None),
+        ("duc-head-bwd-cout-min", _duc(type=DUC_HEAD_BWD, Cout=0, Cin=0), ARG, None),
+        ("duc-head-bwd-cout-max", _duc(type=DUC_HEAD_BWD, Cout=9, Cin=576), ARG, None),
+        ("duc-head-bwd-cin", _duc(type=DUC_HEAD_BWD, Cin=320), ARG, None),
+    ]
+    for m in (4, 6):
+        rows += [("wino%d-dy-%s" % (m, name), _wdy(m, **kw), ARG, None) for name, kw in (
+            ("cin-2", dict(Cin=63)),
+            ("ld-2", dict(ld_in=65)),
+            ("tile-rows", dict(Hi=13)),
+            ("tile-columns", dict(Wi=13)),
+        )]
+    rows += [
+        ("conv1-wgrad-cout", _c1w(Cout=64), UNSUPPORTED, None),
+        ("conv1-wgrad-cin", _c1w(Cin=4), UNSUPPORTED, None),
+        ("conv1-wgrad-ld-aux-4", _c1w(ld_aux=34), ARG, None),
+        ("conv1-wgrad-cout-before-ld-aux", _c1w(Cout=64, ld_aux=34), UNSUPPORTED, None),
+        ("conv1-wgrad-width", _c1w(Wi=2559), UNSUPPORTED, None),
+        ("conv1-wgrad-ld-aux-before-width", _c1w(Wi=2559, ld_aux=34), ARG, None),
+        ("conv1-wgrad-fold-no-table", _c1w(aux2=P, bias=P), ARG, None),
+        ("conv1-wgrad-fold-no-coefficients", _c1w(aux2=P, w=P), ARG, None),
+        ("conv1-wgrad-fold-ld-in-4", _c1w(aux2=P, w=P, bias=P, ld_in=34), ARG, None),
+    ]
+    return rows
+
+
+def _gnb_new_rows():
+    """NOT recorded from the library before the backward launchers were split: there these ops divide by zero (Cin % groups,
+    256 % (Cin / 4), 64 % (Cin / groups)) and kill the process.  xl_run_gnb refuses them before it divides."""
+    rows = []
+    for t, tag in ((GNB_STATS, "gnb-stats-"), (GNB_FINAL, "gnb-final-"), (GNB_APPLY, "gnb-apply-")):
+        rows += [(tag + "no-groups", _gnb(t, groups=0), ARG, None), (tag + "no-channels", _gnb(t, Cin=0), ARG, None)]
+    rows.append(("gnb-stats-negative-groups", _gnb(GNB_STATS, groups=-4), ARG, None))
     return rows
 
 
@@ -307,7 +548,13 @@ TABLE = [
     # ---- XL_OP_CONV 3x3 stride 2 on the split / pair pipe, XL_OP_WGRAD on the split / pair pipe (one launcher per family)
     *_s2_rows(),
     *_wg_rows(),
-    # ---- anything else goes to the backward dispatcher, which knows no such op
+    # ---- XL_OP_CONV 1x1 / XL_CONV_SPLIT_ACT on the split / pair pipe (one launcher), the persistent batched GEMMs of both pipes
+    *_g1_rows(),
+    *_gb_rows(),
+    # ---- the backward ops, one launcher per op type in the file of its kernel family
+    *_bwd_rows(),
+    *_gnb_new_rows(),
+    # ---- and an op type that has no launcher
     ("unknown-op-type", dict(type=99), UNSUPPORTED, "op 0 refused (type 99"),
 ]
 
