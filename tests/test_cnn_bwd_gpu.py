@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+import guarded                             # noqa: E402
+torch = guarded.torch_proxy()              # empty / zeros / full (_like) on the device: between guard bands
 
 from crossloc_amd import networks                      # noqa: E402
 from crossloc_amd.weights import seeded_state_dict     # noqa: E402
@@ -25,6 +27,12 @@ from size_classes import MIXED_PARITY, ids             # noqa: E402
 
 pytestmark = pytest.mark.gpu
 MEAN = torch.tensor([-455.934, 417.50, 520.31])
+
+
+@pytest.fixture(autouse=True)
+def _guard_bands(monkeypatch):
+    """Every device tensor this module allocates (and every packed operand) sits between guard bands: checked after each test."""
+    yield from guarded.op_module_check(monkeypatch, networks, __name__)
 
 
 def _reference_grads(sd, x, wgt, enc_add, dec_add, n_task=3, n_pos=1, in_ch=3):

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
+import guarded                             # noqa: E402
+torch = guarded.torch_proxy()              # empty / zeros / full (_like) on the device: between guard bands
 import torch.nn as nn                      # noqa: E402
 import torch.nn.functional as F            # noqa: E402
 
@@ -18,6 +20,12 @@ from oracle import cnn_oracle              # noqa: E402
 pytestmark = pytest.mark.gpu
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "net_forward.npz"))
 MEAN = torch.tensor([-455.934, 417.50, 520.31])
+
+
+@pytest.fixture(autouse=True)
+def _guard_bands(monkeypatch):
+    """Every device tensor this module allocates (and every packed operand) sits between guard bands: checked after each test."""
+    yield from guarded.op_module_check(monkeypatch, networks, __name__)
 
 
 def _run(ops):

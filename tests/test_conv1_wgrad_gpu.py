@@ -9,12 +9,20 @@ before the launch; the floats behind dW / db must still be NaN afterwards."""
 import pytest
 
 torch = pytest.importorskip("torch")
+import guarded                             # noqa: E402
+torch = guarded.torch_proxy()              # empty / zeros / full (_like) on the device: between guard bands
 
 import head_refs                                        # noqa: E402
 from crossloc_amd import networks                      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
+
+
+@pytest.fixture(autouse=True)
+def _guard_bands(monkeypatch):
+    """Every device tensor this module allocates (and every packed operand) sits between guard bands: checked after each test."""
+    yield from guarded.op_module_check(monkeypatch, networks, __name__)
 
 
 def _run(ops):

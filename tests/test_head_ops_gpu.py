@@ -21,6 +21,8 @@ import math
 import pytest
 
 torch = pytest.importorskip("torch")
+import guarded                             # noqa: E402
+torch = guarded.torch_proxy()              # empty / zeros / full (_like) on the device: between guard bands
 
 import head_refs                                        # noqa: E402
 from crossloc_amd import networks                      # noqa: E402
@@ -30,6 +32,12 @@ LO, HI = head_refs.CLAMP_LO, head_refs.CLAMP_HI
 MEAN = [-455.934, 417.50, 520.31, 241.47, 0.0, 12.5]
 NAN = float("nan")
 BOUNDS = {"task": 1e-4, "pos": 2e-4, "dx": 2e-5, "dW": 2e-5, "db": 2e-5}      # the per-op criteria (module docstring)
+
+
+@pytest.fixture(autouse=True)
+def _guard_bands(monkeypatch):
+    """Every device tensor this module allocates (and every packed operand) sits between guard bands: checked after each test."""
+    yield from guarded.op_module_check(monkeypatch, networks, __name__)
 
 
 def _run(ops):

@@ -13,6 +13,8 @@ _PAIRS_OFF = os.environ.get("XL_GEMM_PAIR") in ("", "0") or os.environ.get("XL_G
 pairs_only = pytest.mark.skipif(_PAIRS_OFF, reason="the fp16-pair forms are switched off (measurement switch set)")
 
 torch = pytest.importorskip("torch")
+import guarded                             # noqa: E402
+torch = guarded.torch_proxy()              # empty / zeros / full (_like) on the device: between guard bands
 import torch.nn as nn                      # noqa: E402
 import torch.nn.functional as F            # noqa: E402
 
@@ -21,6 +23,12 @@ from crossloc_amd import networks          # noqa: E402
 pytestmark = pytest.mark.gpu
 
 PAIR = networks.CONV_SPLIT_BF16 | networks.CONV_SPLIT_IL | networks.CONV_PAIR_F16
+
+
+@pytest.fixture(autouse=True)
+def _guard_bands(monkeypatch):
+    """Every device tensor this module allocates (and every packed operand) sits between guard bands: checked after each test."""
+    yield from guarded.op_module_check(monkeypatch, networks, __name__)
 
 
 def _run(ops):
