@@ -87,6 +87,10 @@ def lib():
             getattr(L, name).argtypes = [c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_f, c_vp, c_vp, c_vp]
         L.xl_metrics_semantics.restype = c_i32
         L.xl_metrics_semantics.argtypes = [c_vp, c_i64, c_i64, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]
+        # include/crossloc_e2e.h
+        L.xl_e2e_pose_gradient.restype = c_i32
+        L.xl_e2e_pose_gradient.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f, c_f, c_f,
+                                           c_vp, c_vp, c_vp]
         for name in ("xl_dsac_forward_rgbd", "xl_dsac_backward_rgbd"):
             getattr(L, name).restype = c_i32
         _lib = L

@@ -305,3 +305,107 @@ def task_loss_and_output_gradient(task, uncertainty, prediction, num_task_channe
             raise NotImplementedError(task)
     _lib.check(rc)
     return out[0], out[1], grad
+
+
+# ------------------------------------------------------------------------------------------ end-to-end DSAC* training
+E2E_MAX_TRIES = 4096            # sampler tries per hypothesis in a training step: 64 trips of a wave (the solver's own default,
+#                                 1 000 000, lets a frame of unusable coordinates hold a workgroup for 15 000 trips per hypothesis)
+E2E_STATS = 4                   # XL_E2E_STATS: doubles per row of the finishing op's statistics
+# column of a per-frame row / of the summary row (the last one); meaning: include/crossloc_e2e.h
+E2E_FRAME_FIELDS = {"loss": 0, "norm": 1, "scale": 2, "accepted": 3}
+E2E_SUMMARY_FIELDS = {"mean_loss": 0, "accepted": 1, "max_norm": 2, "clipped": 3}
+
+
+def finish_pose_gradient(g, losses, channels, weight=1.0, clip_norm=0.0, grad=None, beta=0.0):
+    """The finishing op of the end-to-end step (csrc/xl_e2e.hip, rules: include/crossloc_e2e.h), one launch: the solver's
+    gradient g [B,3,Ho,Wo] (float32 CUDA, any strides) and its expected losses [B] (float64 CUDA) become the gradient w.r.t.
+    the network's `channels`-channel output.  Per frame: the norm of g; a frame whose loss or gradient is not finite is
+    rejected and contributes exact zeros; the others are scaled by weight / B, and by clip_norm / norm where clip_norm > 0 and
+    the norm exceeds it.  `grad` [B,channels,Ho,Wo] (contiguous float32) with `beta` != 0: the result is added onto
+    beta * grad in place; with beta == 0 `grad` is overwritten without being read (allocated when None).  Returns
+    (grad, stats): stats float64 [B+1,4], rows E2E_FRAME_FIELDS and, last, E2E_SUMMARY_FIELDS.  Nothing synchronises."""
+    if not isinstance(g, torch.Tensor) or not g.is_cuda or not isinstance(losses, torch.Tensor) or not losses.is_cuda:
+        raise RuntimeError("crossloc_amd.loss runs on the GPU only (no CPU fallback)")
+    if g.dim() != 4 or g.size(1) != 3 or g.dtype != torch.float32:
+        raise RuntimeError("the solver gradient must be float32 [B,3,Ho,Wo], got %s %s" % (g.dtype, tuple(g.shape)))
+    B, _, Ho, Wo = g.shape
+    if losses.dtype != torch.float64 or tuple(losses.shape) != (B,) or not losses.is_contiguous() or losses.device != g.device:
+        raise RuntimeError("losses must be a contiguous float64 [B] tensor on the device of the gradient")
+    if int(channels) < 3:
+        raise RuntimeError("the network output has at least the 3 coordinate channels, got %d" % channels)
+    shape = (B, int(channels), Ho, Wo)
+    if grad is None:
+        if beta != 0.0:
+            raise RuntimeError("beta != 0 adds onto `grad`: pass it")
+        grad = torch.empty(shape, dtype=torch.float32, device=g.device)
+    elif (not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32 or tuple(grad.shape) != shape
+          or not grad.is_contiguous() or grad.device != g.device):
+        raise RuntimeError("grad must be a contiguous float32 %s tensor on the device of the gradient" % (shape,))
+    stats = torch.empty((B + 1, E2E_STATS), dtype=torch.float64, device=g.device)
+    L = _lib.lib()
+    with torch.cuda.device(g.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        rc = L.xl_e2e_pose_gradient(_ptr(g), *g.stride(), _ptr(losses), B, Ho, Wo, int(channels), float(weight),
+                                    float(clip_norm), float(beta), _ptr(grad), _ptr(stats), stream)
+    _lib.check(rc)
+    return grad, stats
+
+
+def e2e_image_keys(image_keys, B):
+    """(image0, image_stride) of frame keys that form an arithmetic sequence - the only form the solver's ABI keys a batch
+    by.  Any other list is refused: a training step passes its sampler batch as image0 (training.e2e_keys) instead."""
+    keys = [int(k) for k in image_keys]
+    if len(keys) != B:
+        raise ValueError("expected %d image keys, got %d" % (B, len(keys)))
+    stride = keys[1] - keys[0] if B > 1 else 1
+    if stride < 0 or any(keys[i] != keys[0] + i * stride for i in range(B)):
+        raise ValueError("image_keys must be an arithmetic sequence with a non-negative step (image0 + b * image_stride), "
+                         "got %s" % (keys,))
+    return keys[0], stride
+
+
+def expected_pose_loss_and_output_gradient(prediction, gt_poses, focals, image_h, image_w, hypotheses, threshold,
+                                           inlier_alpha, max_pixel_error, weight_rot, weight_trans, soft_clamp, seed,
+                                           image0=0, image_stride=1, image_keys=None, clip_norm=0.0, weight=1.0,
+                                           grad=None, beta=0.0, depth=None, cam_coords=None, rgbd_threshold=10.0,
+                                           max_dist_error=100.0, max_tries=E2E_MAX_TRIES, subsample=8):
+    """The DSAC* expected pose loss of a batch and its gradient w.r.t. the network output, in the form the end-to-end step
+    uses (the sibling of task_loss_and_output_gradient): `prediction` [B, C >= 3, Ho, Wo] (float32 CUDA) is read in place -
+    its [:, :3] view goes to the solver as it is - dsacstar.backward_rgb_batch accumulates into a zeroed [B,3,Ho,Wo] buffer
+    (with `depth` [B,Ho,Wo] or `cam_coords` [B,3,Ho,Wo]: dsacstar.backward_rgbd_batch, thresholds rgbd_threshold and
+    max_dist_error in centimetres, Ho*Wo <= dsacstar.RGBD_MAX_CELLS), and finish_pose_gradient turns that into `grad`
+    [B,C,Ho,Wo] for prediction.backward(grad).  Returns (mean_loss, stats, grad), device tensors only: mean_loss is the mean
+    of the solver's losses over the accepted frames (a 0-dim float64 view of stats), stats as finish_pose_gradient.
+
+    focals: one focal length per frame (sequence or tensor); the principal point is (image_w / 2, image_h / 2); `subsample`
+    is the network's OUTPUT_SUBSAMPLE.  seed / image0 / image_stride key the sampler: frame b draws as image
+    image0 + b * image_stride.  image_keys, when given, replaces image0 and image_stride and must be such an arithmetic
+    sequence (e2e_image_keys); a batch of scattered dataset indices is keyed by its first index and the step's seed instead
+    (training.e2e_keys), which is as deterministic and needs one solver call.  max_tries bounds the sampler per hypothesis.
+    grad / beta / weight / clip_norm: finish_pose_gradient."""
+    from . import dsacstar
+    p = prediction.detach()
+    if not p.is_cuda:
+        raise RuntimeError("crossloc_amd.loss runs on the GPU only (no CPU fallback)")
+    if p.dim() != 4 or p.dtype != torch.float32 or p.size(1) < 3:
+        raise RuntimeError("prediction must be float32 [B, C >= 3, Ho, Wo], got %s %s" % (p.dtype, tuple(p.shape)))
+    B, C, Ho, Wo = p.shape
+    if image_keys is not None:
+        image0, image_stride = e2e_image_keys(image_keys, B)
+    coords = p[:, :3]
+    focals = torch.as_tensor(focals, dtype=torch.float32).reshape(-1)
+    if focals.numel() != B:
+        raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    g = torch.zeros((B, 3, Ho, Wo), dtype=torch.float32, device=p.device)
+    ppx, ppy = image_w / 2, image_h / 2
+    if depth is None and cam_coords is None:
+        losses = dsacstar.backward_rgb_batch(coords, g, gt_poses, hypotheses, threshold, 0.0, ppx, ppy, weight_rot,
+                                             weight_trans, soft_clamp, inlier_alpha, max_pixel_error, subsample, seed,
+                                             image0=image0, image_stride=image_stride, focals=focals, max_tries=max_tries)
+    else:
+        losses = dsacstar.backward_rgbd_batch(coords, cam_coords, g, gt_poses, hypotheses, rgbd_threshold, weight_rot,
+                                              weight_trans, soft_clamp, inlier_alpha, max_dist_error, seed, image0=image0,
+                                              image_stride=image_stride, max_tries=max_tries, depth=depth, ppointX=ppx,
+                                              ppointY=ppy, subSampling=subsample, focals=focals)
+    grad, stats = finish_pose_gradient(g, losses, C, weight, clip_norm, grad, beta)
+    return stats[B, 0], stats, grad

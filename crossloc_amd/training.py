@@ -5,6 +5,8 @@ Reference: utils/learning.py:84-175 (label means), :266-398 (config_network), tr
                    their checkpoints and frozen, decoder initialised from the coord checkpoint); host only.
   make_step        one iteration (forward, uncertainty split, fused loss, backward, gradient all-reduce, fused Adam) as
                    HIP launches plus at most one collective; returns device scalars, nothing synchronises.
+  make_e2e_step    its sibling for end-to-end DSAC* training (train_e2e.py): forward, the solver's backward pass and the
+                   finishing op in place of the fused loss, [joined with the coord loss,] then the same tail.
   epoch_batches    the data-parallel sampler: one seeded permutation per epoch, identical on every rank, cut into
                    disjoint per-rank shards.
   Trainer          the loop: schedule, reference checkpoints (model.net, ckpt_iter_%07d.net, FLAG_training_done.nodata)
@@ -185,6 +187,55 @@ def make_step(network, task, optimizer, uncertainty=None, nodata_value=-1, minde
     return step
 
 
+def e2e_keys(seed, batch, step_index):
+    """(solver seed, image0) of an end-to-end step: the run's --seed plus the step index, and the dataset index of the
+    batch's first frame (frame b of the batch draws as image image0 + b).  They depend on the sampler's batch and the step
+    index only, so a step is reproducible wherever it runs; the solver's ABI keys a batch by such a sequence."""
+    return int(seed) + int(step_index), int(batch[0])
+
+
+def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce=False):
+    """One iteration of end-to-end DSAC* training: step(images, gt_poses, gt_labels, focals, step_index, image0=0) with device
+    tensors (focals: one per frame, host or device; gt_labels: the coord labels, or a dict with 'coord' and, for --mode
+    rgbd, 'depth') -> (mean expected pose loss, summary row of loss.E2E_SUMMARY_FIELDS), device tensors; nothing
+    synchronises.  Forward, [the coord loss's output gradient times opt.init_weight,] the solver's backward pass and the
+    finishing op added onto it, backward, gradient all-reduce, fused Adam.  `opt`: the options of train_e2e.py."""
+    rgbd = opt.mode == 'rgbd'
+    joint = opt.init_weight > 0
+    sub = network.OUTPUT_SUBSAMPLE
+    pixel_grid = xl_loss.get_pixel_grid(sub) if joint else None
+    nodata_value = get_nodata_value(opt.scene)
+
+    def step(images, gt_poses, gt_labels, focals, step_index, image0=0):
+        predictions = network(images)
+        image_h, image_w = images.size(2), images.size(3)
+        focals = torch.as_tensor(focals, dtype=torch.float32).reshape(-1)
+        grad, beta = None, 0.0
+        if joint:
+            gt_coords = gt_labels['coord'] if isinstance(gt_labels, dict) else gt_labels
+            cam_mat = xl_loss.get_cam_mat(image_w, image_h, float(focals[0]))        # the first frame's, as make_step
+            _, _, grad = xl_loss.task_loss_and_output_gradient(
+                'coord', opt.uncertainty, predictions, network.num_task_channel, gt_coords, gt_poses, pixel_grid, cam_mat,
+                nodata_value, opt.mindepth, opt.softclamp, opt.hardclamp, opt.inittolerance)
+            beta = opt.init_weight
+        # the depth label is -1 where nothing was measured; the RGB-D solver takes 0 for that
+        depth = gt_labels['depth'][:, 0].clamp_min(0.0) if rgbd else None
+        seed, image0 = e2e_keys(opt.seed, (image0,), step_index)     # image0: the first frame's dataset index
+        loss, stats, grad = xl_loss.expected_pose_loss_and_output_gradient(
+            predictions, gt_poses, focals, image_h, image_w, opt.hypotheses, opt.threshold, opt.inlieralpha,
+            opt.maxpixelerror, opt.weightrot, opt.weighttrans, opt.softclamp, seed, image0=image0,
+            clip_norm=opt.clip_norm, weight=1.0, grad=grad, beta=beta, depth=depth, rgbd_threshold=opt.threshold,
+            max_dist_error=opt.maxpixelerror, subsample=sub)
+        predictions.backward(grad)
+        if world_size > 1:
+            allreduce_flat_gradients(network, world_size, group, host_reduce)
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=True)          # no view of the gradient buffer outlives the step
+        return loss, stats[-1]
+
+    return step
+
+
 def epoch_batches(n, epoch, batch_size, rank=0, world_size=1, seed=SAMPLER_SEED):
     """The frames of every step of one epoch for `rank`: a permutation of range(n) seeded by (seed, epoch), the same on
     every rank, cut into `world_size` disjoint shards of n // world_size frames (the tail is dropped so that every rank
@@ -258,10 +309,12 @@ def _set_rng_state(st):
 
 class Trainer:
     """The loop of train_single_task.py:207-326 over a CamLocDataset(augment=True), data parallel over `world_size`
-    ranks.  `iteration` counts frames over all ranks (the reference's counter); a de-facto epoch is len(dataset) frames."""
+    ranks.  `iteration` counts frames over all ranks (the reference's counter); a de-facto epoch is len(dataset) frames.
+    `e2e`: the loop takes make_e2e_step's step (end-to-end DSAC* training, `opt` from train_e2e.py) in place of make_step's;
+    sampler, schedule, checkpoints and resume are the same."""
 
     def __init__(self, network, dataset, task, opt, output_dir, ckpt_dir, device, rank=0, world_size=1, group=None,
-                 host_reduce=False, num_workers=0):
+                 host_reduce=False, num_workers=0, e2e=False):
         self.network, self.dataset, self.task, self.opt = network, dataset, task, opt
         self.output_dir, self.ckpt_dir, self.device = output_dir, ckpt_dir, device
         self.rank, self.world_size, self.num_workers = rank, world_size, num_workers
@@ -270,14 +323,19 @@ class Trainer:
             self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, [999999], gamma=1.0)
         else:
             self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, [50, 100], gamma=0.5)
-        self.step_fn = make_step(network, task, self.optimizer, opt.uncertainty, get_nodata_value(opt.scene),
-                                 opt.mindepth, opt.softclamp, opt.hardclamp, opt.inittolerance, world_size, group,
-                                 host_reduce)
+        self.e2e = e2e
+        if e2e:
+            self.step_fn = make_e2e_step(network, self.optimizer, opt, world_size, group, host_reduce)
+        else:
+            self.step_fn = make_step(network, task, self.optimizer, opt.uncertainty, get_nodata_value(opt.scene),
+                                     opt.mindepth, opt.softclamp, opt.hardclamp, opt.inittolerance, world_size, group,
+                                     host_reduce)
         self.save_period = 1 if task == 'semantics' else 5
         self.model_path = os.path.join(output_dir, 'model.net')
         self.state = dict(iteration=0, epoch=0, batch=0, steps=0, save_counter=0, epoch_de_facto=0, last_ckpt=0,
                           seed=SAMPLER_SEED)
-        self.recent = collections.deque(maxlen=1024)    # (loss, valid rate) device scalars of the latest steps
+        # (loss, valid rate) device scalars of the latest steps; e2e: (mean pose loss, summary row of the finishing op)
+        self.recent = collections.deque(maxlen=1024)
 
     def _save_network(self, path):
         if self.rank == 0:
@@ -305,16 +363,17 @@ class Trainer:
             path, self.state["iteration"], self.state["epoch"], self.state["batch"]))
 
     def _batches(self, epoch):
+        """(dataset indices, collated batch on the device) of every remaining step of `epoch`."""
         idx = epoch_batches(len(self.dataset), epoch, self.opt.batch_size, self.rank, self.world_size, self.state["seed"])
         idx = idx[self.state["batch"]:] if epoch == self.state["epoch"] else idx
         if self.num_workers > 0:
             loader = torch.utils.data.DataLoader(self.dataset, batch_sampler=idx, num_workers=self.num_workers,
                                                  pin_memory=True, collate_fn=self.dataset.collate_host)
-            for host in loader:
-                yield self.dataset.to_gpu(host, self.device, self.network.OUTPUT_SUBSAMPLE)
+            for b, host in zip(idx, loader):
+                yield b, self.dataset.to_gpu(host, self.device, self.network.OUTPUT_SUBSAMPLE)
         else:
             for b in idx:
-                yield self.dataset.collate_gpu([self.dataset[i] for i in b], self.device, self.network.OUTPUT_SUBSAMPLE)
+                yield b, self.dataset.collate_gpu([self.dataset[i] for i in b], self.device, self.network.OUTPUT_SUBSAMPLE)
 
     def run(self):
         opt, st, n = self.opt, self.state, len(self.dataset)
@@ -331,18 +390,27 @@ class Trainer:
             if epoch != st["epoch"]:
                 st["epoch"], st["batch"] = epoch, 0
             t0 = time.time()
-            for images, gt_poses, gt_labels, focal_lengths, _ in self._batches(epoch):
+            for b, (images, gt_poses, gt_labels, focal_lengths, _) in self._batches(epoch):
                 # augmentation changes the input size from batch to batch: keep the current size's plans only
                 self.network.drop_plans_except(images.shape[0], images.shape[2], images.shape[3])
-                loss, rate = self.step_fn(images, gt_poses, gt_labels, float(focal_lengths.view(-1)[0]))
+                if self.e2e:
+                    loss, rate = self.step_fn(images, gt_poses, gt_labels, focal_lengths, st["steps"], image0=b[0])
+                else:
+                    loss, rate = self.step_fn(images, gt_poses, gt_labels, float(focal_lengths.view(-1)[0]))
                 self.recent.append((loss, rate))
                 st["batch"] += 1
                 st["steps"] += 1
                 st["iteration"] += len(images) * self.world_size
                 if st["steps"] % log_interval == 0:
                     dt = (time.time() - t0) / (log_interval * len(images))
-                    logging.info('Iteration: %7d, Epoch: %3d, Total loss: %.2f, Valid: %.1f%%, Avg Time: %.3fs' % (
-                        st["iteration"], epoch, loss.item(), float(rate) * 100, dt))
+                    if self.e2e:
+                        mean_loss, accepted, max_norm, clipped = rate.tolist()
+                        logging.info('Iteration: %7d, Epoch: %3d, Pose loss: %.4f, Accepted: %d/%d, Max norm: %.4g, '
+                                     'Clipped: %d, Avg Time: %.3fs' % (st["iteration"], epoch, mean_loss, accepted,
+                                                                       len(images), max_norm, clipped, dt))
+                    else:
+                        logging.info('Iteration: %7d, Epoch: %3d, Total loss: %.2f, Valid: %.1f%%, Avg Time: %.3fs' % (
+                            st["iteration"], epoch, loss.item(), float(rate) * 100, dt))
                     t0 = time.time()
                 snapshot = st["iteration"] > st["save_counter"]                 # train_single_task.py:309-315
                 if snapshot:
@@ -372,9 +440,10 @@ class Trainer:
                 torch.save(None, os.path.join(self.ckpt_dir, 'FLAG_training_done.nodata'))
 
 
-def common_parser(description, sim_data_chunk_default):
+def common_parser(description, sim_data_chunk_default, task=None):
     """The options shared by train_single_task.py:32-117 and finetune_decoder_single_task.py:29-136 (same names and
-    defaults), plus this driver's own: --scene_dir, --output_dir, --max_steps, --log_interval."""
+    defaults), plus this driver's own: --scene_dir, --output_dir, --max_steps, --log_interval.  `task`: the default of
+    --task for an entry point with one task (the option is required otherwise, as in the reference)."""
     import argparse
     p = argparse.ArgumentParser(description=description, formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument('scene', help='name of a scene in the dataset folder')
@@ -384,7 +453,7 @@ def common_parser(description, sim_data_chunk_default):
     p.add_argument('--real_data_chunk', type=float, default=1.0)
     p.add_argument('--real_only', action='store_true')
     p.add_argument('--sim_data_chunk', type=float, default=sim_data_chunk_default)
-    p.add_argument('--task', type=str, required=True)
+    p.add_argument('--task', type=str, required=task is None, default=task)
     p.add_argument('--epoch_plus', '-epoch_plus', action='store_true')
     p.add_argument('--network_in', type=str, default=None)
     p.add_argument('--tiny', '-tiny', action='store_true')
@@ -436,8 +505,9 @@ def data_suffix(opt, pairs_name, sim_only_name='-sim_only'):
     return s
 
 
-def run(opt, basename, encoders_in=None):
-    """Both entry points after option parsing: process group, logging, dataset, network, Trainer."""
+def run(opt, basename, encoders_in=None, e2e=False, dataset_options=None):
+    """The entry points after option parsing: process group, logging, dataset, network, Trainer.  `e2e`: the Trainer takes
+    the end-to-end step; `dataset_options`: keyword arguments of CamLocDataset that replace this function's own."""
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -476,8 +546,10 @@ def run(opt, basename, encoders_in=None):
         scene_dir = opt.scene_dir or os.path.join('datasets', scene)
         from .dataset import CamLocDataset
         dirs = get_training_dirs(scene_dir, opt.real_data_domain, opt.real_data_chunk, opt.sim_data_chunk, opt.real_only)
-        dataset = CamLocDataset(dirs, coord=opt.task == 'coord', depth=opt.task == 'depth', normal=opt.task == 'normal',
-                                semantics=opt.task == 'semantics', augment=True, grayscale=opt.grayscale)
+        data_kw = dict(coord=opt.task == 'coord', depth=opt.task == 'depth', normal=opt.task == 'normal',
+                       semantics=opt.task == 'semantics', augment=True, grayscale=opt.grayscale)
+        data_kw.update(dataset_options or {})
+        dataset = CamLocDataset(dirs, **data_kw)
         logging.info("This training uses {:d} frames from {}; {:d} frames per rank and epoch.".format(
             len(dataset), dirs, len(dataset) // world))
         if len(dataset) < world:
@@ -493,7 +565,7 @@ def run(opt, basename, encoders_in=None):
         workers = switches.live("XL_TRAIN_WORKERS")
         workers = min(6, (os.cpu_count() or 2) // 2) if workers is None else int(workers)
         trainer = Trainer(network, dataset, opt.task, opt, output_dir, ckpt_dir, dev, rank, world, group,
-                          host_reduce=shared, num_workers=workers)
+                          host_reduce=shared, num_workers=workers, e2e=e2e)
         if resume_path:
             trainer.load_resume(resume_path)
         trainer.run()
