@@ -227,6 +227,44 @@ struct AugArgs {
     float fill;
 };
 
+// one output pixel `rem` of frame `b`, all channels, under the rotation record (r00, r10, r01, r11): the per-pixel
+// arithmetic of both augmentation kernels
+__device__ __forceinline__ void augment_pixel(const AugArgs &a, float r00, float r10, float r01, float r11, int b, int rem)
+{
+    const long long plane = (long long)a.oh * a.ow;
+    const int i = rem / a.ow, jx = rem - i * a.ow;
+    // rotation: source pixel of the resized frame (grid_sample nearest, align_corners = false)
+    const float X = (float)jx + 0.5f - (float)a.ow * 0.5f, Y = (float)i + 0.5f - (float)a.oh * 0.5f;
+    const float gx = X * r00 + Y * r10, gy = X * r01 + Y * r11;
+    const float sx = ((gx + 1.f) * (float)a.ow - 1.f) / 2.f, sy = ((gy + 1.f) * (float)a.oh - 1.f) / 2.f;
+    const int ix = (int)rintf(sx), iy = (int)rintf(sy);
+    const bool inside = ix >= 0 && ix < a.ow && iy >= 0 && iy < a.oh;
+    const float *src = a.in + (long long)b * a.C * a.H * a.W;
+    float *dst = a.out + (long long)b * a.C * plane + rem;
+    if (!inside) {
+        for (int c = 0; c < a.C; ++c) dst[c * plane] = a.fill;
+        return;
+    }
+    if (a.bilinear) {                                 // upsample_bilinear2d, align_corners = false
+        float fy = a.scaleH * ((float)iy + 0.5f) - 0.5f, fx = a.scaleW * ((float)ix + 0.5f) - 0.5f;
+        if (fy < 0.f) fy = 0.f;
+        if (fx < 0.f) fx = 0.f;
+        const int y0 = (int)fy, x0 = (int)fx;
+        const int yp = y0 < a.H - 1 ? 1 : 0, xp = x0 < a.W - 1 ? 1 : 0;
+        const float ly = fy - (float)y0, lx = fx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        for (int c = 0; c < a.C; ++c) {
+            const float *q = src + ((long long)c * a.H + y0) * a.W + x0;
+            dst[c * plane] = hy * (hx * q[0] + lx * q[xp]) + ly * (hx * q[(long long)yp * a.W] + lx * q[(long long)yp * a.W + xp]);
+        }
+    } else {                                          // F.interpolate 'nearest': floor(dst * scale)
+        int y0 = (int)floorf((float)iy * a.scaleH), x0 = (int)floorf((float)ix * a.scaleW);
+        if (y0 > a.H - 1) y0 = a.H - 1;
+        if (x0 > a.W - 1) x0 = a.W - 1;
+        for (int c = 0; c < a.C; ++c) dst[c * plane] = src[((long long)c * a.H + y0) * a.W + x0];
+    }
+}
+
 __global__ __launch_bounds__(256)
 void batch_augment_kernel(AugArgs a)
 {
@@ -234,39 +272,60 @@ void batch_augment_kernel(AugArgs a)
     const long long total = (long long)a.B * plane;
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
         const int b = (int)(p / plane);
-        const int rem = (int)(p - (long long)b * plane);
-        const int i = rem / a.ow, jx = rem - i * a.ow;
-        // rotation: source pixel of the resized frame (grid_sample nearest, align_corners = false)
-        const float X = (float)jx + 0.5f - (float)a.ow * 0.5f, Y = (float)i + 0.5f - (float)a.oh * 0.5f;
-        const float gx = X * a.r00 + Y * a.r10, gy = X * a.r01 + Y * a.r11;
-        const float sx = ((gx + 1.f) * (float)a.ow - 1.f) / 2.f, sy = ((gy + 1.f) * (float)a.oh - 1.f) / 2.f;
-        const int ix = (int)rintf(sx), iy = (int)rintf(sy);
-        const bool inside = ix >= 0 && ix < a.ow && iy >= 0 && iy < a.oh;
-        const float *src = a.in + (long long)b * a.C * a.H * a.W;
-        float *dst = a.out + (long long)b * a.C * plane + rem;
-        if (!inside) {
-            for (int c = 0; c < a.C; ++c) dst[c * plane] = a.fill;
-            continue;
-        }
-        if (a.bilinear) {                                 // upsample_bilinear2d, align_corners = false
-            float fy = a.scaleH * ((float)iy + 0.5f) - 0.5f, fx = a.scaleW * ((float)ix + 0.5f) - 0.5f;
-            if (fy < 0.f) fy = 0.f;
-            if (fx < 0.f) fx = 0.f;
-            const int y0 = (int)fy, x0 = (int)fx;
-            const int yp = y0 < a.H - 1 ? 1 : 0, xp = x0 < a.W - 1 ? 1 : 0;
-            const float ly = fy - (float)y0, lx = fx - (float)x0;
-            const float hy = 1.f - ly, hx = 1.f - lx;
-            for (int c = 0; c < a.C; ++c) {
-                const float *q = src + ((long long)c * a.H + y0) * a.W + x0;
-                dst[c * plane] = hy * (hx * q[0] + lx * q[xp]) + ly * (hx * q[(long long)yp * a.W] + lx * q[(long long)yp * a.W + xp]);
-            }
-        } else {                                          // F.interpolate 'nearest': floor(dst * scale)
-            int y0 = (int)floorf((float)iy * a.scaleH), x0 = (int)floorf((float)ix * a.scaleW);
-            if (y0 > a.H - 1) y0 = a.H - 1;
-            if (x0 > a.W - 1) x0 = a.W - 1;
-            for (int c = 0; c < a.C; ++c) dst[c * plane] = src[((long long)c * a.H + y0) * a.W + x0];
-        }
+        augment_pixel(a, a.r00, a.r10, a.r01, a.r11, b, (int)(p - (long long)b * plane));
     }
+}
+
+// One rotation per frame.  The records ride in the kernel arguments like the jitter records above (1 KB for 64 frames;
+// larger mini-batches run in chunks of 64); a workgroup's 256 pixels may straddle two frames, so a lane reads the
+// record of its own pixel's frame.  AugArgs::r00..r11 are unused here.
+constexpr int kRotMax = 64;
+struct RotPack { float4 r[kRotMax]; };                // (r00, r10, r01, r11) of each frame
+
+__global__ __launch_bounds__(256)
+void batch_augment_frames_kernel(AugArgs a, RotPack rot)
+{
+    const long long plane = (long long)a.oh * a.ow;
+    const long long total = (long long)a.B * plane;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+        const int b = (int)(p / plane);
+        const float4 r = rot.r[b];
+        augment_pixel(a, r.x, r.y, r.z, r.w, b, (int)(p - (long long)b * plane));
+    }
+}
+
+// rescaled inverse rotation of torchvision's `rotate` by angle_deg for an oh x ow frame: the inverse affine matrix of
+// -angle as float32, divided by the half sizes in float32
+void rotation_record(double angle_deg, int oh, int ow, float &r00, float &r10, float &r01, float &r11)
+{
+    const double th = angle_deg * (3.14159265358979323846 / 180.0);    // math.radians: x * (pi / 180)
+    const float c = (float)cos(th), s = (float)sin(th);                // (float)(-sin) == -(float)sin: rounding is symmetric
+    r00 = c / (0.5f * (float)ow);
+    r10 = -s / (0.5f * (float)ow);
+    r01 = s / (0.5f * (float)oh);
+    r11 = c / (0.5f * (float)oh);
+}
+
+// ---------------------------------------------------------------------------------------------- pose rotation
+
+struct PoseRot { double c, s; };
+struct PoseRotPack { PoseRot r[kRotMax]; };           // cos / sin of each frame's angle, from the host
+
+// P * Rz(theta) per frame, one thread per matrix row: col0' = c col0 + s col1, col1' = -s col0 + c col1 in float64, rounded
+// to float32 once; columns 2 and 3 are copied.  A thread reads its row before it writes it: out may alias in.
+__global__ __launch_bounds__(256)
+void rotate_poses_kernel(const float *in, float *out, int B, PoseRotPack rot)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= B * 4) return;
+    const PoseRot r = rot.r[t >> 2];
+    const float m0 = in[4 * t], m1 = in[4 * t + 1], m2 = in[4 * t + 2], m3 = in[4 * t + 3];
+    float o0 = m0, o1 = m1;
+    if (!(r.c == 1.0 && r.s == 0.0)) {                // angle 0: the input bit for bit (signed zeros included)
+        o0 = (float)(r.c * (double)m0 + r.s * (double)m1);
+        o1 = (float)(-r.s * (double)m0 + r.c * (double)m1);
+    }
+    out[4 * t] = o0; out[4 * t + 1] = o1; out[4 * t + 2] = m2; out[4 * t + 3] = m3;
 }
 
 unsigned grid_for(long long items)
@@ -380,15 +439,52 @@ int xl_data_batch_augment(const float *in, float *out, int B, int C, int H, int 
     if (!in || !out || B < 1 || C < 1 || H < 1 || W < 1 || oh < 1 || ow < 1) return XL_ERR_ARG;
     AugArgs a;
     a.in = in; a.out = out; a.B = B; a.C = C; a.H = H; a.W = W; a.oh = oh; a.ow = ow; a.bilinear = bilinear; a.fill = fill;
-    const double th = angle_deg * (3.14159265358979323846 / 180.0);    // math.radians: x * (pi / 180)
-    // torchvision: inverse affine matrix of -angle as float32, divided by the half sizes in float32
-    a.r00 = (float)cos(th) / (0.5f * (float)ow);
-    a.r10 = (float)(-sin(th)) / (0.5f * (float)ow);
-    a.r01 = (float)sin(th) / (0.5f * (float)oh);
-    a.r11 = (float)cos(th) / (0.5f * (float)oh);
+    rotation_record(angle_deg, oh, ow, a.r00, a.r10, a.r01, a.r11);
     a.scaleH = (float)H / (float)oh;
     a.scaleW = (float)W / (float)ow;
     hipLaunchKernelGGL(batch_augment_kernel, dim3(grid_for((long long)B * oh * ow)), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
+
+int xl_data_batch_augment_frames(const float *in, float *out, int B, int C, int H, int W, int oh, int ow,
+                                 const double *angles_deg_host, float fill, int bilinear, void *stream)
+{
+    if (!in || !out || !angles_deg_host || B < 1 || C < 1 || H < 1 || W < 1 || oh < 1 || ow < 1) return XL_ERR_ARG;
+    AugArgs a;
+    a.C = C; a.H = H; a.W = W; a.oh = oh; a.ow = ow; a.bilinear = bilinear; a.fill = fill;
+    a.r00 = a.r10 = a.r01 = a.r11 = 0.f;
+    a.scaleH = (float)H / (float)oh;
+    a.scaleW = (float)W / (float)ow;
+    for (int b0 = 0; b0 < B; b0 += kRotMax) {                          // the rotation records ride in the kernel arguments
+        const int nb = B - b0 < kRotMax ? B - b0 : kRotMax;
+        RotPack pack;
+        for (int b = 0; b < kRotMax; ++b) {
+            pack.r[b] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (b < nb) rotation_record(angles_deg_host[b0 + b], oh, ow, pack.r[b].x, pack.r[b].y, pack.r[b].z, pack.r[b].w);
+        }
+        a.in = in + (long long)b0 * C * H * W;
+        a.out = out + (long long)b0 * C * oh * ow;
+        a.B = nb;
+        hipLaunchKernelGGL(batch_augment_frames_kernel, dim3(grid_for((long long)nb * oh * ow)), dim3(256), 0, (hipStream_t)stream,
+                           a, pack);
+    }
+    return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
+
+int xl_data_rotate_poses(const float *poses_in, float *poses_out, int B, const double *angles_deg_host, void *stream)
+{
+    if (!poses_in || !poses_out || !angles_deg_host || B < 1) return XL_ERR_ARG;
+    for (int b0 = 0; b0 < B; b0 += kRotMax) {
+        const int nb = B - b0 < kRotMax ? B - b0 : kRotMax;
+        PoseRotPack pack;
+        for (int b = 0; b < kRotMax; ++b) {
+            const double th = b < nb ? angles_deg_host[b0 + b] * (3.14159265358979323846 / 180.0) : 0.0;
+            pack.r[b].c = cos(th);
+            pack.r[b].s = sin(th);
+        }
+        hipLaunchKernelGGL(rotate_poses_kernel, dim3((unsigned)((nb * 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           poses_in + (long long)b0 * 16, poses_out + (long long)b0 * 16, nb, pack);
+    }
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
 }
 

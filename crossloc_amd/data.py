@@ -6,6 +6,7 @@ import ctypes
 import math
 import random
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -30,6 +31,10 @@ def _bind():
         L.xl_data_prepare_images_gray.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
         L.xl_data_batch_augment.restype = ci
         L.xl_data_batch_augment.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.c_double, cf, ci, vp]
+        L.xl_data_batch_augment_frames.restype = ci
+        L.xl_data_batch_augment_frames.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, ci, vp]
+        L.xl_data_rotate_poses.restype = ci
+        L.xl_data_rotate_poses.argtypes = [vp, vp, ci, vp, vp]
         L._data_bound = True
     return L
 
@@ -85,18 +90,61 @@ def prepare_images(frames_u8, image_height=480, jitter=None, normalize=True, gra
     return out
 
 
+def _angle_array(angles_deg, B):
+    """A sequence of B angles as the host array of doubles the per-frame entry points read."""
+    angles = [float(v) for v in angles_deg]
+    if len(angles) != B:
+        raise RuntimeError("expected %d angles, got %d" % (B, len(angles)))
+    return (ctypes.c_double * B)(*angles)
+
+
 def batch_augment(x, out_h, out_w, angle_deg, fill, bilinear):
     """x float32 GPU [B,C,H,W] -> [B,C,out_h,out_w]: resize (bilinear like F.interpolate(align_corners=False) for
-    images, 'nearest' for label maps) composed with torchvision's nearest-neighbour `rotate` by angle_deg."""
+    images, 'nearest' for label maps) composed with torchvision's nearest-neighbour `rotate` by angle_deg: a float (one
+    rotation for the mini-batch) or a sequence of B floats (one per frame, xl_data_batch_augment_frames; frame b is then
+    bitwise what the float form gives for that frame alone)."""
     if not x.is_cuda:
         raise RuntimeError("crossloc_amd.data runs on the GPU only (no CPU fallback)")
     x = x.detach().to(torch.float32).contiguous()
     B, C, H, W = x.shape
+    per_frame = isinstance(angle_deg, (list, tuple)) or getattr(angle_deg, "ndim", 0) > 0      # (or an array of angles)
+    angles = _angle_array(angle_deg, B) if per_frame else None
     out = torch.empty((B, C, out_h, out_w), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(_bind().xl_data_batch_augment(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, C, H, W,
-                                                 int(out_h), int(out_w), float(angle_deg), float(fill), 1 if bilinear else 0, st))
+        if per_frame:
+            _lib.check(_bind().xl_data_batch_augment_frames(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, C, H,
+                                                            W, int(out_h), int(out_w), angles, float(fill), 1 if bilinear else 0, st))
+        else:
+            _lib.check(_bind().xl_data_batch_augment(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, C, H, W,
+                                                     int(out_h), int(out_w), float(angle_deg), float(fill), 1 if bilinear else 0, st))
+    return out
+
+
+def pose_rotation(angle_deg):
+    """Rz(theta), numpy float64 [4,4]: the pose of a frame rotated by batch_augment(angle_deg) (counter-clockwise about the
+    image centre) is P @ pose_rotation(angle_deg) for the cam->world matrix P (the reference's pose_rot,
+    dataloader.py:430-438).  The host restatement of xl_data_rotate_poses."""
+    th = float(angle_deg) * (math.pi / 180.0)
+    r = np.eye(4)
+    r[0, 0], r[0, 1], r[1, 0], r[1, 1] = math.cos(th), -math.sin(th), math.sin(th), math.cos(th)
+    return r
+
+
+def rotate_poses(poses, angles_deg):
+    """poses float32 GPU [B,4,4] (cam->world, any strides) -> a new tensor P[b] @ pose_rotation(angles_deg[b]): the products
+    in float64, rounded to float32 once; an angle of 0 leaves its pose bit for bit."""
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise RuntimeError("rotate_poses expects a tensor [B,4,4]")
+    if not poses.is_cuda:
+        raise RuntimeError("crossloc_amd.data runs on the GPU only (no CPU fallback)")
+    p = poses.detach().to(torch.float32).contiguous()
+    B = p.shape[0]
+    angles = _angle_array(angles_deg, B)
+    out = torch.empty((B, 4, 4), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_bind().xl_data_rotate_poses(ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, angles, st))
     return out
 
 
@@ -106,7 +154,7 @@ def batch_resize(images, labels, focal_lengths, scale_factor, angle_deg, output_
     multi-label form, :553-563; non-tensor entries pass through as 0); focal lengths are multiplied by the scale (:535).
     Label maps are resized to ceil(image / output_subsample) and filled with -1 outside the rotated frame; a semantics
     map follows the image size and is filled with 0 (:545-547).  The ground-truth poses are NOT rotated in this path
-    (the reference only rotates them in its per-item path, :455-464) - reproduced as is."""
+    (the reference only rotates them in its per-item path, :430-438) - reproduced as is; batch_resize_posed rotates them."""
     H, W = images.shape[2], images.shape[3]
     image_h, image_w = math.ceil(H * scale_factor), math.ceil(W * scale_factor)
     out_images = batch_augment(images, image_h, image_w, angle_deg, -1.0, True)
@@ -121,3 +169,12 @@ def batch_resize(images, labels, focal_lengths, scale_factor, angle_deg, output_
     else:
         out_labels = one(labels, semantics)
     return out_images, out_labels, [f * scale_factor for f in focal_lengths]
+
+
+def batch_resize_posed(images, labels, poses, focal_lengths, scale_factor, angles_deg, output_subsample=8, semantics=False):
+    """batch_resize with one rotation per frame and the poses that go with it: the common scale, sizes, fills and label
+    dict of batch_resize, frame b rotated by angles_deg[b], and poses [B,4,4] -> P[b] @ pose_rotation(angles_deg[b]).
+    Returns (images, labels, poses, focals).  Normal vectors of a 'normal' label map are resampled, not rotated."""
+    angles = [float(v) for v in angles_deg]
+    out_images, out_labels, focals = batch_resize(images, labels, focal_lengths, scale_factor, angles, output_subsample, semantics)
+    return out_images, out_labels, rotate_poses(poses, angles), focals

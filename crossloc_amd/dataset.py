@@ -20,11 +20,18 @@ Covered: mode=1 / sparse labels.
     DataLoader's collate_fn) uploads the frames once and runs resize, colour jitter, ToTensor, normalisation and the
     common scale + rotation of the mini-batch on the GPU (crossloc_amd/data.py, csrc/xl_data.hip).  Random draws follow
     the reference: one (brightness, contrast) pair per frame, one (scale, angle) pair per mini-batch from `random`.
+    The reference's batched path leaves the ground-truth poses of the rotated frames alone (it rotates them in its per-item
+    path only, :430-438), and so does this one by default.  rotate_poses=True: one scale per mini-batch, then one angle
+    PER FRAME (`draw_geometry`: 1 + B draws from `random`), frames and label maps rotated frame by frame, and each pose
+    returned as P * Rz(angle) (data.batch_resize_posed, include/crossloc_data.h) - what a pose loss or the reprojection
+    term of the coord loss needs.
 Semantics labels (round 3): read with numpy, trimmed to the 6 training classes (loss.trim_semantic_label), float [1,H,W];
   collate_gpu resizes them to the IMAGE size with 'nearest' and rotates them with fill 0 (:540-543).  Grayscale (round 3):
   Resize -> Grayscale -> [ColorJitter] -> ToTensor -> Normalize(0.4308, 0.1724) (:171-187, 359-373), one channel.
-Not covered: augment=True with batch=False (per-item scale / rotation with a rotated pose, :349-464: no CrossLoc
-training script uses it), dense-depth initialisation (sparse=False), mode 0 / 2.
+Not covered: augment=True with batch=False (per-item scale / rotation, :349-464: no CrossLoc training script uses it;
+rotate_poses=True gives its rotated poses in the batched path), a scale per frame (the frames of a mini-batch share a
+size), rotation of the VECTORS of a normal label map (the augmentation resamples the map and leaves its vectors as they
+are, as the reference does), dense-depth initialisation (sparse=False), mode 0 / 2.
 collate_gpu makes GPU calls: it must run in the main process (DataLoader(num_workers=0), or - to keep the reference's CPU
 worker parallelism for PNG decoding, utils/learning.py:238-252 - workers with `collate_host` and `to_gpu` on the fetched
 batch in the training loop).
@@ -47,7 +54,7 @@ def _sorted_files(d):
 class CamLocDataset(Dataset):
     def __init__(self, root_dir, mode=1, sparse=True, coord=True, depth=False, normal=False, semantics=False,
                  augment=False, grayscale=False, batch=True, raw_image=False, aug_rotation=30, aug_scale_min=2 / 3,
-                 aug_scale_max=3 / 2, aug_contrast=0.1, aug_brightness=0.1, image_height=480, **unused):
+                 aug_scale_max=3 / 2, aug_contrast=0.1, aug_brightness=0.1, image_height=480, rotate_poses=False, **unused):
         if mode != 1 or not sparse:
             raise NotImplementedError("only mode=1 with sparse labels is read (the configuration CrossLoc uses)")
         if raw_image:
@@ -57,6 +64,7 @@ class CamLocDataset(Dataset):
         self.augment, self.batch = augment, batch
         self.aug_rotation, self.aug_scale_min, self.aug_scale_max = aug_rotation, aug_scale_min, aug_scale_max
         self.aug_contrast, self.aug_brightness = aug_contrast, aug_brightness
+        self.rotate_poses = bool(rotate_poses)             # one rotation per frame, poses rotated with the frames
         if not (coord or depth or normal or semantics):
             raise Exception("At least one 3D label should be enabled! Coord: {}, Depth: {}, Normal: {}".format(
                 coord, depth, normal))
@@ -139,10 +147,21 @@ class CamLocDataset(Dataset):
             labels = torch.stack([it[2] for it in batch])
         return frames, poses, labels, [it[3] for it in batch], [it[4] for it in batch]
 
+    def draw_geometry(self, n):
+        """The scale and rotation draws of a mini-batch of n frames from `random` (host only) -> (scale, angles): one
+        scale, then one angle (a float) for the mini-batch, the reference's two draws (:525-526) - or, with rotate_poses,
+        a list of n angles, one per frame in frame order: 1 + n draws."""
+        import random
+        scale_factor = random.uniform(self.aug_scale_min, self.aug_scale_max)      # :525-526, one draw per mini-batch
+        if not self.rotate_poses:
+            return scale_factor, random.uniform(-self.aug_rotation, self.aug_rotation)
+        return scale_factor, [random.uniform(-self.aug_rotation, self.aug_rotation) for _ in range(n)]
+
     def to_gpu(self, host_batch, device="cuda", output_subsample=8):
         """The GPU half of `batch_resize` (dataloader.py:512-586) on a batch stacked by `collate_host`: upload once as
         bytes, then resize, (grayscale,) colour jitter, ToTensor, normalisation and the common scale + rotation of the
-        mini-batch as HIP kernels.  Main process only."""
+        mini-batch as HIP kernels; with rotate_poses, one rotation per frame and the poses rotated with their frames.
+        Main process only."""
         from . import data
         frames, poses, labels, focals, files = host_batch
         frames = frames.to(device, non_blocking=True)
@@ -153,11 +172,13 @@ class CamLocDataset(Dataset):
             labels = labels.to(device, non_blocking=True)
         jitter = [data.draw_jitter(self.aug_brightness, self.aug_contrast) for _ in files]
         images = data.prepare_images(frames, self.image_height, jitter=jitter, normalize=True, grayscale=self.grayscale)
-        import random
-        scale_factor = random.uniform(self.aug_scale_min, self.aug_scale_max)      # :525-526, one draw per mini-batch
-        angle = random.uniform(-self.aug_rotation, self.aug_rotation)
-        images, labels, focals = data.batch_resize(images, labels, list(focals), scale_factor, angle, output_subsample,
-                                                   semantics=self.semantics)
+        scale_factor, angles = self.draw_geometry(len(files))
+        if self.rotate_poses:
+            images, labels, poses, focals = data.batch_resize_posed(images, labels, poses, list(focals), scale_factor, angles,
+                                                                    output_subsample, semantics=self.semantics)
+        else:
+            images, labels, focals = data.batch_resize(images, labels, list(focals), scale_factor, angles, output_subsample,
+                                                       semantics=self.semantics)
         return images, poses, labels, torch.tensor(focals, dtype=torch.float64), files
 
     def collate_gpu(self, batch, device="cuda", output_subsample=8):

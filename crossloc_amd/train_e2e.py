@@ -9,10 +9,15 @@ solver's.  Their defaults follow DSAC*'s published train_e2e.py; the CrossLoc re
 defaults, not parity claims.  --network_in is required: the expected pose loss only has a useful gradient around an
 initialised network.  --init_weight w > 0 keeps the coord loss in the step, w * coord gradient + pose gradient.
 
-Augmentation: colour jitter and the per-batch scale stay; rotation is OFF - the batched augmentation does not rotate the
-ground-truth poses (as the reference's, data.batch_resize), and a pose loss on rotated frames would be wrong.  --mode rgbd
-reads the depth labels, takes --threshold and --maxpixelerror in centimetres, and fixes the scale to 1: the RGB-D kernels
-take at most dsacstar.RGBD_MAX_CELLS cells (60 x 90 fits, 90 x 135 does not).
+Augmentation: colour jitter and the per-batch scale always; in-plane rotation with --aug_rotation DEG (default 0: none;
+DSAC*'s own recipe trains with 30).  Each frame of a mini-batch then draws its own angle in +-DEG, frame and label maps are
+rotated by it, and the ground-truth pose becomes P * Rz(angle) (CamLocDataset(rotate_poses=True), data.batch_resize_posed),
+so the pose loss sees the pose of the frame it is given.  The reference's batched augmentation, and this package's default,
+rotate the frames of a mini-batch by one common angle and leave the poses alone - no input for a pose loss, which is why
+the default here is no rotation.  --mode rgbd reads the depth labels, takes --threshold and --maxpixelerror in
+centimetres, and fixes the scale to 1: the RGB-D kernels take at most dsacstar.RGBD_MAX_CELLS cells (60 x 90 fits, 90 x 135
+does not); its depth label rotates like any label map (fill -1: nothing measured), the depth along the optical axis being
+what an in-plane rotation leaves unchanged.
 
 See crossloc_amd/training.py (make_e2e_step, Trainer) and loss.expected_pose_loss_and_output_gradient.
 """
@@ -37,6 +42,8 @@ def _parser():
                    help='clip the pose gradient of a frame to this norm (0: no clipping)')
     p.add_argument('--init_weight', type=float, default=0.0,
                    help='weight of the coord loss kept in the step (0: the pose loss alone)')
+    p.add_argument('--aug_rotation', type=float, default=0.0, metavar='DEG',
+                   help='rotate each frame by its own angle in +-DEG, and its ground-truth pose with it (0: no rotation)')
     p.add_argument('--seed', type=int, default=RANSAC_SEED, help="the sampler's seed; step k draws with seed + k")
     return p
 
@@ -50,14 +57,19 @@ def _config_parser(argv=None):
         p.error("--network_in is required: end-to-end training starts from an initialised network")
     if opt.fullsize:
         p.error("--fullsize: the solver works on the 8x subsampled grid")
+    if opt.aug_rotation < 0:
+        p.error("--aug_rotation is the half width of the angle range: it cannot be negative")
     if opt.real_only:
         assert opt.sim_data_chunk == 0
     return opt
 
 
 def dataset_options(opt):
-    """What the end-to-end step needs of CamLocDataset: no rotation; --mode rgbd: the depth labels and the scale fixed to 1."""
+    """What the end-to-end step needs of CamLocDataset: no rotation, or with --aug_rotation one per frame with the poses
+    rotated along; --mode rgbd: the depth labels and the scale fixed to 1."""
     kw = dict(coord=True, depth=opt.mode == 'rgbd', aug_rotation=0)
+    if opt.aug_rotation > 0:
+        kw.update(aug_rotation=opt.aug_rotation, rotate_poses=True)
     if opt.mode == 'rgbd':
         kw.update(aug_scale_min=1, aug_scale_max=1)
     return kw
@@ -73,6 +85,8 @@ def get_output_path(opt):
     b += '-no_unc' if opt.uncertainty is None else '-unc-{:s}'.format(opt.uncertainty)
     b += '-e{:d}-lr{:.8f}'.format(opt.epochs, opt.learningrate)
     b += training.data_suffix(opt, '-pairs')
+    if opt.aug_rotation > 0:
+        b += '-rot{:g}'.format(opt.aug_rotation)
     if opt.tiny:
         b += '-tiny'
     if opt.debug:

@@ -477,6 +477,9 @@ def common_parser(description, sim_data_chunk_default, task=None):
     p.add_argument('--max_steps', type=int, default=None, help='stop after this many optimiser steps in total')
     p.add_argument('--log_interval', type=int, default=20,
                    help='iterations between log lines (the only points where the step synchronises with the host)')
+    p.add_argument('--rotate_poses', action='store_true',
+                   help="coord task: draw one rotation per frame and rotate the ground-truth poses with the frames "
+                        "(CamLocDataset(rotate_poses=True)); off: one rotation per mini-batch, poses untouched, as the reference")
     return p
 
 
@@ -490,6 +493,9 @@ def finish_options(opt):
     assert opt.uncertainty in [None, 'MLE'], '--uncertainty {} is not supported!'.format(opt.uncertainty)
     assert opt.real_data_domain in ['in_place', 'out_of_place'], \
         '--real_data_domain {:} is not supported!'.format(opt.real_data_domain)
+    if opt.rotate_poses and opt.task != 'coord':
+        # the other tasks do not read the poses, and the augmentation does not rotate the vectors of a normal map
+        raise ValueError('--rotate_poses is for the coord task, not --task {:s}'.format(opt.task))
     return opt
 
 
@@ -548,6 +554,8 @@ def run(opt, basename, encoders_in=None, e2e=False, dataset_options=None):
         dirs = get_training_dirs(scene_dir, opt.real_data_domain, opt.real_data_chunk, opt.sim_data_chunk, opt.real_only)
         data_kw = dict(coord=opt.task == 'coord', depth=opt.task == 'depth', normal=opt.task == 'normal',
                        semantics=opt.task == 'semantics', augment=True, grayscale=opt.grayscale)
+        if opt.rotate_poses:
+            data_kw.update(rotate_poses=True)
         data_kw.update(dataset_options or {})
         dataset = CamLocDataset(dirs, **data_kw)
         logging.info("This training uses {:d} frames from {}; {:d} frames per rank and epoch.".format(

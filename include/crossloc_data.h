@@ -55,6 +55,23 @@ int xl_data_prepare_images_gray(const uint8_t *src, int B, int Hs, int Ws, int C
 int xl_data_batch_augment(const float *in, float *out, int B, int C, int H, int W, int oh, int ow,
                           double angle_deg, float fill, int bilinear, void *stream);
 
+/* xl_data_batch_augment with one angle per frame, the whole batch in one launch (64 frames per launch: the rotation
+ * records travel as kernel arguments, like the jitter records).  angles_deg_host: host array of B doubles, free to
+ * release when the call returns.  Frame b equals xl_data_batch_augment of that frame alone with angles_deg_host[b],
+ * bit for bit: the same per-pixel device code under the same four float32 rotation entries. */
+int xl_data_batch_augment_frames(const float *in, float *out, int B, int C, int H, int W, int oh, int ow,
+                                 const double *angles_deg_host, float fill, int bilinear, void *stream);
+
+/* The ground-truth poses of frames rotated by xl_data_batch_augment[_frames].  poses_in / poses_out: float32
+ * [B][4][4] row-major cam->world matrices; poses_out may alias poses_in.  The rotation above is counter-clockwise
+ * about the image centre by theta = angle * (pi / 180); the pose of the rotated frame is P * Rz(theta),
+ *     Rz(theta) = [[c, -s, 0, 0], [s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]],  c = cos(theta), s = sin(theta)
+ * (the reference's pose_rot, dataloader.py:430-438), so only columns 0 and 1 change:
+ *     col0' = c col0 + s col1,  col1' = -s col0 + c col1
+ * with c and s from the host's cos / sin in double, the sums in float64, one rounding to float32.  Angle 0 returns the
+ * input bit for bit.  angles_deg_host: host array of B doubles, free to release when the call returns. */
+int xl_data_rotate_poses(const float *poses_in, float *poses_out, int B, const double *angles_deg_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
