@@ -5,6 +5,7 @@
 // three channels of a pixel together, consecutive lanes on consecutive pixels.
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdint.h>
 #include <map>
 #include <mutex>
@@ -227,16 +228,25 @@ struct AugArgs {
     float fill;
 };
 
+// source position (sx, sy), in pixel-centre coordinates of the oh x ow frame, of output pixel `rem` under the record
+// (r00, r10, r01, r11): grid_sample's affine grid and its un-normalisation (align_corners = false), float32 in this order
+__device__ __forceinline__ void rotated_source(const AugArgs &a, float r00, float r10, float r01, float r11, int rem,
+                                               float &sx, float &sy)
+{
+    const int i = rem / a.ow, jx = rem - i * a.ow;
+    const float X = (float)jx + 0.5f - (float)a.ow * 0.5f, Y = (float)i + 0.5f - (float)a.oh * 0.5f;
+    const float gx = X * r00 + Y * r10, gy = X * r01 + Y * r11;
+    sx = ((gx + 1.f) * (float)a.ow - 1.f) / 2.f;
+    sy = ((gy + 1.f) * (float)a.oh - 1.f) / 2.f;
+}
+
 // one output pixel `rem` of frame `b`, all channels, under the rotation record (r00, r10, r01, r11): the per-pixel
 // arithmetic of both augmentation kernels
 __device__ __forceinline__ void augment_pixel(const AugArgs &a, float r00, float r10, float r01, float r11, int b, int rem)
 {
     const long long plane = (long long)a.oh * a.ow;
-    const int i = rem / a.ow, jx = rem - i * a.ow;
-    // rotation: source pixel of the resized frame (grid_sample nearest, align_corners = false)
-    const float X = (float)jx + 0.5f - (float)a.ow * 0.5f, Y = (float)i + 0.5f - (float)a.oh * 0.5f;
-    const float gx = X * r00 + Y * r10, gy = X * r01 + Y * r11;
-    const float sx = ((gx + 1.f) * (float)a.ow - 1.f) / 2.f, sy = ((gy + 1.f) * (float)a.oh - 1.f) / 2.f;
+    float sx, sy;
+    rotated_source(a, r00, r10, r01, r11, rem, sx, sy);
     const int ix = (int)rintf(sx), iy = (int)rintf(sy);
     const bool inside = ix >= 0 && ix < a.ow && iy >= 0 && iy < a.oh;
     const float *src = a.in + (long long)b * a.C * a.H * a.W;
@@ -291,6 +301,63 @@ void batch_augment_frames_kernel(AugArgs a, RotPack rot)
         const int b = (int)(p / plane);
         const float4 r = rot.r[b];
         augment_pixel(a, r.x, r.y, r.z, r.w, b, (int)(p - (long long)b * plane));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- fixed-size canvas
+//
+// A scale and a rotation per frame onto a canvas of the frame's own size (include/crossloc_data.h).  The record of a frame is
+// its rotation record times (float)(1 / scale): the zoom about the centre rides in the four entries, so the source position
+// is rotated_source() unchanged.  Label maps (bilinear = 0) are augment_pixel's nearest path under that record.  Images take
+// ONE bilinear sample at the source position itself (not a nearest rotation of a resized frame): a streaming gather, lanes
+// on consecutive output pixels read along a line of the source, the taps of neighbouring lanes share cache lines.
+struct CanvasPack { float4 r[kRotMax]; unsigned long long identity; };    // bit b: frame b is scale 1, angle 0
+
+__device__ __forceinline__ void canvas_bilinear_pixel(const AugArgs &a, float4 r, int b, int rem)
+{
+    const long long plane = (long long)a.H * a.W;
+    float sx, sy;
+    rotated_source(a, r.x, r.y, r.z, r.w, rem, sx, sy);
+    const int ix = (int)rintf(sx), iy = (int)rintf(sy);
+    const float *src = a.in + (long long)b * a.C * plane;
+    float *dst = a.out + (long long)b * a.C * plane + rem;
+    if (!(ix >= 0 && ix < a.W && iy >= 0 && iy < a.H)) {                  // the inside rule of the label maps
+        for (int c = 0; c < a.C; ++c) dst[c * plane] = a.fill;
+        return;
+    }
+    // inside: sx in [-0.5, W - 0.5], so the taps floor(sx), floor(sx) + 1 lie in [-1, W]: clamped to the edge
+    const float fx = floorf(sx), fy = floorf(sy);
+    const float lx = sx - fx, ly = sy - fy;
+    const float hx = 1.f - lx, hy = 1.f - ly;
+    int x0 = (int)fx, y0 = (int)fy;
+    int x1 = x0 + 1, y1 = y0 + 1;
+    x0 = x0 < 0 ? 0 : x0; y0 = y0 < 0 ? 0 : y0;
+    x1 = x1 > a.W - 1 ? a.W - 1 : x1; y1 = y1 > a.H - 1 ? a.H - 1 : y1;
+    const long long o00 = (long long)y0 * a.W + x0, o01 = (long long)y0 * a.W + x1;
+    const long long o10 = (long long)y1 * a.W + x0, o11 = (long long)y1 * a.W + x1;
+    for (int c = 0; c < a.C; ++c) {
+        const float *q = src + c * plane;
+        dst[c * plane] = hy * (hx * q[o00] + lx * q[o01]) + ly * (hx * q[o10] + lx * q[o11]);
+    }
+}
+
+__global__ __launch_bounds__(256)
+void canvas_augment_kernel(AugArgs a, CanvasPack rot)
+{
+    const long long plane = (long long)a.H * a.W;
+    const long long total = (long long)a.B * plane;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < total; p += (long long)gridDim.x * 256) {
+        const int b = (int)(p / plane);
+        const int rem = (int)(p - (long long)b * plane);
+        if ((rot.identity >> b) & 1ull) {                                 // scale 1, angle 0: the input bit for bit
+            const float *src = a.in + (long long)b * a.C * plane + rem;
+            float *dst = a.out + (long long)b * a.C * plane + rem;
+            for (int c = 0; c < a.C; ++c) dst[c * plane] = src[c * plane];
+            continue;
+        }
+        const float4 r = rot.r[b];
+        if (a.bilinear) canvas_bilinear_pixel(a, r, b, rem);
+        else augment_pixel(a, r.x, r.y, r.z, r.w, b, rem);
     }
 }
 
@@ -466,6 +533,39 @@ int xl_data_batch_augment_frames(const float *in, float *out, int B, int C, int 
         a.out = out + (long long)b0 * C * oh * ow;
         a.B = nb;
         hipLaunchKernelGGL(batch_augment_frames_kernel, dim3(grid_for((long long)nb * oh * ow)), dim3(256), 0, (hipStream_t)stream,
+                           a, pack);
+    }
+    return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
+
+int xl_data_canvas_augment(const float *in, float *out, int B, int C, int H, int W,
+                           const double *scales_host, const double *angles_deg_host, float fill, int bilinear, void *stream)
+{
+    if (!in || !out || in == out || !scales_host || !angles_deg_host || B < 1 || C < 1 || H < 1 || W < 1) return XL_ERR_ARG;
+    if ((long long)H * W > 0x7fffffffLL) return XL_ERR_ARG;
+    for (int b = 0; b < B; ++b)
+        if (!std::isfinite(scales_host[b]) || !(scales_host[b] > 0.0) || !std::isfinite(angles_deg_host[b])) return XL_ERR_ARG;
+    AugArgs a;
+    a.C = C; a.H = H; a.W = W; a.oh = H; a.ow = W; a.bilinear = bilinear ? 1 : 0; a.fill = fill;
+    a.r00 = a.r10 = a.r01 = a.r11 = 0.f;
+    a.scaleH = a.scaleW = 1.f;                                         // the canvas has the frame's size
+    for (int b0 = 0; b0 < B; b0 += kRotMax) {                          // the records ride in the kernel arguments
+        const int nb = B - b0 < kRotMax ? B - b0 : kRotMax;
+        CanvasPack pack;
+        pack.identity = 0;
+        for (int b = 0; b < kRotMax; ++b) {
+            pack.r[b] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (b >= nb) continue;
+            const double scale = scales_host[b0 + b], angle = angles_deg_host[b0 + b];
+            rotation_record(angle, H, W, pack.r[b].x, pack.r[b].y, pack.r[b].z, pack.r[b].w);
+            const float zoom = (float)(1.0 / scale);
+            pack.r[b].x *= zoom; pack.r[b].y *= zoom; pack.r[b].z *= zoom; pack.r[b].w *= zoom;
+            if (scale == 1.0 && angle == 0.0) pack.identity |= 1ull << b;
+        }
+        a.in = in + (long long)b0 * C * H * W;
+        a.out = out + (long long)b0 * C * H * W;
+        a.B = nb;
+        hipLaunchKernelGGL(canvas_augment_kernel, dim3(grid_for((long long)nb * H * W)), dim3(256), 0, (hipStream_t)stream,
                            a, pack);
     }
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;

@@ -69,6 +69,7 @@ __device__ void inverse_rows3(const float *m, float *P /*12*/)
 
 struct CoordArgs {
     const float *pred, *unc, *poses, *gt;
+    const float *focals;              // [B] one focal length per image, or NULL: `f` for every image
     float *dpred, *dunc;
     double *partials;
     int B, Ho, Wo, N, nblk, mode;
@@ -84,6 +85,7 @@ void coord_loss_kernel(CoordArgs a)
     const int b = blockIdx.y;
     if (threadIdx.x == 0) inverse_rows3(a.poses + b * 16, sP);
     __syncthreads();
+    const float f = a.focals ? a.focals[b] : a.f;     // the image's own focal length (uniform over the workgroup)
     const int i = blockIdx.x * kT + threadIdx.x;
     Sums s{ 0.0, 0.0, 0.0, 0.0 };
     if (i < a.N) {
@@ -101,7 +103,7 @@ void coord_loss_kernel(CoordArgs a)
         const float dx = xc - xg, dy = yc - yg, dz = zc - zg;
         const float d = sqrtf(dx * dx + dy * dy + dz * dz);                                   // coord.py:120
         // get_repro_err (coord.py:41-57)
-        const float px = a.f * xc + a.cx * zc, py = a.f * yc + a.cy * zc, pz = zc;
+        const float px = f * xc + a.cx * zc, py = f * yc + a.cy * zc, pz = zc;
         const float zt = fmaxf(pz, a.minDepth);
         const float u = px / zt, v = py / zt;
         const int yy = i / a.Wo, xx = i - yy * a.Wo;
@@ -149,7 +151,7 @@ void coord_loss_kernel(CoordArgs a)
             const float gpx = gu / zt, gpy = gv / zt;
             float gpz = 0.f;
             if (pz >= a.minDepth) gpz = -(gu * px + gv * py) / (zt * zt);
-            float gxc = a.f * gpx, gyc = a.f * gpy, gzc = a.cx * gpx + a.cy * gpy + gpz;
+            float gxc = f * gpx, gyc = f * gpy, gzc = a.cx * gpx + a.cy * gpy + gpz;
             if (d > 0.f) { const float k = dLdd / d; gxc += k * dx; gyc += k * dy; gzc += k * dz; }
             a.dpred[pbase] = (sP[0] * gxc + sP[4] * gyc + sP[8] * gzc) * a.gscale;
             a.dpred[pbase + a.N] = (sP[1] * gxc + sP[5] * gyc + sP[9] * gzc) * a.gscale;
@@ -431,16 +433,17 @@ int xl_loss_coord(const float *pred, const float *unc, const float *gt_poses, co
                             hard_clamp, init_tolerance, nodata, mode, per_image_scale, dpred, dunc, workspace, out, stream);
 }
 
-int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
-                     int B, int Ho, int Wo, int ld_pred, int ld_unc, float focal, float cx, float cy, float subsample,
-                     float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
-                     int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream)
+// both coord entries: `focals` (device [B]) when given, else `focal` for every image
+static int coord_launch(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                        int B, int Ho, int Wo, int ld_pred, int ld_unc, float focal, const float *focals, float cx, float cy,
+                        float subsample, float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
+                        int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream)
 {
     if (ld_pred < 3 || ld_unc < 1) return XL_ERR_ARG;
     if (!pred || !gt_poses || !gt_coords || !workspace || !out || B <= 0 || Ho <= 0 || Wo <= 0) return XL_ERR_ARG;
     if (mode == 1 && !unc) return XL_ERR_ARG;
     CoordArgs a;
-    a.pred = pred; a.unc = unc; a.poses = gt_poses; a.gt = gt_coords; a.dpred = dpred; a.dunc = dunc;
+    a.pred = pred; a.unc = unc; a.poses = gt_poses; a.gt = gt_coords; a.focals = focals; a.dpred = dpred; a.dunc = dunc;
     a.partials = workspace; a.B = B; a.Ho = Ho; a.Wo = Wo; a.N = Ho * Wo; a.nblk = (a.N + kT - 1) / kT; a.mode = mode;
     a.f = focal; a.cx = cx; a.cy = cy; a.sub = subsample; a.minDepth = min_depth; a.soft = soft_clamp;
     a.hard = hard_clamp; a.tol = init_tolerance; a.nodata = nodata;
@@ -450,6 +453,26 @@ int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses,
     hipLaunchKernelGGL(coord_loss_kernel, dim3(a.nblk, B), dim3(kT), 0, st, a);
     hipLaunchKernelGGL(finalize_kernel, dim3(1), dim3(256), 0, st, workspace, B, a.nblk, a.N, 1, out);
     return launch_ok();
+}
+
+int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                     int B, int Ho, int Wo, int ld_pred, int ld_unc, float focal, float cx, float cy, float subsample,
+                     float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
+                     int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream)
+{
+    return coord_launch(pred, unc, gt_poses, gt_coords, B, Ho, Wo, ld_pred, ld_unc, focal, nullptr, cx, cy, subsample, min_depth,
+                        soft_clamp, hard_clamp, init_tolerance, nodata, mode, per_image_scale, dpred, dunc, workspace, out, stream);
+}
+
+int xl_loss_coord_frames_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                            int B, int Ho, int Wo, int ld_pred, int ld_unc, const float *focals, float cx, float cy,
+                            float subsample, float min_depth, float soft_clamp, float hard_clamp, float init_tolerance,
+                            float nodata, int mode, int per_image_scale, float *dpred, float *dunc, double *workspace,
+                            float *out, void *stream)
+{
+    if (!focals) return XL_ERR_ARG;
+    return coord_launch(pred, unc, gt_poses, gt_coords, B, Ho, Wo, ld_pred, ld_unc, 0.f, focals, cx, cy, subsample, min_depth,
+                        soft_clamp, hard_clamp, init_tolerance, nodata, mode, per_image_scale, dpred, dunc, workspace, out, stream);
 }
 
 int xl_loss_depth(const float *pred, const float *unc, const float *gt_depth, int B, int Ho, int Wo,

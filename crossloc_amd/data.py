@@ -35,6 +35,8 @@ def _bind():
         L.xl_data_batch_augment_frames.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, ci, vp]
         L.xl_data_rotate_poses.restype = ci
         L.xl_data_rotate_poses.argtypes = [vp, vp, ci, vp, vp]
+        L.xl_data_canvas_augment.restype = ci
+        L.xl_data_canvas_augment.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, cf, ci, vp]
         L._data_bound = True
     return L
 
@@ -121,6 +123,29 @@ def batch_augment(x, out_h, out_w, angle_deg, fill, bilinear):
     return out
 
 
+def canvas_augment(x, scales, angles_deg, fill, bilinear):
+    """x float32 GPU [B,C,H,W] -> the same shape: frame b zoomed by scales[b] and rotated by angles_deg[b] (the sense of
+    batch_augment) about the image centre onto a canvas of its own size (xl_data_canvas_augment).  bilinear: one bilinear
+    sample at the source position (images); else the nearest source cell (label maps); `fill` where the nearest source cell
+    is outside.  A frame with scale 1 and angle 0 comes back bit for bit."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise RuntimeError("canvas_augment expects a tensor [B,C,H,W]")
+    if not x.is_cuda:
+        raise RuntimeError("crossloc_amd.data runs on the GPU only (no CPU fallback)")
+    x = x.detach().to(torch.float32).contiguous()
+    B, C, H, W = x.shape
+    s = [float(v) for v in scales]
+    if len(s) != B:
+        raise RuntimeError("expected %d scales, got %d" % (B, len(s)))
+    angles = _angle_array(angles_deg, B)
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_bind().xl_data_canvas_augment(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(out.data_ptr()), B, C, H, W,
+                                                  (ctypes.c_double * B)(*s), angles, float(fill), 1 if bilinear else 0, st))
+    return out
+
+
 def pose_rotation(angle_deg):
     """Rz(theta), numpy float64 [4,4]: the pose of a frame rotated by batch_augment(angle_deg) (counter-clockwise about the
     image centre) is P @ pose_rotation(angle_deg) for the cam->world matrix P (the reference's pose_rot,
@@ -178,3 +203,26 @@ def batch_resize_posed(images, labels, poses, focal_lengths, scale_factor, angle
     angles = [float(v) for v in angles_deg]
     out_images, out_labels, focals = batch_resize(images, labels, focal_lengths, scale_factor, angles, output_subsample, semantics)
     return out_images, out_labels, rotate_poses(poses, angles), focals
+
+
+def batch_canvas(images, labels, poses, focal_lengths, scales, angles_deg, output_subsample=8, semantics=False):
+    """Fixed-size augmentation of a mini-batch: frame b zoomed by scales[b] and rotated by angles_deg[b] about the image
+    centre onto a canvas of its own size (canvas_augment), so no tensor changes its shape.  Images: bilinear, fill -1; label
+    maps (a tensor or a dict, as batch_resize): nearest, fill -1, each on its own grid; a semantics map: nearest, fill 0, at
+    image size; poses [B,4,4] -> P[b] @ pose_rotation(angles_deg[b]); focal lengths times the frame's scale.  Returns
+    (images, labels, poses, focals).  Normal vectors of a 'normal' label map are resampled, not rotated.
+    `output_subsample` is not needed (every map keeps its grid); it is accepted so that the call reads like batch_resize."""
+    scales = [float(v) for v in scales]
+    angles = [float(v) for v in angles_deg]
+    focal_lengths = list(focal_lengths)
+    if len(focal_lengths) != len(scales):
+        raise RuntimeError("expected %d focal lengths, got %d" % (len(scales), len(focal_lengths)))
+    out_images = canvas_augment(images, scales, angles, -1.0, True)
+
+    def one(t, is_sem):
+        return canvas_augment(t, scales, angles, 0.0 if is_sem else -1.0, False)
+    if isinstance(labels, dict):
+        out_labels = {k: (one(v, semantics and k == "semantics") if isinstance(v, torch.Tensor) else 0) for k, v in labels.items()}
+    else:
+        out_labels = one(labels, semantics)
+    return out_images, out_labels, rotate_poses(poses, angles), [f * s for f, s in zip(focal_lengths, scales)]

@@ -25,13 +25,17 @@ Covered: mode=1 / sparse labels.
     PER FRAME (`draw_geometry`: 1 + B draws from `random`), frames and label maps rotated frame by frame, and each pose
     returned as P * Rz(angle) (data.batch_resize_posed, include/crossloc_data.h) - what a pose loss or the reprojection
     term of the coord loss needs.
+    canvas=True (fixed-size augmentation): one scale AND one angle per frame (`draw_geometry`: 2 B draws from `random`), each
+    frame and its label maps warped about the image centre onto a canvas of their own size (data.batch_canvas,
+    xl_data_canvas_augment), so every tensor keeps its shape from batch to batch and the network keeps one plan; the focal
+    length of frame b becomes f_b * scale_b and its pose P_b * Rz(angle_b).  Minification takes one bilinear sample without an
+    anti-alias filter, as the reference's F.interpolate does.
 Semantics labels (round 3): read with numpy, trimmed to the 6 training classes (loss.trim_semantic_label), float [1,H,W];
   collate_gpu resizes them to the IMAGE size with 'nearest' and rotates them with fill 0 (:540-543).  Grayscale (round 3):
   Resize -> Grayscale -> [ColorJitter] -> ToTensor -> Normalize(0.4308, 0.1724) (:171-187, 359-373), one channel.
 Not covered: augment=True with batch=False (per-item scale / rotation, :349-464: no CrossLoc training script uses it;
-rotate_poses=True gives its rotated poses in the batched path), a scale per frame (the frames of a mini-batch share a
-size), rotation of the VECTORS of a normal label map (the augmentation resamples the map and leaves its vectors as they
-are, as the reference does), dense-depth initialisation (sparse=False), mode 0 / 2.
+rotate_poses=True gives its rotated poses in the batched path, canvas=True its scale per frame), rotation of the VECTORS
+of a normal label map (the augmentation resamples the map and leaves its vectors as they are, as the reference does), dense-depth initialisation (sparse=False), mode 0 / 2.
 collate_gpu makes GPU calls: it must run in the main process (DataLoader(num_workers=0), or - to keep the reference's CPU
 worker parallelism for PNG decoding, utils/learning.py:238-252 - workers with `collate_host` and `to_gpu` on the fetched
 batch in the training loop).
@@ -54,7 +58,8 @@ def _sorted_files(d):
 class CamLocDataset(Dataset):
     def __init__(self, root_dir, mode=1, sparse=True, coord=True, depth=False, normal=False, semantics=False,
                  augment=False, grayscale=False, batch=True, raw_image=False, aug_rotation=30, aug_scale_min=2 / 3,
-                 aug_scale_max=3 / 2, aug_contrast=0.1, aug_brightness=0.1, image_height=480, rotate_poses=False, **unused):
+                 aug_scale_max=3 / 2, aug_contrast=0.1, aug_brightness=0.1, image_height=480, rotate_poses=False, canvas=False,
+                 **unused):
         if mode != 1 or not sparse:
             raise NotImplementedError("only mode=1 with sparse labels is read (the configuration CrossLoc uses)")
         if raw_image:
@@ -65,6 +70,9 @@ class CamLocDataset(Dataset):
         self.aug_rotation, self.aug_scale_min, self.aug_scale_max = aug_rotation, aug_scale_min, aug_scale_max
         self.aug_contrast, self.aug_brightness = aug_contrast, aug_brightness
         self.rotate_poses = bool(rotate_poses)             # one rotation per frame, poses rotated with the frames
+        self.canvas = bool(canvas)                         # a scale and a rotation per frame at a fixed tensor size
+        if self.canvas and not (augment and batch):
+            raise ValueError("canvas=True is an augmentation of the batched path: it needs augment=True, batch=True")
         if not (coord or depth or normal or semantics):
             raise Exception("At least one 3D label should be enabled! Coord: {}, Depth: {}, Normal: {}".format(
                 coord, depth, normal))
@@ -150,8 +158,15 @@ class CamLocDataset(Dataset):
     def draw_geometry(self, n):
         """The scale and rotation draws of a mini-batch of n frames from `random` (host only) -> (scale, angles): one
         scale, then one angle (a float) for the mini-batch, the reference's two draws (:525-526) - or, with rotate_poses,
-        a list of n angles, one per frame in frame order: 1 + n draws."""
+        a list of n angles, one per frame in frame order: 1 + n draws.  With canvas: (scales, angles), two lists of n, drawn
+        frame by frame - scale_b, then angle_b: always 2 n draws, also at aug_rotation = 0."""
         import random
+        if self.canvas:
+            scales, angles = [], []
+            for _ in range(n):
+                scales.append(random.uniform(self.aug_scale_min, self.aug_scale_max))
+                angles.append(random.uniform(-self.aug_rotation, self.aug_rotation))
+            return scales, angles
         scale_factor = random.uniform(self.aug_scale_min, self.aug_scale_max)      # :525-526, one draw per mini-batch
         if not self.rotate_poses:
             return scale_factor, random.uniform(-self.aug_rotation, self.aug_rotation)
@@ -160,7 +175,8 @@ class CamLocDataset(Dataset):
     def to_gpu(self, host_batch, device="cuda", output_subsample=8):
         """The GPU half of `batch_resize` (dataloader.py:512-586) on a batch stacked by `collate_host`: upload once as
         bytes, then resize, (grayscale,) colour jitter, ToTensor, normalisation and the common scale + rotation of the
-        mini-batch as HIP kernels; with rotate_poses, one rotation per frame and the poses rotated with their frames.
+        mini-batch as HIP kernels; with rotate_poses, one rotation per frame and the poses rotated with their frames; with
+        canvas, a scale and a rotation per frame at a fixed size, per-frame focal lengths and rotated poses.
         Main process only."""
         from . import data
         frames, poses, labels, focals, files = host_batch
@@ -173,7 +189,10 @@ class CamLocDataset(Dataset):
         jitter = [data.draw_jitter(self.aug_brightness, self.aug_contrast) for _ in files]
         images = data.prepare_images(frames, self.image_height, jitter=jitter, normalize=True, grayscale=self.grayscale)
         scale_factor, angles = self.draw_geometry(len(files))
-        if self.rotate_poses:
+        if self.canvas:
+            images, labels, poses, focals = data.batch_canvas(images, labels, poses, list(focals), scale_factor, angles,
+                                                              output_subsample, semantics=self.semantics)
+        elif self.rotate_poses:
             images, labels, poses, focals = data.batch_resize_posed(images, labels, poses, list(focals), scale_factor, angles,
                                                                     output_subsample, semantics=self.semantics)
         else:

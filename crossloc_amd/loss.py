@@ -129,11 +129,20 @@ def _run(kind, launch_args_fn, pred, unc, reduction):
     return loss, out[1]
 
 
+def _frame_focals(focals, B, device):
+    """One focal length per image as the float32 device array [B] xl_loss_coord_frames_ld reads."""
+    f = torch.as_tensor(focals).detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+    if f.numel() != B:
+        raise RuntimeError("expected %d focal lengths, got %d" % (B, f.numel()))
+    return f
+
+
 def scene_coords_regression_loss(min_depth, soft_clamp, hard_clamp, init_tolerance, uncertainty,
                                  pixel_grid, nodata_value, cam_mat,
-                                 scene_coords, uncertainty_map, gt_poses, gt_coords, reduction='mean'):
+                                 scene_coords, uncertainty_map, gt_poses, gt_coords, reduction='mean', focals=None):
     """loss/coord.py:87-188.  pixel_grid / cam_mat as returned by get_pixel_grid / get_cam_mat above (host
-    tensors; device tensors are accepted at the price of one D2H read)."""
+    tensors; device tensors are accepted at the price of one D2H read).  focals: one focal length per image (sequence or
+    tensor of B) in place of cam_mat's, which still supplies cx and cy; None: cam_mat's for every image, as the reference."""
     mode = _mode(uncertainty)
     cm = cam_mat.detach().cpu()
     pg = pixel_grid[:, 0, :2].detach().cpu()
@@ -143,8 +152,14 @@ def scene_coords_regression_loss(min_depth, soft_clamp, hard_clamp, init_toleran
     gt = _prep(gt_coords)
     B, _, Ho, Wo = scene_coords.shape
     unc = uncertainty_map if mode == 1 else None
+    fb = _frame_focals(focals, B, scene_coords.device) if focals is not None else None
 
     def args(L, p32, u32, per_image, dpred, dunc, ws, out, stream):
+        if fb is not None:
+            return _bind_ld().xl_loss_coord_frames_ld(
+                _ptr(p32), _ptr(u32), _ptr(poses), _ptr(gt), B, Ho, Wo, 3, 1, _ptr(fb), cx, cy, sub, float(min_depth),
+                float(soft_clamp), float(hard_clamp), float(init_tolerance), float(nodata_value), mode, per_image, _ptr(dpred),
+                _ptr(dunc), _ptr(ws), _ptr(out), stream)
         return L.xl_loss_coord(_ptr(p32), _ptr(u32), _ptr(poses), _ptr(gt), B, Ho, Wo, f, cx, cy, sub,
                                float(min_depth), float(soft_clamp), float(hard_clamp), float(init_tolerance),
                                float(nodata_value), mode, per_image, _ptr(dpred), _ptr(dunc), _ptr(ws), _ptr(out), stream)
@@ -243,6 +258,9 @@ def _bind_ld():
         L.xl_loss_coord_ld.restype = ci
         L.xl_loss_coord_ld.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, cf, cf, cf, cf, cf, ci, ci,
                                        vp, vp, vp, vp, vp]
+        L.xl_loss_coord_frames_ld.restype = ci
+        L.xl_loss_coord_frames_ld.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, cf, cf, cf, cf, cf, cf, cf, cf, ci, ci,
+                                              vp, vp, vp, vp, vp]
         L.xl_loss_depth_ld.restype = ci
         L.xl_loss_depth_ld.argtypes = [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, ci, vp, vp, vp, vp, vp]
         L.xl_loss_normal_ld.restype = ci
@@ -253,12 +271,13 @@ def _bind_ld():
 
 def task_loss_and_output_gradient(task, uncertainty, prediction, num_task_channel, gt_labels, gt_poses=None,
                                   pixel_grid=None, cam_mat=None, nodata_value=-1, min_depth=0.1, soft_clamp=100.0,
-                                  hard_clamp=1000.0, init_tolerance=50.0):
+                                  hard_clamp=1000.0, init_tolerance=50.0, focals=None):
     """The four losses of train_single_task.py:274-296 (reduction 'mean') in the form the training step uses: the kernels
     read the network output `prediction` [B, num_task_channel (+1 uncertainty channel), H, W] in place - no torch.split
     copies - and write d loss / d prediction into ONE tensor of its shape, ready for prediction.backward(grad) - no
     autograd node of the loss, hence no gradient scaling or concatenation kernels.  Returns (loss, valid_rate, grad);
-    loss and valid_rate are 0-dim device tensors.  Same values and gradients as the functions above."""
+    loss and valid_rate are 0-dim device tensors.  Same values and gradients as the functions above.  focals (coord task): one
+    focal length per image in place of cam_mat's (scene_coords_regression_loss)."""
     mode = _mode(uncertainty)
     p = prediction.detach()
     if not p.is_cuda:
@@ -276,6 +295,9 @@ def task_loss_and_output_gradient(task, uncertainty, prediction, num_task_channe
     L = _bind_ld()
     ws = torch.empty(L.xl_loss_workspace_doubles(B, Ho, Wo), dtype=torch.float64, device=dev)
     out = torch.empty(2 + B, dtype=torch.float32, device=dev)
+    if focals is not None and task != 'coord':
+        raise RuntimeError("focals belong to the coord task, not %s" % task)
+    fb = _frame_focals(focals, B, dev) if focals is not None else None
     unc = ctypes.c_void_p(p.data_ptr() + 4 * num_task_channel * N) if mode else None
     dunc = ctypes.c_void_p(grad.data_ptr() + 4 * num_task_channel * N) if mode else None
     pp, gp, wp, op = _ptr(p), _ptr(grad), _ptr(ws), _ptr(out)
@@ -286,10 +308,12 @@ def task_loss_and_output_gradient(task, uncertainty, prediction, num_task_channe
             pg = pixel_grid[:, 0, :2].detach().cpu()
             poses = _prep(gt_poses).reshape(-1, 16)
             gt = _prep(gt_labels)
-            rc = L.xl_loss_coord_ld(pp, unc, _ptr(poses), _ptr(gt), B, Ho, Wo, C, C, float(cm[0, 0]), float(cm[0, 2]),
-                                    float(cm[1, 2]), float(pg[0, 1] - pg[0, 0]), float(min_depth), float(soft_clamp),
-                                    float(hard_clamp), float(init_tolerance), float(nodata_value), mode, 0, gp, dunc, wp, op,
-                                    stream)
+            rest = (float(cm[0, 2]), float(cm[1, 2]), float(pg[0, 1] - pg[0, 0]), float(min_depth), float(soft_clamp),
+                    float(hard_clamp), float(init_tolerance), float(nodata_value), mode, 0, gp, dunc, wp, op, stream)
+            if fb is not None:
+                rc = L.xl_loss_coord_frames_ld(pp, unc, _ptr(poses), _ptr(gt), B, Ho, Wo, C, C, _ptr(fb), *rest)
+            else:
+                rc = L.xl_loss_coord_ld(pp, unc, _ptr(poses), _ptr(gt), B, Ho, Wo, C, C, float(cm[0, 0]), *rest)
         elif task == 'depth':
             gt = _prep(gt_labels)
             rc = L.xl_loss_depth_ld(pp, unc, _ptr(gt), B, Ho, Wo, C, C, float(min_depth), float(hard_clamp),

@@ -17,7 +17,10 @@ rotate the frames of a mini-batch by one common angle and leave the poses alone 
 the default here is no rotation.  --mode rgbd reads the depth labels, takes --threshold and --maxpixelerror in
 centimetres, and fixes the scale to 1: the RGB-D kernels take at most dsacstar.RGBD_MAX_CELLS cells (60 x 90 fits, 90 x 135
 does not); its depth label rotates like any label map (fill -1: nothing measured), the depth along the optical axis being
-what an in-plane rotation leaves unchanged.
+what an in-plane rotation leaves unchanged.  --aug_canvas: fixed-size augmentation (CamLocDataset(canvas=True),
+data.batch_canvas) - every frame draws its own scale and, with --aug_rotation DEG, its own angle (at 0: scale only), and is
+warped onto a canvas of its own size; the solver and the --init_weight coord term read one focal length per frame.  The
+label grid stays 60 x 90, so --mode rgbd keeps the scale range 2/3 - 3/2 with it.
 
 See crossloc_amd/training.py (make_e2e_step, Trainer) and loss.expected_pose_loss_and_output_gradient.
 """
@@ -66,8 +69,12 @@ def _config_parser(argv=None):
 
 def dataset_options(opt):
     """What the end-to-end step needs of CamLocDataset: no rotation, or with --aug_rotation one per frame with the poses
-    rotated along; --mode rgbd: the depth labels and the scale fixed to 1."""
+    rotated along; --mode rgbd: the depth labels and the scale fixed to 1.  --aug_canvas: a scale and an angle (in
+    +-aug_rotation, 0: none) per frame at a fixed size, in either mode with the dataset's own scale range."""
     kw = dict(coord=True, depth=opt.mode == 'rgbd', aug_rotation=0)
+    if opt.aug_canvas:
+        kw.update(aug_rotation=opt.aug_rotation, canvas=True)
+        return kw
     if opt.aug_rotation > 0:
         kw.update(aug_rotation=opt.aug_rotation, rotate_poses=True)
     if opt.mode == 'rgbd':
@@ -87,6 +94,8 @@ def get_output_path(opt):
     b += training.data_suffix(opt, '-pairs')
     if opt.aug_rotation > 0:
         b += '-rot{:g}'.format(opt.aug_rotation)
+    if opt.aug_canvas:
+        b += '-canvas'
     if opt.tiny:
         b += '-tiny'
     if opt.debug:

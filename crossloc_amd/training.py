@@ -164,19 +164,23 @@ def allreduce_flat_gradients(network, world_size, group=None, host=False):
 def make_step(network, task, optimizer, uncertainty=None, nodata_value=-1, mindepth=0.1, softclamp=100.0,
               hardclamp=1000.0, inittolerance=50.0, world_size=1, group=None, host_reduce=False):
     """One iteration of train_single_task.py:245-301 for `task`: step(images, gt_poses, gt_labels, focal_length) with
-    device tensors (focal_length: a float, the first frame's as the reference uses) -> (loss, valid_rate) device scalars."""
+    device tensors (focal_length: a float, the first frame's as the reference uses - or one focal length per frame, a
+    sequence or tensor of B, which the coord loss then applies frame by frame) -> (loss, valid_rate) device scalars."""
     if task not in TASK_CHANNELS:
         raise NotImplementedError(task)
     pixel_grid = xl_loss.get_pixel_grid(network.OUTPUT_SUBSAMPLE) if task == 'coord' else None
 
     def step(images, gt_poses, gt_labels, focal_length):
         predictions = network(images)
+        focals = None
+        if task == 'coord' and not isinstance(focal_length, (int, float)) and getattr(focal_length, 'ndim', 1) > 0:
+            focals, focal_length = focal_length, 1.0       # per frame: cam_mat only supplies the principal point
         cam_mat = xl_loss.get_cam_mat(images.size(3), images.size(2), focal_length) if task == 'coord' else None
         # the loss kernel reads the output in place and writes d loss / d output whole: the uncertainty split
         # (train_single_task.py:266-271) is a channel offset, and no autograd node of the loss launches anything
         loss, rate, grad = xl_loss.task_loss_and_output_gradient(
             task, uncertainty, predictions, network.num_task_channel, gt_labels, gt_poses, pixel_grid, cam_mat,
-            nodata_value, mindepth, softclamp, hardclamp, inittolerance)
+            nodata_value, mindepth, softclamp, hardclamp, inittolerance, focals=focals)
         predictions.backward(grad)
         if world_size > 1:
             allreduce_flat_gradients(network, world_size, group, host_reduce)
@@ -199,8 +203,10 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
     tensors (focals: one per frame, host or device; gt_labels: the coord labels, or a dict with 'coord' and, for --mode
     rgbd, 'depth') -> (mean expected pose loss, summary row of loss.E2E_SUMMARY_FIELDS), device tensors; nothing
     synchronises.  Forward, [the coord loss's output gradient times opt.init_weight,] the solver's backward pass and the
-    finishing op added onto it, backward, gradient all-reduce, fused Adam.  `opt`: the options of train_e2e.py."""
+    finishing op added onto it, backward, gradient all-reduce, fused Adam.  `opt`: the options of train_e2e.py.  With
+    opt.aug_canvas the frames carry their own scale: the coord term then reads one focal length per frame."""
     rgbd = opt.mode == 'rgbd'
+    canvas = bool(getattr(opt, 'aug_canvas', False))
     joint = opt.init_weight > 0
     sub = network.OUTPUT_SUBSAMPLE
     pixel_grid = xl_loss.get_pixel_grid(sub) if joint else None
@@ -213,10 +219,12 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
         grad, beta = None, 0.0
         if joint:
             gt_coords = gt_labels['coord'] if isinstance(gt_labels, dict) else gt_labels
-            cam_mat = xl_loss.get_cam_mat(image_w, image_h, float(focals[0]))        # the first frame's, as make_step
+            # the first frame's focal length, as make_step; canvas mode: cam_mat's is unused, each frame has its own
+            cam_mat = xl_loss.get_cam_mat(image_w, image_h, 1.0 if canvas else float(focals[0]))
             _, _, grad = xl_loss.task_loss_and_output_gradient(
                 'coord', opt.uncertainty, predictions, network.num_task_channel, gt_coords, gt_poses, pixel_grid, cam_mat,
-                nodata_value, opt.mindepth, opt.softclamp, opt.hardclamp, opt.inittolerance)
+                nodata_value, opt.mindepth, opt.softclamp, opt.hardclamp, opt.inittolerance,
+                focals=focals if canvas else None)
             beta = opt.init_weight
         # the depth label is -1 where nothing was measured; the RGB-D solver takes 0 for that
         depth = gt_labels['depth'][:, 0].clamp_min(0.0) if rgbd else None
@@ -395,6 +403,8 @@ class Trainer:
                 self.network.drop_plans_except(images.shape[0], images.shape[2], images.shape[3])
                 if self.e2e:
                     loss, rate = self.step_fn(images, gt_poses, gt_labels, focal_lengths, st["steps"], image0=b[0])
+                elif getattr(self.dataset, 'canvas', False):       # every frame has its own scale: all focal lengths
+                    loss, rate = self.step_fn(images, gt_poses, gt_labels, focal_lengths.view(-1))
                 else:
                     loss, rate = self.step_fn(images, gt_poses, gt_labels, float(focal_lengths.view(-1)[0]))
                 self.recent.append((loss, rate))
@@ -480,6 +490,10 @@ def common_parser(description, sim_data_chunk_default, task=None):
     p.add_argument('--rotate_poses', action='store_true',
                    help="coord task: draw one rotation per frame and rotate the ground-truth poses with the frames "
                         "(CamLocDataset(rotate_poses=True)); off: one rotation per mini-batch, poses untouched, as the reference")
+    p.add_argument('--aug_canvas', action='store_true',
+                   help="fixed-size augmentation: one scale and one rotation per frame onto a canvas of the frame's own size "
+                        "(CamLocDataset(canvas=True)): the input size never changes, the coord loss reads one focal length per "
+                        "frame and the rotated poses; off: one scale and rotation per mini-batch, as the reference")
     return p
 
 
@@ -556,6 +570,8 @@ def run(opt, basename, encoders_in=None, e2e=False, dataset_options=None):
                        semantics=opt.task == 'semantics', augment=True, grayscale=opt.grayscale)
         if opt.rotate_poses:
             data_kw.update(rotate_poses=True)
+        if getattr(opt, 'aug_canvas', False):
+            data_kw.update(canvas=True)
         data_kw.update(dataset_options or {})
         dataset = CamLocDataset(dirs, **data_kw)
         logging.info("This training uses {:d} frames from {}; {:d} frames per rank and epoch.".format(

@@ -18,6 +18,8 @@
  *   batch aug   images: bilinear resize (align_corners = false, like F.interpolate) to (oh, ow) composed with the
  *               nearest-neighbour rotation of torchvision's tensor `rotate` about the image centre, `fill` outside;
  *               labels: nearest resize (F.interpolate 'nearest') composed with the same rotation
+ *   canvas      a scale and a rotation per frame at a fixed size (xl_data_canvas_augment, below): no reference counterpart;
+ *               checked bit for bit against the float32 restatement tests/canvas_ref.py
  * All pointers are device pointers unless stated; calls are asynchronous on `stream` (the per-frame jitter records
  * travel as kernel arguments: the host arrays may be freed when a call returns) and return 0 or a negative xl
  * status (crossloc_dsac.h).  Frames of one call share their size (the reference's collate stacks them, :563).
@@ -61,6 +63,30 @@ int xl_data_batch_augment(const float *in, float *out, int B, int C, int H, int 
  * bit for bit: the same per-pixel device code under the same four float32 rotation entries. */
 int xl_data_batch_augment_frames(const float *in, float *out, int B, int C, int H, int W, int oh, int ow,
                                  const double *angles_deg_host, float fill, int bilinear, void *stream);
+
+/* Fixed-size augmentation: frame b is zoomed by scales_host[b] and rotated by angles_deg_host[b] (counter-clockwise, the
+ * sense of xl_data_batch_augment) about the image centre onto a canvas of its own size.  in / out: float32 [B][C][H][W],
+ * distinct buffers.  The principal point stays at the centre, the focal length of frame b becomes f_b * scale_b and its
+ * pose P_b * Rz(theta_b) (xl_data_rotate_poses).  Output pixel (i, j), X = j + 0.5 - W/2, Y = i + 0.5 - H/2, takes its
+ * value from the source position
+ *     sx = (c X - s Y) / scale + W/2 - 0.5,   sy = (s X + c Y) / scale + H/2 - 0.5,   c = cos(theta), s = sin(theta)
+ * computed in float32 as the rotation kernels compute theirs: the record (r00, r10, r01, r11) of xl_data_batch_augment for
+ * an H x W frame, each entry multiplied by (float)(1 / scale); gx = X r00 + Y r10, gy = X r01 + Y r11;
+ * sx = ((gx + 1) W - 1) / 2, sy = ((gy + 1) H - 1) / 2.  (ix, iy) = (rintf(sx), rintf(sy)) is the nearest source cell;
+ * where it lies outside the frame the pixel is `fill`, in both modes.  Otherwise
+ *   bilinear = 0 (label maps)  the value of cell (ix, iy): the nearest path of xl_data_batch_augment_frames under the scaled
+ *                record, so a frame with scale 1 is bitwise what that entry returns for it at (oh, ow) = (H, W);
+ *   bilinear = 1 (images)      ONE bilinear sample at (sx, sy) itself: x0 = floor(sx), lx = sx - x0, hx = 1 - lx (y alike), the
+ *                taps x0, x0 + 1, y0, y0 + 1 clamped to the frame, and in float32, in this order, no contraction,
+ *                    hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11).
+ *                This is not the "nearest rotation of a bilinearly resized frame" of xl_data_batch_augment: a rotated image is
+ *                not bitwise that kernel's output.  Minification (scale < 1) takes the one sample without an anti-alias
+ *                filter, as F.interpolate does.
+ * A frame with scale == 1.0 and angle == 0.0 is copied through bit for bit.  The records travel as kernel arguments, 64 frames
+ * per launch; both host arrays (B doubles each) are free to release when the call returns.  Refused (-1) before any HIP call:
+ * null pointers, in == out, non-positive sizes, a scale that is not finite or not positive, an angle that is not finite. */
+int xl_data_canvas_augment(const float *in, float *out, int B, int C, int H, int W,
+                           const double *scales_host, const double *angles_deg_host, float fill, int bilinear, void *stream);
 
 /* The ground-truth poses of frames rotated by xl_data_batch_augment[_frames].  poses_in / poses_out: float32
  * [B][4][4] row-major cam->world matrices; poses_out may alias poses_in.  The rotation above is counter-clockwise

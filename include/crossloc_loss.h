@@ -53,6 +53,16 @@ int xl_loss_coord_ld(const float *pred, const float *unc, const float *gt_poses,
                      float min_depth, float soft_clamp, float hard_clamp, float init_tolerance, float nodata,
                      int mode, int per_image_scale, float *dpred, float *dunc, double *workspace, float *out, void *stream);
 
+/* xl_loss_coord_ld with one focal length per image: `focals` is a device array of B floats, and image b is projected with
+ * focals[b] where xl_loss_coord_ld uses `focal` (cx, cy stay common).  The per-cell arithmetic is the same code: with all
+ * entries equal to `focal` the results are those of xl_loss_coord_ld bit for bit.  For frames that carry their own scale
+ * (xl_data_canvas_augment) or calibration.  A NULL `focals` is refused like the other NULL arguments. */
+int xl_loss_coord_frames_ld(const float *pred, const float *unc, const float *gt_poses, const float *gt_coords,
+                            int B, int Ho, int Wo, int ld_pred, int ld_unc, const float *focals, float cx, float cy,
+                            float subsample, float min_depth, float soft_clamp, float hard_clamp, float init_tolerance,
+                            float nodata, int mode, int per_image_scale, float *dpred, float *dunc, double *workspace,
+                            float *out, void *stream);
+
 int xl_loss_depth_ld(const float *pred, const float *unc, const float *gt_depth, int B, int Ho, int Wo, int ld_pred, int ld_unc,
                      float min_depth, float hard_clamp, float nodata, int mode, int per_image_scale,
                      float *dpred, float *dunc, double *workspace, float *out, void *stream);

@@ -12,7 +12,12 @@ the figure is the median over rounds of the per-call time, the spread is max - m
 own spread is the margin a difference has to exceed to mean anything.  Results are compared bit for bit before anything is
 timed.  Bytes are what the kernel must move (output written once, every input pixel read at most once), from the shapes.
 
-    python tools/augment_timing.py [--json out.json]
+--canvas adds the fixed-size augmentation (xl_data_canvas_augment through data.canvas_augment: a scale and an angle per frame,
+one bilinear sample of four taps per image pixel) as further legs on the same tensors, alternating with the per-frame rotation
+kernel in the same windows: the 16 distinct angles at scale 1 (the rotation kernel's own work; nearest mode is then bitwise
+its output, which is checked), and 16 distinct scales in 2/3 - 3/2 with those angles.
+
+    python tools/augment_timing.py [--canvas] [--json out.json]
 """
 import argparse
 import json
@@ -52,6 +57,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--json", type=str, default=None)
+    ap.add_argument("--canvas", action="store_true", help="also time data.canvas_augment on the same tensors")
     opt = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("augment_timing needs the GPU: a timing taken elsewhere says nothing")
@@ -60,6 +66,8 @@ def main():
     B = 16
     equal = [12.345] * B
     distinct = [-30.0 + 60.0 * b / (B - 1) for b in range(B)]
+    ones = [1.0] * B
+    scales = [2 / 3 + (3 / 2 - 2 / 3) * ((5 * b) % B) / (B - 1) for b in range(B)]
     results = []
 
     # warm clocks: a second of streaming work before the first timed window
@@ -77,16 +85,28 @@ def main():
         many = data.batch_augment(x, oh, ow, distinct, -1.0, bilinear)
         for b in (0, 7, B - 1):
             assert torch.equal(many[b:b + 1], data.batch_augment(x[b:b + 1], oh, ow, distinct[b], -1.0, bilinear))
-        t = time_legs([("one_angle", lambda: data.batch_augment(x, oh, ow, 12.345, -1.0, bilinear), per_window),
-                       ("per_frame_equal", lambda: data.batch_augment(x, oh, ow, equal, -1.0, bilinear), per_window),
-                       ("per_frame_distinct", lambda: data.batch_augment(x, oh, ow, distinct, -1.0, bilinear), per_window)],
-                      opt.warmup, opt.iters, opt.rounds)
+        legs = [("one_angle", lambda: data.batch_augment(x, oh, ow, 12.345, -1.0, bilinear), per_window),
+                ("per_frame_equal", lambda: data.batch_augment(x, oh, ow, equal, -1.0, bilinear), per_window),
+                ("per_frame_distinct", lambda: data.batch_augment(x, oh, ow, distinct, -1.0, bilinear), per_window)]
+        if opt.canvas:
+            if not bilinear:                                    # nearest at scale 1 is the rotation kernel's output
+                assert torch.equal(many, data.canvas_augment(x, ones, distinct, -1.0, False))
+            both = data.canvas_augment(x, scales, distinct, -1.0, bilinear)
+            for b in (0, 7, B - 1):
+                assert torch.equal(both[b:b + 1], data.canvas_augment(x[b:b + 1], scales[b:b + 1], distinct[b:b + 1], -1.0, bilinear))
+            del both
+            legs += [("canvas_rotation_only", lambda: data.canvas_augment(x, ones, distinct, -1.0, bilinear), per_window),
+                     ("canvas_scale_and_rotation", lambda: data.canvas_augment(x, scales, distinct, -1.0, bilinear), per_window)]
+        t = time_legs(legs, opt.warmup, opt.iters, opt.rounds)
         nbytes = 2 * x.numel() * 4
         r = dict(leg=what, shape=list(shape), bilinear=bilinear, bytes=nbytes)
         for k, (ms, spread) in t.items():
             r[k + "_ms"], r[k + "_spread_ms"], r[k + "_GBps"] = ms, spread, nbytes / ms / 1e6
         r["per_frame_equal_minus_one_angle_ms"] = t["per_frame_equal"][0] - t["one_angle"][0]
         r["per_frame_distinct_minus_one_angle_ms"] = t["per_frame_distinct"][0] - t["one_angle"][0]
+        if opt.canvas:
+            for k in ("canvas_rotation_only", "canvas_scale_and_rotation"):
+                r[k + "_minus_per_frame_distinct_ms"] = t[k][0] - t["per_frame_distinct"][0]
         results.append(r)
         del x, one, many
 
