@@ -426,6 +426,19 @@ XL_MATH_CALL_FN bool p3p(V3 P0, V3 P1, V3 P2, V3 P3, const double uv[4][2], cons
 
 /* ------------------------------------------------------------------------------ LM pieces */
 
+/* pose2trans: the float 4x4 cam->world matrix (row-major) of a world -> camera pose, the inverse rigid transform as the
+ * solver's write step forms it */
+XL_MATH_FN void pose_to_c2w16(const Pose *p, float *o)
+{
+    XL_MATH_UNROLL
+    for (int i = 0; i < 3; ++i) {
+        XL_MATH_UNROLL
+        for (int j = 0; j < 3; ++j) o[4 * i + j] = (float)p->R[3 * j + i];
+        o[4 * i + 3] = (float)(-(p->R[i] * p->t[0] + p->R[3 + i] * p->t[1] + p->R[6 + i] * p->t[2]));
+    }
+    o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+}
+
 /* solve (JtJ with diag*(1+lambda)) d = Jtr by Cholesky; false on breakdown */
 XL_MATH_FN bool solve6(const double *ne, double lambda, double *d)
 {

@@ -20,6 +20,8 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
     gradient w.r.t. the scene coordinates; the reference-shaped `forward_rgbd` / `backward_rgbd` still raise NotImplementedError.
   * `pose_quality_batch` / `pose_quality_rgbd_batch` rate one given pose per image (inlier statistics, JtJ, covariance) by its
     reprojection residuals and by its metric 3-D residuals.
+  * `refine_pose_batch` re-fits one given pose per image over its inliers, every cell weighted by the standard deviation the
+    network predicts for it (or unweighted), and returns the refined poses with a row of diagnostics per image.
 There is no CPU fallback: without the HIP library the call raises.
 """
 import ctypes
@@ -176,6 +178,74 @@ def pose_quality_batch(sceneCoordinates, poses, inlierThreshold, focalLength, pp
             _ptr(rows), ctypes.c_void_p(stream))
     _lib.check(rc)
     return rows
+
+
+REFINE_DOUBLES = 64                      # XL_DSAC_REFINE_DOUBLES: doubles per row of refine_pose_batch
+REFINE_MAX_CELLS = 10128                 # XL_DSAC_REFINE_MAX_CELLS: largest Ho*Wo refine_pose_batch accepts
+REFINE_MAX_ROUNDS = 16                   # XL_DSAC_REFINE_MAX_ROUNDS
+# field name -> column (or columns) of a refine_pose_batch row; layout and meaning: include/crossloc_dsac.h.  status, sigma_pos_m,
+# sigma_rot_deg, JtJ, cov and cov_center sit where the pose-quality row has them (QUALITY_FIELDS)
+REFINE_FIELDS = {
+    "n_cells": 0, "n_inliers": 1, "n_inliers_in": 2, "cost_in": 3, "cost_out": 4, "n_bad_sigma": 5, "status": 6,
+    "chi": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
+    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58),
+    "rounds": 58, "evals": 59, "converged": 60, "moved_rot_deg": 61, "moved_pos_m": 62, "reserved": 63,
+}
+
+
+def refine_pose_batch(sceneCoordinates, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY, maxReproj, subSampling,
+                      sigmaFloorPx=1.0, maxRounds=8, focals=None, outPoses=None, w2c=None):
+    """Re-fit the poses of B images over their inliers, every cell weighted by its predicted standard deviation: iteratively
+    re-weighted Levenberg-Marquardt with the weights 1 / (sigmaFloorPx^2 + (f sigma / z)^2) (model: include/crossloc_dsac.h),
+    from the given pose of each image - usually what forward_rgb_batch wrote; enqueue this behind it on the same stream.
+    sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, Ho*Wo <= REFINE_MAX_CELLS); sigma [B,Ho,Wo] float32 CUDA (any strides,
+    metres; e.g. the channel view pred[:, 3] of the network output) or None for the unweighted re-fit; poses [B,4,4] float32 CUDA
+    contiguous cam->world.  outPoses (float32 [B,4,4], may be `poses`) and w2c (float64 [B,12], the refined world->camera pose)
+    are optional CUDA contiguous outputs.  Returns (outPoses, rows): the refined poses and a float64 CUDA tensor [B,64]
+    (REFINE_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    _check_coords(sceneCoordinates, True)
+    if not sceneCoordinates.is_cuda or not isinstance(poses, torch.Tensor) or not poses.is_cuda:
+        raise RuntimeError("refine_pose_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
+        raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
+    dev = sceneCoordinates.device
+    if poses.device != dev:
+        raise RuntimeError("poses must be on the device of sceneCoordinates")
+    if sigma is not None:
+        if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or tuple(sigma.shape) != (B, Ho, Wo):
+            raise RuntimeError("sigma must be a float32 [B,Ho,Wo] tensor like sceneCoordinates")
+        if sigma.device != dev:
+            raise RuntimeError("sigma must be on the device of sceneCoordinates")
+    if Ho * Wo > REFINE_MAX_CELLS:
+        raise RuntimeError("refine_pose_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
+                           % (Ho * Wo, REFINE_MAX_CELLS))
+    if not float(sigmaFloorPx) > 0.0:
+        raise RuntimeError("sigmaFloorPx must be positive")
+    if not 1 <= int(maxRounds) <= REFINE_MAX_ROUNDS:
+        raise RuntimeError("maxRounds must be in 1..%d" % REFINE_MAX_ROUNDS)
+    if outPoses is None:
+        outPoses = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)        # (the kernel writes all 16 of every pose)
+    elif (not isinstance(outPoses, torch.Tensor) or outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4)
+          or not outPoses.is_contiguous() or outPoses.device != dev):
+        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor on the device of sceneCoordinates")
+    if w2c is not None and (not isinstance(w2c, torch.Tensor) or w2c.dtype != torch.float64 or tuple(w2c.shape) != (B, 12)
+                            or not w2c.is_contiguous() or w2c.device != dev):
+        raise RuntimeError("w2c must be a contiguous float64 [B,12] tensor on the device of sceneCoordinates")
+    if focals is not None:
+        focals = focals.to(device=dev, dtype=torch.float32).contiguous()
+        assert focals.numel() == B
+    rows = torch.empty((B, REFINE_DOUBLES), dtype=torch.float64, device=dev)       # (the kernel writes all 64 of every row)
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    gb, gy, gx = sigma.stride() if sigma is not None else (0, 0, 0)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_refine_pose_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(sigma), gb, gy, gx, B, Ho, Wo, _ptr(poses), _ptr(outPoses), _ptr(rows),
+            _ptr(w2c), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY), float(maxReproj),
+            int(subSampling), _ptr(focals), float(sigmaFloorPx), int(maxRounds), ctypes.c_void_p(stream))
+    _lib.check(rc)
+    return outPoses, rows
 
 
 BWD_REC = 128                            # XL_DSAC_BWD_REC: doubles per hypothesis in the debug record

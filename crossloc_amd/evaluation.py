@@ -236,11 +236,44 @@ def _check_quality_mode(quality, depth, cam_coords):
         raise RuntimeError("quality=\"rgbd\" rates the RGB-D solver's pose: it needs depth or cam_coords")
 
 
+def _check_refine_mode(refine, depth, cam_coords):
+    """`refine`: False, "inliers" (unweighted re-fit over the inliers) or "sigma" (weighted by the predicted uncertainty);
+    the pass re-fits the RGB solver's pose by its reprojection residuals, so it does not go with the RGB-D solver"""
+    if refine is False or refine is None:
+        return False
+    if refine not in ("inliers", "sigma"):
+        raise RuntimeError("refine must be False, \"inliers\" or \"sigma\", got %r" % (refine,))
+    if depth is not None or cam_coords is not None:
+        raise RuntimeError("refine=%r re-fits the RGB solver's pose: it does not take depth or cam_coords" % (refine,))
+    return True
+
+
+def _refine_sigma(refine, sigma, pred, nt):
+    """The sigma map the refinement reads: None for "inliers"; for "sigma" the side input if given, otherwise the
+    uncertainty channel of the prediction (a strided channel view, read in place)"""
+    if refine != "sigma":
+        return None
+    if sigma is not None:
+        return sigma
+    if pred.shape[1] <= nt:
+        raise RuntimeError("refine=\"sigma\" needs the network's uncertainty channel, and this network has none; pass sigma= "
+                           "or use refine=\"inliers\"")
+    return pred[:, nt]
+
+
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
-                   quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0):
+                   quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0,
+                   refine=False, sigma=None, sigma_floor_px=1.0):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
-    (:354), HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda, predictions [B,4,Ho,Wo]).
+    (:354) unless `refine="sigma"` asks for it, HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda,
+    predictions [B,4,Ho,Wo]).
+    `refine`: "inliers" or "sigma" enqueues the pose refinement (dsacstar.refine_pose_batch) behind the RGB solver on the
+    solver's stream: an iteratively re-weighted re-fit over the inliers, unweighted or weighted by the per-cell standard
+    deviation `sigma` [B,Ho,Wo] (a side input like `scene_coords`; default: the prediction's uncertainty channel, RuntimeError
+    if the network has none) with the pixel floor `sigma_floor_px`.  The first returned value is then the REFINED poses and the
+    refinement's rows [B,64] float64 are appended as the LAST value; a `quality=True` pass runs behind the refinement and
+    rates the refined pose.  Not with `depth` / `cam_coords`.
     `quality=True`: the pose-quality pass (dsacstar.pose_quality_batch) is enqueued directly behind the solver on the
     solver's stream and its rows [B,64] float64 are returned as a third value.
     `focal`: a number, or one focal length per frame.
@@ -257,6 +290,7 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     if depth is not None and cam_coords is not None:
         raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
     _check_quality_mode(quality, depth, cam_coords)
+    refine = _check_refine_mode(refine, depth, cam_coords) and refine
     with torch.no_grad():
         pred = network(images)
     nt = network.num_task_channel
@@ -274,6 +308,12 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
         dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
                                    inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
                                    image0=image0, image_stride=image_stride, focals=focals)
+    tail = ()
+    if refine:
+        poses, refine_rows = dsacstar.refine_pose_batch(coords, _refine_sigma(refine, sigma, pred, nt), poses, threshold, f0,
+                                                        float(image_w / 2), float(image_h / 2), max_pixel_error,
+                                                        network.OUTPUT_SUBSAMPLE, sigmaFloorPx=sigma_floor_px, focals=focals)
+        tail = (refine_rows,)
     if _is_rgbd_quality(quality):
         rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, inlier_alpha, max_dist_error,
                                                 depth=depth, focalLength=f0, ppointX=float(image_w / 2),
@@ -282,8 +322,8 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     if quality:
         rows = dsacstar.pose_quality_batch(coords, poses, threshold, f0, float(image_w / 2), float(image_h / 2),
                                            inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE, focals=focals)
-        return poses, pred, rows
-    return poses, pred
+        return (poses, pred, rows) + tail
+    return (poses, pred) + tail
 
 
 class PipelinedLocalizer:
@@ -336,16 +376,19 @@ class PipelinedLocalizer:
         return pred, [ev]
 
     def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False, depth=None,
-               cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0):
+               cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0, refine=False, sigma=None, sigma_floor_px=1.0):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
         side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
         RGB-D solver runs in place of the RGB one, as in localize_batch; `quality="rgbd"` (only with them): the RGB-D
-        pose-quality pass runs behind it instead of the reprojection pass."""
+        pose-quality pass runs behind it instead of the reprojection pass.  `refine` ("inliers" / "sigma"), `sigma` and
+        `sigma_floor_px` as in localize_batch: the refinement runs behind the RGB solver on the side stream, the first value
+        is the refined poses, its rows [B,64] are the last value, and a `quality=True` pass rates the refined pose."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
         _check_quality_mode(quality, depth, cam_coords)
+        refine = _check_refine_mode(refine, depth, cam_coords) and refine
         pred, events = self.forward_cnn(images, plant)
         coords = pred[:, :self.net.num_task_channel] if scene_coords is None else scene_coords
         poses = torch.empty((coords.shape[0], 4, 4), dtype=torch.float32, device=coords.device)   # (the solver writes all 16)
@@ -364,6 +407,16 @@ class PipelinedLocalizer:
                 dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
                                            image0=image0, image_stride=image_stride)
+            if refine:
+                f0, focals = _focal_args(self.focal, coords.shape[0])
+                sg = _refine_sigma(refine, sigma, pred, self.net.num_task_channel)
+                solved = poses
+                poses, refine_rows = dsacstar.refine_pose_batch(coords, sg, solved, self.thr, f0, float(self.w / 2),
+                                                                float(self.h / 2), self.maxerr, self.net.OUTPUT_SUBSAMPLE,
+                                                                sigmaFloorPx=sigma_floor_px, focals=focals)
+                solved.record_stream(self.side)
+                if sigma is not None:
+                    sigma.record_stream(self.side)
             if _is_rgbd_quality(quality):
                 rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, self.alpha, max_dist_error,
                                                         depth=depth, focalLength=f0, ppointX=float(self.w / 2),
@@ -374,10 +427,16 @@ class PipelinedLocalizer:
                                                    self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE)
         pred.record_stream(self.side)
         poses.record_stream(self.side)
+        tail = ()
+        if refine:
+            # allocated on the side stream, read by the caller's after finish()
+            poses.record_stream(torch.cuda.current_stream())
+            refine_rows.record_stream(torch.cuda.current_stream())
+            tail = (refine_rows,)
         if quality:
             rows.record_stream(torch.cuda.current_stream())  # allocated on the side stream, read by the caller's after finish()
-            return poses, pred, rows
-        return poses, pred
+            return (poses, pred, rows) + tail
+        return (poses, pred) + tail
 
     def finish(self):
         """Make the caller's stream wait for every enqueued CNN and solver launch."""

@@ -84,6 +84,30 @@ def make_scene(seed, noise=0.5, outlier_ratio=0.3, Ho=IMAGE_H // SUBSAMPLE, Wo=I
                 focal=float(focal), ppx=float(ppx), ppy=float(ppy))
 
 
+def make_hetero_scene(seed, sigma_range=(0.1, 3.0), outlier_ratio=0.3, Ho=IMAGE_H // SUBSAMPLE, Wo=IMAGE_W // SUBSAMPLE,
+                      sub=SUBSAMPLE, focal=FOCAL):
+    """One heteroscedastic frame: make_scene's dict plus sigma [Ho,Wo] f32, the standard deviation (metres) an honest network
+    would predict for each cell.  sigma is log-uniform in `sigma_range` per cell and the coordinate noise of a cell is Gaussian
+    with that sigma per axis; the gross outliers (drawn as in make_scene) keep their drawn sigma.  A function of its own:
+    the draws of make_scene do not move."""
+    rng = np.random.default_rng(seed)
+    ppx, ppy = Wo * sub / 2.0, Ho * sub / 2.0
+    pose = random_pose(rng)
+    gt, hit = raycast(pose, Ho, Wo, sub, focal, ppx, ppy)
+    lo_s, hi_s = float(sigma_range[0]), float(sigma_range[1])
+    sigma = np.exp(rng.uniform(np.log(lo_s), np.log(hi_s), size=(Ho, Wo)))
+    pred = gt + rng.normal(0.0, 1.0, size=gt.shape) * sigma[None]
+    n_out = int(round(outlier_ratio * Ho * Wo))
+    if n_out > 0:
+        idx = rng.choice(Ho * Wo, size=n_out, replace=False)
+        lo = np.array([SCENE_MEAN[0] - 750, SCENE_MEAN[1] - 750, SCENE_MEAN[2] - 300])
+        hi = np.array([SCENE_MEAN[0] + 750, SCENE_MEAN[1] + 750, SCENE_MEAN[2] - 180])
+        pred.reshape(3, -1)[:, idx] = rng.uniform(lo[:, None], hi[:, None], size=(3, n_out))
+    gt_lab = np.where(hit[None], gt, NODATA)
+    return dict(coords=pred.astype(np.float32), gt_coords=gt_lab.astype(np.float32), pose=pose,
+                focal=float(focal), ppx=float(ppx), ppy=float(ppy), sigma=sigma.astype(np.float32))
+
+
 def make_batch(seed0, count, **kw):
     """`count` frames with seeds seed0, seed0+1, ... stacked: coords [B,3,Ho,Wo], gt [B,3,Ho,Wo], poses [B,4,4]."""
     scenes = [make_scene(seed0 + i, **kw) for i in range(count)]

@@ -318,6 +318,76 @@ int xl_dsac_pose_quality_rgbd_batch(const float *coords_dev, int64_t sb, int64_t
                                     float focal, float ppx, float ppy, int sub, const float *focals_dev,
                                     double *rows_dev /* [B,64] */, void *stream);
 
+/*
+ * Uncertainty-weighted pose refinement (no reference counterpart): ONE given pose per image - usually the one
+ * xl_dsac_forward_rgb_batch wrote, enqueued behind it on the same stream - is re-fitted over its inliers by iteratively
+ * re-weighted Levenberg-Marquardt, every cell weighted by the standard deviation the network predicts for it.  A stand-alone
+ * pass, one 256-thread workgroup per image; the solver's kernels are not involved.  Asynchronous on `stream`: no host
+ * synchronisation, no allocation.
+ *
+ *   coords_dev     [B,3,Ho,Wo] float32, strides (sb, sc, sy, sx) in elements
+ *   sigma_dev      [B,Ho,Wo] float32 standard deviation of each cell's scene coordinate in metres, strides (gb, gy, gx) - the
+ *                  fourth channel of a network trained with the MLE coordinate loss, which models the error of a cell as an
+ *                  isotropic 3-D Gaussian of that sigma - or NULL: every weight is 1, a plain re-fit over the inliers
+ *   poses_dev      [B,16] float32 cam->world 4x4, read as xl_dsac_pose_quality_batch reads it
+ *   out_poses_dev  [B,16] float32 cam->world, the refined pose, formed from the double pose as the solver forms its output;
+ *                  the input's 16 floats bit for bit when no round completed (status != 0).  May be poses_dev itself.
+ *   rows_dev       [B,XL_DSAC_REFINE_DOUBLES] float64, one row per image, all 64 written
+ *   w2c_dev        optional [B,12] float64: the refined world->camera pose, R row-major then t (the pose read from poses_dev
+ *                  when no round completed; NaN with status 3)
+ *   thr, focal, ppx, ppy, max_reproj, sub, focals_dev   as in xl_dsac_forward_rgb_batch
+ *   s0             floor of the residual's standard deviation in pixels (the pixel noise of a perfectly known cell), > 0
+ *   max_rounds     1 .. XL_DSAC_REFINE_MAX_ROUNDS
+ *
+ * Model.  A round starts at pose P_k.  Its inlier set is { i : e_i(P_k) < thr } with e the solver's clamped float reprojection
+ * error and float comparison; with z_i the camera depth of cell i at P_k (z_i == 0 read as 1) its weight is
+ * w_i = 1 / (s0^2 + (f sigma_i / z_i)^2).  A cell whose sigma is not finite or is negative is left out of every set and
+ * counted in [5].  Set and weights stay fixed for the whole round (weights that followed the moving pose would favour large
+ * depths and bias the estimating equation sum w_i J_i^T r_i = 0) while the solver's Levenberg-Marquardt (damping from 1e-3,
+ * accept test on the weighted cost, 20 iterations at most, the same step-size stop) minimises sum w_i |r_i|^2 over the
+ * increment R' = Exp(w) R, t' = t + d of the world->camera pose.  The rounds stop when a round's set equals the previous
+ * round's (converged), after max_rounds, when the set has fewer than 4 cells, or when a solve breaks down or the pose stops
+ * being finite; the pose of the last completed round is the result.  With sigma_dev == NULL the weights are 1; a map of zeros
+ * with s0 == 1 gives the bits of the NULL form.
+ *
+ * Row of image b (doubles; the pose-quality row's positions wherever the meaning is the same):
+ *     [0]      n_cells = Ho * Wo
+ *     [1]      inliers of the last completed round
+ *     [2]      inliers at the input pose
+ *     [3]      weighted cost sum w |r|^2 at the input pose (the first evaluation)
+ *     [4]      weighted cost at the output pose, over the last completed round's set and weights
+ *     [5]      cells left out for an unusable sigma
+ *     [6]      status: 0 ok; 1 fewer than 4 inliers at the input pose; 2 the first round failed (normal matrix not positive
+ *              definite, LM breakdown or a pose that is not finite); 3 an input pose entry (rows 0..2) is not finite
+ *     [7]      chi = sqrt([4] / (2 [1] - 6)): 1 when sigma is calibrated, > 1 when the network is over-confident
+ *     [8]      sigma_pos_m = sqrt(trace Sigma_C)
+ *     [9]      sigma_rot_deg = sqrt(Sigma_00 + Sigma_11 + Sigma_22) * 180/pi
+ *     [10..30] J^T W J at the output pose, upper triangle row-major
+ *     [31..51] Sigma = chi^2 (J^T W J)^-1, upper triangle row-major
+ *     [52..57] Sigma_C, covariance of the camera centre as in the pose-quality row
+ *     [58]     rounds completed       [59] normal-equation evaluations       [60] converged (1 / 0)
+ *     [61]     rotation between input and output pose, degrees               [62] distance of their camera centres, metres
+ *     [63]     0.0
+ *   NaN pattern as in the pose-quality row.  With status 1 or 2 no round completed: [1] = [2], [4] = [3] and [10..30] come from
+ *   the first evaluation at the input pose, [7..9] and [31..57] are NaN, [58] and [60..62] are 0.  With status 3 every field
+ *   except [0] and [6] is NaN.  With status 0, [8], [9] and [31..57] are NaN if J^T W J at the output pose has no Cholesky factor.
+ *   The hard gate at thr truncates the residuals of cells whose sigma in pixels approaches thr, so chi reads below 1 on honest
+ *   sigma there, and an s0 above the true pixel noise makes Sigma conservative.
+ *
+ * The image is staged in the LDS of one CU as four float planes: Ho * Wo <= XL_DSAC_REFINE_MAX_CELLS, else XL_ERR_GRID.
+ * XL_ERR_ARG: a null coords / poses / out_poses / rows pointer, B, Ho, Wo or sub not positive, s0 not above 0, max_rounds out
+ * of range.  Both are returned before any HIP call.
+ */
+#define XL_DSAC_REFINE_DOUBLES 64
+#define XL_DSAC_REFINE_MAX_CELLS 10128      /* (160 KiB - reduction scratch) / 16 bytes per cell */
+#define XL_DSAC_REFINE_MAX_ROUNDS 16
+int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                              const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                              int B, int Ho, int Wo, const float *poses_dev /* [B,16] cam->world */,
+                              float *out_poses_dev /* [B,16] */, double *rows_dev /* [B,64] */, double *w2c_dev /* [B,12] or NULL */,
+                              float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
+                              const float *focals_dev, float s0, int max_rounds, void *stream);
+
 /* The reference-shaped single-image RGB-D entries (dsacstar.cpp:889-891) are not wired to the solver above yet: they
  * return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);
