@@ -82,6 +82,9 @@ def lib():
             c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
         L.xl_dsac_pose_quality_rgbd_batch.restype = c_i32
         L.xl_dsac_pose_quality_rgbd_batch.argtypes = rgbd_in + [c_vp, c_f, c_f, c_f] + intr + [c_vp, c_vp]
+        L.xl_dsac_refine_pose_rgbd_batch.restype = c_i32
+        L.xl_dsac_refine_pose_rgbd_batch.argtypes = rgbd_in[:-3] + [c_vp, c_i64, c_i64, c_i64] * 2 + rgbd_in[-3:] + [
+            c_vp, c_vp, c_vp, c_vp, c_f, c_f] + intr + [c_f, c_f, c_i32, c_vp]
         # include/crossloc_metrics.h
         L.xl_metrics_workspace_bytes.restype = c_i64
         L.xl_metrics_workspace_bytes.argtypes = [c_i32, c_i32]

@@ -21,7 +21,9 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
   * `pose_quality_batch` / `pose_quality_rgbd_batch` rate one given pose per image (inlier statistics, JtJ, covariance) by its
     reprojection residuals and by its metric 3-D residuals.
   * `refine_pose_batch` re-fits one given pose per image over its inliers, every cell weighted by the standard deviation the
-    network predicts for it (or unweighted), and returns the refined poses with a row of diagnostics per image.
+    network predicts for it (or unweighted), and returns the refined poses with a row of diagnostics per image;
+    `refine_pose_rgbd_batch` is its RGB-D twin: metric 3-D residuals under a 3x3 information matrix per cell (isotropic
+    coordinate noise plus depth noise along the viewing ray).
 There is no CPU fallback: without the HIP library the call raises.
 """
 import ctypes
@@ -503,6 +505,77 @@ def pose_quality_rgbd_batch(sceneCoordinates, cameraCoordinates, poses, inlierTh
             _ptr(rows), ctypes.c_void_p(stream))
     _lib.check(rc)
     return rows
+
+
+# field name -> column (or columns) of a refine_pose_rgbd_batch row; layout and meaning: include/crossloc_dsac.h.  The positions
+# of REFINE_FIELDS; chi is metres per axis in the plain form, the costs are r^T W r, and the last column is n_valid
+RGBD_REFINE_FIELDS = {
+    "n_cells": 0, "n_inliers": 1, "n_inliers_in": 2, "cost_in": 3, "cost_out": 4, "n_bad_sigma": 5, "status": 6,
+    "chi": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
+    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58),
+    "rounds": 58, "evals": 59, "converged": 60, "moved_deg": 61, "moved_m": 62, "n_valid": 63,
+}
+
+
+def _rgbd_sigma_map(name, m, sceneCoordinates):
+    """sigma / depthSigma of refine_pose_rgbd_batch: None or a float32 [B,Ho,Wo] tensor on the device of sceneCoordinates"""
+    if m is None:
+        return (0, 0, 0)
+    B, _, Ho, Wo = sceneCoordinates.shape
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or tuple(m.shape) != (B, Ho, Wo):
+        raise RuntimeError("%s must be a float32 [B,Ho,Wo] tensor like sceneCoordinates" % name)
+    if m.device != sceneCoordinates.device:
+        raise RuntimeError("%s must be on the device of sceneCoordinates" % name)
+    return m.stride()
+
+
+def refine_pose_rgbd_batch(sceneCoordinates, cameraCoordinates, sigma, poses, inlierThreshold, maxDistError, depthSigma=None,
+                           depthRel=0.0, sigmaFloorM=0.01, maxRounds=8, depth=None, focalLength=None, ppointX=None, ppointY=None,
+                           subSampling=None, focals=None, outPoses=None, w2c=None):
+    """Ray-aware uncertainty-weighted refinement of the RGB-D poses of B images (model: include/crossloc_dsac.h): Levenberg-
+    Marquardt over the inliers of the metric 3-D residuals p - (R X + t) under a 3x3 information matrix per cell, from the given
+    pose of each image - usually what forward_rgbd_batch wrote; enqueue this behind it on the same stream.  Tensor rules as in
+    pose_quality_rgbd_batch: sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, any grid size), EXACTLY ONE of
+    cameraCoordinates [B,3,Ho,Wo] and depth [B,Ho,Wo] (float32 CUDA, any strides; depth needs focalLength or focals, ppointX,
+    ppointY, subSampling), thresholds in centimetres; poses [B,4,4] float32 CUDA contiguous cam->world.  sigma [B,Ho,Wo] float32
+    CUDA (any strides, metres; e.g. the channel view pred[:, 3] of the network output) or None; depthSigma [B,Ho,Wo] float32 CUDA
+    (any strides, metres of depth; e.g. a depth network's uncertainty channel) or None; depthRel: relative depth noise;
+    sigmaFloorM: the floor of sigma in metres.  With sigma None, depthSigma None and depthRel 0 it is a plain re-fit over the
+    inliers.  outPoses (float32 [B,4,4], may be `poses`) and w2c (float64 [B,12], the refined world->camera pose) are optional
+    CUDA contiguous outputs.  Returns (outPoses, rows): the refined poses and a float64 CUDA tensor [B,64] (RGBD_REFINE_FIELDS
+    names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    intr = (focalLength, ppointX, ppointY, subSampling, focals)
+    _rgbd_source("refine_pose_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, intr)
+    _rgbd_on_device("refine_pose_rgbd_batch", sceneCoordinates, cameraCoordinates, depth, poses)
+    B = sceneCoordinates.shape[0]
+    if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
+        raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
+    gs = _rgbd_sigma_map("sigma", sigma, sceneCoordinates)
+    zs = _rgbd_sigma_map("depthSigma", depthSigma, sceneCoordinates)
+    if not float(sigmaFloorM) > 0.0:
+        raise RuntimeError("sigmaFloorM must be positive")
+    if not 0.0 <= float(depthRel) < float("inf"):
+        raise RuntimeError("depthRel must be finite and not negative")
+    if not 1 <= int(maxRounds) <= REFINE_MAX_ROUNDS:
+        raise RuntimeError("maxRounds must be in 1..%d" % REFINE_MAX_ROUNDS)
+    prefix, tail, dev, focals = _rgbd_call_args(sceneCoordinates, cameraCoordinates, depth, intr)
+    if outPoses is None:
+        outPoses = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)        # (the kernel writes all 16 of every pose)
+    elif (not isinstance(outPoses, torch.Tensor) or outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4)
+          or not outPoses.is_contiguous() or outPoses.device != dev):
+        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor on the device of sceneCoordinates")
+    if w2c is not None and (not isinstance(w2c, torch.Tensor) or w2c.dtype != torch.float64 or tuple(w2c.shape) != (B, 12)
+                            or not w2c.is_contiguous() or w2c.device != dev):
+        raise RuntimeError("w2c must be a contiguous float64 [B,12] tensor on the device of sceneCoordinates")
+    rows = torch.empty((B, REFINE_DOUBLES), dtype=torch.float64, device=dev)       # (the kernel writes all 64 of every row)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_refine_pose_rgbd_batch(
+            *prefix[:-3], _ptr(sigma), *gs, _ptr(depthSigma), *zs, *prefix[-3:], _ptr(poses), _ptr(outPoses), _ptr(rows), _ptr(w2c),
+            float(inlierThreshold), float(maxDistError), *tail, float(sigmaFloorM), float(depthRel), int(maxRounds),
+            ctypes.c_void_p(stream))
+    _lib.check(rc)
+    return outPoses, rows
 
 
 def forward_rgbd(*args, **kwargs):

@@ -241,30 +241,50 @@ def _check_refine_mode(refine, depth, cam_coords):
     the pass re-fits the RGB solver's pose by its reprojection residuals, so it does not go with the RGB-D solver"""
     if refine is False or refine is None:
         return False
+    if refine in RGBD_REFINE_MODES:
+        if depth is None and cam_coords is None:
+            raise RuntimeError("refine=%r re-fits the RGB-D solver's pose: it needs depth or cam_coords" % (refine,))
+        return True
     if refine not in ("inliers", "sigma"):
-        raise RuntimeError("refine must be False, \"inliers\" or \"sigma\", got %r" % (refine,))
+        raise RuntimeError("refine must be False, \"inliers\", \"sigma\", \"rgbd_inliers\" or \"rgbd_sigma\", got %r" % (refine,))
     if depth is not None or cam_coords is not None:
         raise RuntimeError("refine=%r re-fits the RGB solver's pose: it does not take depth or cam_coords" % (refine,))
     return True
 
 
+# the refinement behind the RGB-D solver (dsacstar.refine_pose_rgbd_batch): the plain re-fit over the inliers, and the re-fit
+# under the per-cell information matrix of sigma, depth_sigma and depth_rel
+RGBD_REFINE_MODES = ("rgbd_inliers", "rgbd_sigma")
+
+
 def _refine_sigma(refine, sigma, pred, nt):
-    """The sigma map the refinement reads: None for "inliers"; for "sigma" the side input if given, otherwise the
-    uncertainty channel of the prediction (a strided channel view, read in place)"""
-    if refine != "sigma":
+    """The sigma map the refinement reads: None for "inliers" / "rgbd_inliers"; for "sigma" / "rgbd_sigma" the side input if
+    given, otherwise the uncertainty channel of the prediction (a strided channel view, read in place)"""
+    if refine not in ("sigma", "rgbd_sigma"):
         return None
     if sigma is not None:
         return sigma
     if pred.shape[1] <= nt:
-        raise RuntimeError("refine=\"sigma\" needs the network's uncertainty channel, and this network has none; pass sigma= "
-                           "or use refine=\"inliers\"")
+        raise RuntimeError("refine=\"%s\" needs the network's uncertainty channel, and this network has none; pass sigma= "
+                           "or use refine=\"%s\"" % (refine, refine.replace("sigma", "inliers")))
     return pred[:, nt]
+
+
+def _refine_rgbd(refine, coords, cam_coords, depth, sg, poses, rgbd_threshold, max_dist_error, depth_sigma, depth_rel,
+                 sigma_floor_m, intr):
+    """The RGB-D refinement behind the RGB-D solver on the current stream -> (refined poses, rows).  "rgbd_inliers" is the plain
+    form: neither map nor depth_rel is passed on."""
+    import dsacstar
+    weighted = refine == "rgbd_sigma"
+    return dsacstar.refine_pose_rgbd_batch(coords, cam_coords, sg, poses, rgbd_threshold, max_dist_error,
+                                           depthSigma=depth_sigma if weighted else None,
+                                           depthRel=depth_rel if weighted else 0.0, sigmaFloorM=sigma_floor_m, depth=depth, **intr)
 
 
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
                    quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0,
-                   refine=False, sigma=None, sigma_floor_px=1.0):
+                   refine=False, sigma=None, sigma_floor_px=1.0, depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
     (:354) unless `refine="sigma"` asks for it, HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda,
     predictions [B,4,Ho,Wo]).
@@ -274,6 +294,12 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     if the network has none) with the pixel floor `sigma_floor_px`.  The first returned value is then the REFINED poses and the
     refinement's rows [B,64] float64 are appended as the LAST value; a `quality=True` pass runs behind the refinement and
     rates the refined pose.  Not with `depth` / `cam_coords`.
+    `refine`: "rgbd_inliers" or "rgbd_sigma" (only with `depth` or `cam_coords`, RuntimeError without) enqueues the RGB-D
+    refinement (dsacstar.refine_pose_rgbd_batch) behind the RGB-D solver on its stream: the plain re-fit over the inliers of the
+    metric 3-D residuals, or the re-fit under a 3x3 information matrix per cell from `sigma` (as above), `depth_sigma`
+    [B,Ho,Wo] (the standard deviation of the depth in metres, e.g. a depth network's uncertainty channel; optional), the relative
+    depth noise `depth_rel` and the floor `sigma_floor_m` in metres.  The refined poses come first and the rows [B,64] last; a
+    `quality="rgbd"` pass behind it rates the refined pose.
     `quality=True`: the pose-quality pass (dsacstar.pose_quality_batch) is enqueued directly behind the solver on the
     solver's stream and its rows [B,64] float64 are returned as a third value.
     `focal`: a number, or one focal length per frame.
@@ -309,7 +335,13 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
                                    inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
                                    image0=image0, image_stride=image_stride, focals=focals)
     tail = ()
-    if refine:
+    if refine in RGBD_REFINE_MODES:
+        intr = dict(focalLength=f0, ppointX=float(image_w / 2), ppointY=float(image_h / 2), subSampling=network.OUTPUT_SUBSAMPLE,
+                    focals=focals)
+        poses, refine_rows = _refine_rgbd(refine, coords, cam_coords, depth, _refine_sigma(refine, sigma, pred, nt), poses,
+                                          rgbd_threshold, max_dist_error, depth_sigma, depth_rel, sigma_floor_m, intr)
+        tail = (refine_rows,)
+    elif refine:
         poses, refine_rows = dsacstar.refine_pose_batch(coords, _refine_sigma(refine, sigma, pred, nt), poses, threshold, f0,
                                                         float(image_w / 2), float(image_h / 2), max_pixel_error,
                                                         network.OUTPUT_SUBSAMPLE, sigmaFloorPx=sigma_floor_px, focals=focals)
@@ -318,7 +350,7 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
         rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, inlier_alpha, max_dist_error,
                                                 depth=depth, focalLength=f0, ppointX=float(image_w / 2),
                                                 ppointY=float(image_h / 2), subSampling=network.OUTPUT_SUBSAMPLE, focals=focals)
-        return poses, pred, rows
+        return (poses, pred, rows) + tail
     if quality:
         rows = dsacstar.pose_quality_batch(coords, poses, threshold, f0, float(image_w / 2), float(image_h / 2),
                                            inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE, focals=focals)
@@ -376,14 +408,17 @@ class PipelinedLocalizer:
         return pred, [ev]
 
     def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False, depth=None,
-               cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0, refine=False, sigma=None, sigma_floor_px=1.0):
+               cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0, refine=False, sigma=None, sigma_floor_px=1.0,
+               depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
         side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
         RGB-D solver runs in place of the RGB one, as in localize_batch; `quality="rgbd"` (only with them): the RGB-D
         pose-quality pass runs behind it instead of the reprojection pass.  `refine` ("inliers" / "sigma"), `sigma` and
         `sigma_floor_px` as in localize_batch: the refinement runs behind the RGB solver on the side stream, the first value
-        is the refined poses, its rows [B,64] are the last value, and a `quality=True` pass rates the refined pose."""
+        is the refined poses, its rows [B,64] are the last value, and a `quality=True` pass rates the refined pose.
+        `refine` "rgbd_inliers" / "rgbd_sigma" with `depth_sigma`, `depth_rel` and `sigma_floor_m` (only with `depth` or
+        `cam_coords`): the RGB-D refinement runs behind the RGB-D solver on the side stream, as in localize_batch."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
@@ -407,7 +442,18 @@ class PipelinedLocalizer:
                 dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
                                            image0=image0, image_stride=image_stride)
-            if refine:
+            if refine in RGBD_REFINE_MODES:
+                sg = _refine_sigma(refine, sigma, pred, self.net.num_task_channel)
+                solved = poses
+                intr = dict(focalLength=f0, ppointX=float(self.w / 2), ppointY=float(self.h / 2),
+                            subSampling=self.net.OUTPUT_SUBSAMPLE, focals=focals)
+                poses, refine_rows = _refine_rgbd(refine, coords, cam_coords, depth, sg, solved, rgbd_threshold, max_dist_error,
+                                                  depth_sigma, depth_rel, sigma_floor_m, intr)
+                solved.record_stream(self.side)
+                for side_input in (sigma, depth_sigma):
+                    if side_input is not None:
+                        side_input.record_stream(self.side)
+            elif refine:
                 f0, focals = _focal_args(self.focal, coords.shape[0])
                 sg = _refine_sigma(refine, sigma, pred, self.net.num_task_channel)
                 solved = poses

@@ -108,6 +108,40 @@ def make_hetero_scene(seed, sigma_range=(0.1, 3.0), outlier_ratio=0.3, Ho=IMAGE_
                 focal=float(focal), ppx=float(ppx), ppy=float(ppy), sigma=sigma.astype(np.float32))
 
 
+def camera_from_depth(depth, focal, ppx, ppy, sub=SUBSAMPLE):
+    """Camera coordinates [3,Ho,Wo] float32 of a depth map [Ho,Wo] float32: the ray through the centre of every cell times the
+    depth, every step in float32 - the formula the RGB-D solver applies to `depth` itself."""
+    Ho, Wo = depth.shape
+    f = np.float32(focal)
+    rx = ((np.arange(Wo) * sub + sub // 2).astype(np.float32) - np.float32(ppx)) / f
+    ry = ((np.arange(Ho) * sub + sub // 2).astype(np.float32) - np.float32(ppy)) / f
+    return np.stack([rx[None, :] * depth, ry[:, None] * depth, depth]).astype(np.float32)
+
+
+def make_hetero_rgbd_scene(seed, sigma_range=(0.02, 0.5), depth_rel=0.01, holes=0.0, outlier_ratio=0.3,
+                           Ho=IMAGE_H // SUBSAMPLE, Wo=IMAGE_W // SUBSAMPLE, sub=SUBSAMPLE, focal=FOCAL):
+    """One heteroscedastic RGB-D frame: make_hetero_scene's dict (the same draws) plus the depth a sensor at the ground-truth
+    pose would measure.  depth [Ho,Wo] f32: the z of the ground-truth camera coordinate times (1 + depth_rel N(0, 1)), zero
+    where the ray hits nothing and in a share `holes` of the cells; cam [3,Ho,Wo] f32: that depth through camera_from_depth;
+    depth_sigma [Ho,Wo] f32: the standard deviation an honest depth network would predict, depth_rel times the true depth
+    (zero where there is no depth).  A function of its own with a generator of its own: no existing draw moves."""
+    s = make_hetero_scene(seed, sigma_range=sigma_range, outlier_ratio=outlier_ratio, Ho=Ho, Wo=Wo, sub=sub, focal=focal)
+    pose = s["pose"]
+    gt = s["gt_coords"].astype(np.float64)
+    hit = ~np.all(s["gt_coords"] == np.float32(NODATA), axis=0)
+    z = np.einsum("k,khw->hw", pose[:3, 2], gt - pose[:3, 3][:, None, None])          # z row of R^T (gt - c)
+    z = np.where(hit, z, 0.0)
+    rng = np.random.default_rng([seed, 0x5244])
+    depth = z * (1.0 + depth_rel * rng.normal(size=z.shape))
+    if holes > 0:
+        idx = rng.choice(Ho * Wo, size=int(round(holes * Ho * Wo)), replace=False)
+        depth.reshape(-1)[idx] = 0.0
+    depth = depth.astype(np.float32)
+    s.update(depth=depth, cam=camera_from_depth(depth, s["focal"], s["ppx"], s["ppy"], sub),
+             depth_sigma=np.where(depth != 0, depth_rel * z, 0.0).astype(np.float32))
+    return s
+
+
 def make_batch(seed0, count, **kw):
     """`count` frames with seeds seed0, seed0+1, ... stacked: coords [B,3,Ho,Wo], gt [B,3,Ho,Wo], poses [B,4,4]."""
     scenes = [make_scene(seed0 + i, **kw) for i in range(count)]

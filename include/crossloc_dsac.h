@@ -388,6 +388,98 @@ int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, int64_t sc, i
                               float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
                               const float *focals_dev, float s0, int max_rounds, void *stream);
 
+/*
+ * Ray-aware uncertainty-weighted pose refinement behind the RGB-D solver (no reference counterpart): ONE given pose per image -
+ * usually the one xl_dsac_forward_rgbd_batch wrote, enqueued behind it on the same stream - is re-fitted over its inliers by
+ * Levenberg-Marquardt under a 3x3 information matrix per cell.  The sibling of xl_dsac_refine_pose_batch and of
+ * xl_dsac_pose_quality_rgbd_batch: a stand-alone pass, one 256-thread workgroup per image, nothing staged in LDS (any grid size,
+ * XL_DSAC_RGBD_MAX_CELLS does not apply); the solver's kernels are not involved.  Asynchronous on `stream`: no host
+ * synchronisation, no allocation.
+ *
+ *   coords / cam / depth with their strides, thr, max_dist (centimetres), focal, ppx, ppy, sub, focals_dev
+ *                  as in xl_dsac_forward_rgbd_batch: EXACTLY ONE of cam_dev and depth_dev is non-null, the depth form builds the
+ *                  camera coordinate with the same float formula and bits
+ *   sigma_dev      [B,Ho,Wo] float32 standard deviation of each cell's scene coordinate in metres, strides (gb, gy, gx) - the
+ *                  uncertainty channel of the coordinate network - or NULL: sigma = 0
+ *   depth_sigma_dev  [B,Ho,Wo] float32 standard deviation of each cell's depth (camera z) in metres, strides (zb, zy, zx) - the
+ *                  uncertainty channel of a depth network - or NULL: sigma_z = 0
+ *   poses_dev      [B,16] float32 cam->world 4x4, read as xl_dsac_pose_quality_rgbd_batch reads it
+ *   out_poses_dev  [B,16] float32 cam->world, the refined pose, formed from the double pose as the solver forms its output;
+ *                  the input's 16 floats bit for bit when no round completed (status != 0).  May be poses_dev itself.
+ *   rows_dev       [B,XL_DSAC_REFINE_DOUBLES] float64, one row per image, all 64 written
+ *   w2c_dev        optional [B,12] float64: the refined world->camera pose, R row-major then t (the pose read from poses_dev
+ *                  when no round completed; NaN with status 3)
+ *   s0             floor of the scene coordinate's standard deviation in metres, > 0
+ *   depth_rel      k: relative depth noise (0.01: one per cent of the depth), >= 0 and finite
+ *   max_rounds     1 .. XL_DSAC_REFINE_MAX_ROUNDS
+ *
+ * Model.  m = R X + t is the predicted camera point of a cell (X its scene coordinate), r = p - m its residual in metres (p its
+ * camera coordinate).  A cell is valid iff its camera z != 0.  A valid cell is an inlier at pose P_k iff
+ * e = min((float)(|r| * 100), max_dist) < thr, the solver's clamp and float comparison.  Noise of cell i: the scene coordinate
+ * has isotropic noise a_i = s0^2 + sigma_i^2; the depth noise acts along the unit ray rho_i = p_i / |p_i| with variance
+ * b_i = (sigma_z,i^2 + (k z_i)^2) |p_i|^2 / z_i^2 (an error dz of the depth moves p = z (x/z, y/z, 1) by dz |p| / z along the
+ * ray).  The covariance of r_i is a_i I + b_i rho_i rho_i^T and, by Sherman-Morrison, its information matrix is
+ * W_i = (I - b_i / (a_i + b_i) rho_i rho_i^T) / a_i.  rho, a and b belong to the measurement: they do not depend on the pose and
+ * are fixed for the whole call.  A valid cell whose sigma or sigma_z is negative or not finite is left out of every inlier set and
+ * counted in [5].  Plain form: with sigma_dev == NULL, depth_sigma_dev == NULL and depth_rel == 0 every W_i is the identity and
+ * s0 is not used - a plain re-fit over the inliers, and chi is the residual standard deviation in metres per axis, the RGB-D
+ * quality row's sigma_m.  Maps of zeros with s0 == 1 and depth_rel == 0 give the bits of the plain form.
+ *
+ * Rounds.  The inlier set is fixed per round and taken at the round's start pose P_k.  Within a round the solver's
+ * Levenberg-Marquardt (damping from 1e-3, accept test on the cost, 20 iterations at most, the same step-size stop) minimises
+ * sum r^T W r over the 6-parameter increment.  The rounds stop when a round's set equals the previous round's (converged), after
+ * max_rounds, when fewer than 3 inliers remain, when the normal matrix has no sound Cholesky factor (a pivot not above 1e-12
+ * times its diagonal entry: inliers on one line) or LM breaks down, or on a pose that is not finite.  The result is the pose of
+ * the last completed round.  The row rates the pose the caller receives: after the last round the normal equations are
+ * evaluated once more, over that round's set, at the float32 matrix written to out_poses_dev read back as every pass reads a
+ * pose (counted in [59]); [4], [7..57], [61] and [62] refer to that pose, so a xl_dsac_pose_quality_rgbd_batch call behind this
+ * one rates the same pose.  w2c_dev keeps the unrounded double pose.
+ *
+ * Conditioning.  Scene coordinates lie up to 1200 m from the world origin; the uncentred normal matrix has a condition number of
+ * 1e7 to 1e9.  Every normal equation is accumulated about the round's inlier centroid c of m, and the step is solved in
+ * (rotation w about c, centroid translation tau): m' = Exp(w) (m - c) + c + tau, J = [[m - c]x, -I].  JtJ and Sigma are reported
+ * in the parameters of the other rows, (wx, wy, wz, tx, ty, tz) with R' = Exp(w) R, t' = t + d, through d = tau - [t - c]x w, the
+ * G of the RGB-D quality row: G = [[I, 0], [-[t - c]x, I]], JtJ = G^-T (J^T W J) G^-1 (= sum J^T W J with J = [[R X]x, -I]: the
+ * lever arm of the rotation is R X, not m), Sigma = G (chi^2 (J^T W J)^-1) G^T.
+ *
+ * Row of image b (doubles; the positions of the xl_dsac_refine_pose_batch row):
+ *     [0]      n_cells = Ho * Wo
+ *     [1]      inliers of the last completed round
+ *     [2]      inliers at the input pose
+ *     [3]      cost sum r^T W r at the input pose (the first evaluation)
+ *     [4]      cost at the output pose, over the last completed round's set
+ *     [5]      valid cells left out for an unusable sigma or sigma_z
+ *     [6]      status: 0 ok; 1 fewer than 3 inliers at the input pose; 2 the first round failed (normal matrix degenerate, LM
+ *              breakdown or a pose that is not finite); 3 an input pose entry (rows 0..2) is not finite
+ *     [7]      chi = sqrt([4] / (3 [1] - 6)): 1 when sigma, sigma_z and k are calibrated; metres per axis in the plain form
+ *     [8]      sigma_pos_m = sqrt(trace Sigma_C)
+ *     [9]      sigma_rot_deg = sqrt(Sigma_00 + Sigma_11 + Sigma_22) * 180/pi
+ *     [10..30] J^T W J at the output pose, upper triangle row-major
+ *     [31..51] Sigma = chi^2 (J^T W J)^-1, upper triangle row-major
+ *     [52..57] Sigma_C, covariance of the camera centre as in the pose-quality row
+ *     [58]     rounds completed       [59] normal-equation evaluations       [60] converged (1 / 0)
+ *     [61]     rotation between input and output pose, degrees               [62] distance of their camera centres, metres
+ *     [63]     n_valid
+ *   NaN pattern as in the sibling.  With status 1 or 2 no round completed: [1] = [2], [4] = [3] and [10..30] come from the first
+ *   evaluation at the input pose, [7..9] and [31..57] are NaN, [58] and [60..62] are 0.  With status 3 every field except [0] and
+ *   [6] is NaN.  With status 0, [8], [9] and [31..57] are NaN if J^T W J at the output pose has no Cholesky factor.
+ *   The gate stays the solver's Euclidean one: it truncates the residuals of cells whose noise approaches thr, so chi reads
+ *   below 1 on honest sigma there, and an s0 above the true floor makes Sigma conservative.
+ *
+ * XL_ERR_ARG (before any HIP call): a null coords / poses / out_poses / rows pointer, neither or both of cam_dev and depth_dev, B,
+ * Ho, Wo or sub not positive, s0 not above 0, depth_rel negative or not finite, max_rounds out of range.  XL_ERR_GRID: Ho * Wo does
+ * not fit the int cell index.
+ */
+int xl_dsac_refine_pose_rgbd_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                   const float *cam_dev, int64_t mb, int64_t mc, int64_t my, int64_t mx,
+                                   const float *depth_dev, int64_t db, int64_t dy, int64_t dx,
+                                   const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                                   const float *depth_sigma_dev, int64_t zb, int64_t zy, int64_t zx,
+                                   int B, int Ho, int Wo, const float *poses_dev /* [B,16] cam->world */,
+                                   float *out_poses_dev /* [B,16] */, double *rows_dev /* [B,64] */, double *w2c_dev /* [B,12] or NULL */,
+                                   float thr, float max_dist, float focal, float ppx, float ppy, int sub,
+                                   const float *focals_dev, float s0, float depth_rel, int max_rounds, void *stream);
+
 /* The reference-shaped single-image RGB-D entries (dsacstar.cpp:889-891) are not wired to the solver above yet: they
  * return XL_ERR_UNSUPPORTED. */
 int xl_dsac_forward_rgbd(void);

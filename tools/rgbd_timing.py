@@ -21,6 +21,14 @@ with pose_quality_batch behind it, at 95 frames x 256 hypotheses on 60 x 90 and 
 difference of the pair.
 
     python tools/rgbd_timing.py --quality [--json out.json]
+
+With --refine the RGB-D refinement is timed behind its solver, three legs alternately in the same way: forward_rgbd_batch
+(camera-tensor form) alone, with the plain refine_pose_rgbd_batch behind it and with the weighted one (sigma + depthRel 0.01)
+behind it, at 95 frames x 256 hypotheses on 60 x 90 and at 1 frame; synth.make_hetero_rgbd_scene frames: sigma 0.02 - 0.5 m,
+1 % depth noise, 30 % outliers.  The cost of a pass is its leg minus the solver leg of the same run; rounds and evaluations per
+frame and the median pose errors of the three legs are reported beside it.
+
+    python tools/rgbd_timing.py --refine [--json out.json]
 """
 import argparse
 import json
@@ -144,6 +152,56 @@ def quality_results(opt, dev):
     return results
 
 
+def refine_results(opt, dev):
+    """one dict per batch size: per-call milliseconds of the RGB-D solver alone, with the plain and with the weighted refinement
+    behind it, alternately; rounds and evaluations per frame; the median pose errors of the three legs"""
+    results = []
+    for B in (95, 1):
+        scs = [synth.make_hetero_rgbd_scene(2021 + b, depth_rel=0.01) for b in range(B)]
+        co = torch.from_numpy(np.stack([s["coords"] for s in scs])).to(dev)
+        cam = torch.from_numpy(np.stack([s["cam"] for s in scs])).to(dev)
+        sg = torch.from_numpy(np.stack([s["sigma"] for s in scs])).to(dev)
+        gt_poses = [s["pose"] for s in scs]
+        poses = [torch.zeros((B, 4, 4), dtype=torch.float32, device=dev) for _ in range(3)]
+        refined, rows = {}, {}
+
+        def solver():
+            dsacstar.forward_rgbd_batch(co, cam, poses[0], opt.hypotheses, *RGBD_ARGS)
+
+        def plain():
+            dsacstar.forward_rgbd_batch(co, cam, poses[1], opt.hypotheses, *RGBD_ARGS)
+            refined["plain"], rows["plain"] = dsacstar.refine_pose_rgbd_batch(co, cam, None, poses[1], RGBD_ARGS[0], RGBD_ARGS[2])
+
+        def weighted():
+            dsacstar.forward_rgbd_batch(co, cam, poses[2], opt.hypotheses, *RGBD_ARGS)
+            refined["weighted"], rows["weighted"] = dsacstar.refine_pose_rgbd_batch(co, cam, sg, poses[2], RGBD_ARGS[0], RGBD_ARGS[2],
+                                                                                    depthRel=0.01)
+
+        sides = (solver, plain, weighted)
+        for fn in sides:
+            fn()
+        torch.cuda.synchronize()
+        assert torch.equal(poses[0], poses[1]) and torch.equal(poses[0], poses[2])
+        first = {k: v.cpu().numpy() for k, v in rows.items()}
+        assert (first["plain"][:, 6] == 0).all() and (first["weighted"][:, 6] == 0).all()
+        legs = dict(solver=poses[0], plain=refined["plain"], weighted=refined["weighted"])
+        errs = {k: np.array([synth.pose_error(gt_poses[b], v[b].cpu().numpy().astype(np.float64)) for b in range(B)])
+                for k, v in legs.items()}
+        t, sp = time_sides(sides, opt.warmup, opt.iters, opt.rounds)
+        r = dict(mode="refine", frames=B, hypotheses=opt.hypotheses, grid=[60, 90], rounds=opt.rounds, iters=opt.iters,
+                 rgbd_ms=t[0], rgbd_spread_ms=sp[0], rgbd_with_plain_ms=t[1], rgbd_with_plain_spread_ms=sp[1],
+                 rgbd_with_weighted_ms=t[2], rgbd_with_weighted_spread_ms=sp[2],
+                 plain_cost_ms=t[1] - t[0], weighted_cost_ms=t[2] - t[0])
+        for k in ("plain", "weighted"):
+            r.update({k + "_mean_rounds": float(first[k][:, 58].mean()), k + "_mean_evals": float(first[k][:, 59].mean()),
+                      k + "_max_evals": float(first[k][:, 59].max()), k + "_converged": float(first[k][:, 60].mean()),
+                      k + "_median_chi": float(np.median(first[k][:, 7]))})
+        for k, e in errs.items():
+            r.update({k + "_median_t_err_m": float(np.median(e[:, 0])), k + "_median_r_err_deg": float(np.median(e[:, 1]))})
+        results.append(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -153,6 +211,7 @@ def main():
     ap.add_argument("--json", type=str, default=None)
     ap.add_argument("--backward", action="store_true", help="time backward_rgbd_batch beside backward_rgb_batch instead")
     ap.add_argument("--quality", action="store_true", help="time each solver alone and with its pose-quality pass behind it instead")
+    ap.add_argument("--refine", action="store_true", help="time the RGB-D solver alone and with the plain / weighted refinement behind it instead")
     opt = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rgbd_timing needs the GPU: a timing taken elsewhere says nothing")
@@ -165,8 +224,9 @@ def main():
     torch.cuda.synchronize()
     del x
 
-    results = backward_results(opt, dev) if opt.backward else quality_results(opt, dev) if opt.quality else []
-    for B in (() if opt.backward or opt.quality else (95, 1)):
+    results = (backward_results(opt, dev) if opt.backward else quality_results(opt, dev) if opt.quality
+               else refine_results(opt, dev) if opt.refine else [])
+    for B in (() if opt.backward or opt.quality or opt.refine else (95, 1)):
         coords, gt, gt_poses = synth.make_batch(2021, B, noise=0.5, outlier_ratio=0.3)
         rng = np.random.default_rng(7)
         depth_np = np.stack([depth_of(gt[b], gt_poses[b], rng, 0.01) for b in range(B)])
