@@ -74,6 +74,12 @@ struct Coords {
     }
 };
 
+// validity mask of the image (masked solver): a bit plane in LDS beside the coordinate planes, bit i & 31 of word i >> 5 <-> cell i
+struct MaskBits {
+    const uint32_t *w;
+    __device__ __forceinline__ bool usable(int i) const { return (w[i >> 5] >> (i & 31)) & 1u; }
+};
+
 // row / column of a cell index that advances by a constant stride: one division at the start, then adds and compares (an integer
 // division by the run-time grid width is ~25 of a cell's ~160 instructions in the scoring loop)
 struct CellWalk {
@@ -83,7 +89,10 @@ struct CellWalk {
 };
 
 // one sampling try (dsacstar_util.h:159-219); returns accept flag, pose = try result (identity if P3P failed)
-__device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, uint32_t hyp, uint32_t t,
+// MASKED: the same four draws; a try that drew a masked-out cell is rejected before P3P (identity pose, like a failed P3P) and
+// the coordinates of such a cell are never read
+template <bool MASKED>
+__device__ bool sample_try(const Coords &co, const MaskBits &mb, const Cam &cam, uint64_t imageKey, uint32_t hyp, uint32_t t,
                            Pose &pose, int (&cells)[4])
 {
     uint64_t st = try_state(imageKey, hyp, t);
@@ -98,7 +107,15 @@ __device__ bool sample_try(const Coords &co, const Cam &cam, uint64_t imageKey, 
         px[j] = (float)(x * cam.sub + cam.sub / 2);
         py[j] = (float)(y * cam.sub + cam.sub / 2);
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
-        co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
+        if constexpr (!MASKED) co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
+    }
+    if constexpr (MASKED) {
+        if (!(mb.usable(cells[0]) && mb.usable(cells[1]) && mb.usable(cells[2]) && mb.usable(cells[3]))) {
+            pose_identity(&pose);
+            return false;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
     }
     if (!p3p(P[0], P[1], P[2], P[3], uv, &cam, &pose)) {
         pose_identity(&pose);
@@ -171,6 +188,8 @@ struct Params {
     float thr, focal, ppx, ppy, alpha, maxReproj;
     int pairCells;                // scoring loop: two cells per lane and trip (same bits, more instruction-level parallelism)
     int cellWalk;                 // scoring loop: row / column carried along instead of divided out (XL_DSAC_CELL_WALK=0: divide)
+    const uint8_t *mask;          // masked solver: [B][Ho*Wo], nonzero = usable cell
+    int32_t *status;              // masked solver, optional: [B], 1 = fewer than four usable cells (identity pose written)
 };
 
 // LDS carve (all dynamic, 16-byte aligned pieces)
@@ -182,16 +201,19 @@ struct Smem {
     int bestIdx[kWaves];
     int anyNan[kWaves];
     unsigned cnt[2][kWaves];
-    int pad[4];
+    int pad[4];                   // masked solver: the usable cells each wave counted while staging the mask
 };
 
 // refineHyp (dsacstar_util.h:522-597), cooperative over the 256 threads of the workgroup: the pose is refined in
 // place; o.inlAcc is this thread's slice (bit j <-> cell tid + 256 j) of the inlier map of the last successful
 // re-fit, o.finalInl its size.  redSel / cntSel select the double-buffered LDS reduction scratch.
+// MASKED: `usable` is this thread's slice of the validity mask in the layout of inlAcc; a cell is an inlier iff it is usable and
+// its error is below the threshold.
 struct RefineOut { unsigned long long inlAcc; unsigned finalInl; int rounds, evals; };
 
+template <bool MASKED = false>
 __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Smem &S, int tid, int wave, int lane,
-                                            Pose &pose, RefineOut &o, int &redSel, int &cntSel)
+                                            Pose &pose, RefineOut &o, int &redSel, int &cntSel, unsigned long long usable = ~0ull)
 {
     const int N = cam.N;
     unsigned long long inlAcc = 0ull;
@@ -207,6 +229,7 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
                 if (e < cam.thr) inl |= (1ull << j);
             }
         }
+        if constexpr (MASKED) inl &= usable;
         unsigned cnt = (unsigned)__popcll(inl);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) cnt += (unsigned)__shfl_xor((int)cnt, off);
@@ -271,7 +294,14 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
 // PHASE 2: select over the S*4 per-wave bests + refine + write, one workgroup per image.
 // The split (1 then 2) exists for small batches: with B < ~100 images the fused kernel leaves most CUs idle and
 // its latency is the 64 hypotheses each wavefront walks through.  Results are identical in both forms.
-template <int PHASE>
+// MASKED (xl_dsac_forward_rgb_masked_batch): the same pipeline over the cells P.mask admits.  The mask is staged as a bit plane
+// behind the coordinate planes and its usable cells are counted; a try that drew a masked-out cell is rejected before P3P; the
+// score sums the usable cells only (a masked cell's term is selected away, so whatever is stored there reaches neither the sum
+// nor the NaN flag); an inlier is a usable cell below the threshold.  An image with fewer than four usable cells is dead: the
+// try loop is not entered, the identity pose and status 1 are written (the branch is uniform over the workgroup, and over the
+// workgroups of an image in the split form: each of them counts the same mask).  With an all-ones mask every output is the
+// unmasked kernel's, bit for bit.
+template <int PHASE, bool MASKED = false>
 __global__ __launch_bounds__(kThreads, PHASE == 1 ? 2 : 1)     // (sample + score: LDS allows two workgroups per CU, 256 registers per wave)
 void xl_dsac_forward_kernel(Params P)
 {
@@ -303,8 +333,58 @@ void xl_dsac_forward_kernel(Params P)
             sCo[2 * P.Npad + i] = q[2 * P.sc];
         }
     }
+    // ---- masked: the mask as a bit plane (each wave ballots 64 consecutive cells into two words), usable cells counted per wave
+    uint32_t *sMask = reinterpret_cast<uint32_t *>(sCo + 3 * P.Npad);
+    if constexpr (MASKED) {
+        const uint8_t *gm = P.mask + (int64_t)b * N;
+        const int nWords = (N + 31) >> 5;
+        int cnt = 0;
+        for (int base = wave * 64; base < N; base += kThreads) {
+            const int i = base + lane;
+            const bool u = (i < N) && gm[i] != 0;
+            const unsigned long long m = __ballot(u);
+            cnt += __popcll(m);
+            if (lane == 0) {
+                sMask[base >> 5] = (uint32_t)m;
+                if ((base >> 5) + 1 < nWords) sMask[(base >> 5) + 1] = (uint32_t)(m >> 32);
+            }
+        }
+        if (lane == 0) S.pad[wave] = cnt;
+    }
     __syncthreads();
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
+    MaskBits mb{ sMask };
+    unsigned long long usable = ~0ull;                              // this thread's slice of the mask: bit j <-> cell tid + 256 j
+    if constexpr (MASKED) {
+        const int nUsable = S.pad[0] + S.pad[1] + S.pad[2] + S.pad[3];
+        if (nUsable < 4) {
+            // dead image (the same decision in every thread of every workgroup of this image): nothing is sampled
+            if (PHASE != 2 && sub == 0)
+                for (int h = tid; h < P.nHyp; h += kThreads) {
+                    if (P.cells) {
+                        int32_t *o = P.cells + ((int64_t)b * P.nHyp + h) * 4;
+                        o[0] = -1; o[1] = -1; o[2] = -1; o[3] = -1;
+                    }
+                    if (P.tries) P.tries[(int64_t)b * P.nHyp + h] = 0;
+                    if (P.scores) P.scores[(int64_t)b * P.nHyp + h] = 0.0;
+                }
+            if (PHASE != 1 && tid == 0) {
+                float *o = P.outPoses + (int64_t)b * 16;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) o[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+                if (P.status) P.status[b] = 1;
+                if (P.dbg) {
+                    double *q = P.dbg + (int64_t)b * XL_DSAC_DBG_DOUBLES;
+                    q[0] = -1.0; q[1] = 0.0; q[2] = 0.0; q[3] = 0.0;
+                    for (int i = 0; i < 12; ++i) { const double v = (i < 9 && i % 4 == 0) ? 1.0 : 0.0; q[4 + i] = v; q[16 + i] = v; }
+                }
+            }
+            return;
+        }
+        usable = 0ull;
+        int j = 0;
+        for (int i = tid; i < N; i += kThreads, ++j) if (mb.usable(i)) usable |= (1ull << j);
+    }
 
     const uint64_t imageIdx = P.image0 + (uint64_t)b * P.imageStride;
     const uint64_t imageKey = image_key(P.seed, imageIdx);
@@ -326,7 +406,7 @@ void xl_dsac_forward_kernel(Params P)
             Pose p;
             int cc[4] = { 0, 0, 0, 0 };
             bool ok = false;
-            if (t < P.maxTries) ok = sample_try(co, cam, imageKey, (uint32_t)h, t, p, cc);
+            if (t < P.maxTries) ok = sample_try<MASKED>(co, mb, cam, imageKey, (uint32_t)h, t, p, cc);
             else pose_identity(&p);
             unsigned long long m = __ballot(ok);
             int src;
@@ -357,15 +437,21 @@ void xl_dsac_forward_kernel(Params P)
             double st0 = (double)(beta * (e0 - cam.thr)), st1 = (double)(beta * (e1 - cam.thr));
             st0 = 1.0 / (1.0 + det_exp(-st0));
             st1 = 1.0 / (1.0 + det_exp(-st1));
-            acc += 1.0 - st0;
-            acc += 1.0 - st1;
+            if constexpr (MASKED) {
+                acc += mb.usable(i) ? 1.0 - st0 : 0.0;
+                acc += mb.usable(i + 64) ? 1.0 - st1 : 0.0;
+            } else {
+                acc += 1.0 - st0;
+                acc += 1.0 - st1;
+            }
         }
         for (; i < N; i += 64) {
             float e = co.err(pose, i, cam);
             float stf = beta * (e - cam.thr);
             double st = (double)stf;
             st = 1.0 / (1.0 + det_exp(-st));
-            acc += 1.0 - st;
+            if constexpr (MASKED) acc += mb.usable(i) ? 1.0 - st : 0.0;
+            else acc += 1.0 - st;
         }
         double total = wave_butterfly(acc);
         double score = total * (double)fac;
@@ -457,7 +543,7 @@ void xl_dsac_forward_kernel(Params P)
     // ---- refine (refineHyp, dsacstar_util.h:522-597)
     RefineOut ro;
     int redSel = 0, cntSel = 0;
-    refine_pose(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel);
+    refine_pose<MASKED>(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel, usable);
     const int rounds = ro.rounds, evals = ro.evals;
     const unsigned finalInl = ro.finalInl;
 
@@ -471,6 +557,7 @@ void xl_dsac_forward_kernel(Params P)
             o[4 * i + 3] = (float)(-(pose.R[i] * pose.t[0] + pose.R[3 + i] * pose.t[1] + pose.R[6 + i] * pose.t[2]));
         }
         o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+        if constexpr (MASKED) if (P.status) P.status[b] = 0;
         if (P.dbg) {
             double *q = P.dbg + (int64_t)b * XL_DSAC_DBG_DOUBLES;
             q[1] = (double)rounds; q[2] = (double)finalInl; q[3] = (double)evals;
@@ -851,19 +938,28 @@ int xl_dsac_forward_sub_blocks(int B, int n_hyp)
     return S;
 }
 
-int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
-                              int B, int Ho, int Wo, float *out_poses_dev,
-                              int n_hyp, float thr, float focal, float ppx, float ppy,
-                              float alpha, float max_reproj, int sub, const float *focals_dev,
-                              uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
-                              void *stream,
-                              int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
+}  // extern "C"
+
+namespace {
+
+// the forward launch of both solvers: MASKED adds the mask and the status vector, the bit plane to the LDS carve, and launches
+// the masked instantiations (which keep an LDS limit of their own)
+template <bool MASKED>
+int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                       int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
+                       int n_hyp, float thr, float focal, float ppx, float ppy,
+                       float alpha, float max_reproj, int sub, const float *focals_dev,
+                       uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                       void *stream,
+                       int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
 {
     if (!coords_dev || !out_poses_dev || B <= 0 || Ho <= 0 || Wo <= 0 || n_hyp <= 0 || sub <= 0 || max_tries == 0)
         return XL_ERR_ARG;
+    if (MASKED && !mask_dev) return XL_ERR_ARG;
     const int N = Ho * Wo;
     if (N > kMaxCells) return XL_ERR_GRID;
     Params P;
+    P.mask = mask_dev; P.status = status_dev;
     P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
     P.outPoses = out_poses_dev; P.focals = focals_dev;
     P.cells = cells_dev; P.tries = tries_dev; P.scores = scores_dev; P.dbg = dbg_dev; P.hypPoses = nullptr;
@@ -872,15 +968,16 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
     P.thr = thr; P.focal = focal; P.ppx = ppx; P.ppy = ppy; P.alpha = alpha; P.maxReproj = max_reproj;
 
     size_t lds = ((sizeof(Smem) + 15) & ~size_t(15)) + (size_t)3 * P.Npad * sizeof(float);
+    if (MASKED) lds += sizeof(uint32_t) * (size_t)((N + 31) / 32);          // the bit plane: 676 B at 60x90
     if (lds > 160 * 1024) return XL_ERR_GRID;
     static XlLdsLimit configured;
     int cfgDev;
     if (configured.needs(lds, &cfgDev)) {
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<0>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<0, MASKED>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASKED>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<2>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<2, MASKED>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured.done(lds, cfgDev);
     }
@@ -892,16 +989,46 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
     static const int cellWalk = getenv("XL_DSAC_CELL_WALK") ? atoi(getenv("XL_DSAC_CELL_WALK")) : 1;
     P.cellWalk = cellWalk;
     if (S == 1) {
-        hipLaunchKernelGGL(xl_dsac_forward_kernel<0>, dim3(B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<0, MASKED>), dim3(B), dim3(kThreads), lds, st, P);
     } else {
         const size_t bytes = sizeof(double) * ((size_t)B * S * kWaves * 16 + (size_t)B * 12);
         XL_HIP(hipMallocAsync((void **)&P.part, bytes, st));
-        hipLaunchKernelGGL(xl_dsac_forward_kernel<1>, dim3(S, B), dim3(kThreads), lds, st, P);
-        hipLaunchKernelGGL(xl_dsac_forward_kernel<2>, dim3(B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASKED>), dim3(S, B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<2, MASKED>), dim3(B), dim3(kThreads), lds, st, P);
         XL_HIP(hipFreeAsync(P.part, st));
     }
     XL_HIP(hipGetLastError());
     return XL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                              int B, int Ho, int Wo, float *out_poses_dev,
+                              int n_hyp, float thr, float focal, float ppx, float ppy,
+                              float alpha, float max_reproj, int sub, const float *focals_dev,
+                              uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                              void *stream,
+                              int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
+{
+    return forward_rgb_launch<false>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, out_poses_dev, nullptr, n_hyp, thr, focal,
+                                     ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream,
+                                     cells_dev, tries_dev, scores_dev, dbg_dev);
+}
+
+int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                     int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
+                                     int n_hyp, float thr, float focal, float ppx, float ppy,
+                                     float alpha, float max_reproj, int sub, const float *focals_dev,
+                                     uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                                     void *stream,
+                                     int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
+{
+    return forward_rgb_launch<true>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, out_poses_dev, status_dev, n_hyp, thr, focal,
+                                    ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream,
+                                    cells_dev, tries_dev, scores_dev, dbg_dev);
 }
 
 // The reference's call shape (utils/evaluation.py:160-172): ONE frame, host tensors in, host pose out, blocking.  Round 6: the device
@@ -1030,6 +1157,7 @@ int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, 
     P.thr = thr; P.focal = focal; P.ppx = ppx; P.ppy = ppy; P.alpha = alpha; P.maxReproj = max_reproj;
     P.part = part; P.S = S;
     P.pairCells = 1; P.cellWalk = 1;
+    P.mask = nullptr; P.status = nullptr;
     BwdParams Q;
     Q.coords = coords_dev; Q.sb = sb; Q.sc = sc; Q.sy = sy; Q.sx = sx;
     Q.grad = grad_dev; Q.gsb = gsb; Q.gsc = gsc; Q.gsy = gsy; Q.gsx = gsx;

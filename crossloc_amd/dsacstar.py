@@ -13,6 +13,10 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
     (thread_rand.cpp:17); here every call consumes one "image index" from a module counter
     (reset with `set_image_index`), and results do not depend on thread or rank count.
   * `forward_rgb_batch` localises B images per launch (the reference is batch-1 only).
+  * `forward_rgb_masked_batch` is forward_rgb_batch over a per-cell validity mask (uint8 / bool [B,Ho,Wo], nonzero = usable; build
+    one with crossloc_amd.evaluation.cell_mask): masked-out cells are never sampled, scored or counted as inliers, and what is
+    stored there cannot influence the result.  It returns a status per image (1: fewer than four usable cells, identity pose).
+    The mask reaches the solver only: not the quality / refinement passes, the backward passes, the RGB-D solver or forward_rgb.
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
     form `backward_rgb_batch` run on the GPU as well.
   * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
@@ -107,6 +111,65 @@ def forward_rgb_batch(sceneCoordinates, outPoses, ransacHypotheses, inlierThresh
             _ptr(cells), _ptr(tries), _ptr(scores), _ptr(dbg))
     _lib.check(rc)
     return out
+
+
+def forward_rgb_masked_batch(sceneCoordinates, mask, outPoses, ransacHypotheses, inlierThreshold, focalLength, ppointX,
+                             ppointY, inlierAlpha, maxReproj, subSampling, image0=0, image_stride=1, focals=None,
+                             seed=None, max_tries=None, debug=False):
+    """forward_rgb_batch over the cells `mask` admits.  mask: uint8 or bool [B,Ho,Wo] CUDA contiguous on the device of
+    sceneCoordinates, nonzero = usable; the other arguments as in forward_rgb_batch.  A try that drew a masked-out cell is rejected
+    before P3P (the draws themselves are the unmasked solver's, so the expected number of tries grows as (usable fraction)^-4),
+    the score sums the usable cells only, and an inlier of the refinement is a usable cell below the threshold; the values stored
+    at masked-out cells (NaN and Inf included) influence no output bit, and with an all-ones mask every output is
+    forward_rgb_batch's bit for bit.  An image with fewer than four usable cells gets the 4x4 identity and status 1 (with
+    debug: tries 0, scores 0, cells -1, winner -1).  Returns status, int32 [B] on the device (asynchronous on the current stream);
+    with debug=True the debug dict of forward_rgb_batch with `status` in it.  Shape, dtype and device mismatches raise
+    RuntimeError before any device work.  The quality and refinement passes, the backward passes, the RGB-D solver and the
+    single-image forward_rgb take no mask."""
+    _check_coords(sceneCoordinates, True)
+    if not isinstance(mask, torch.Tensor) or not isinstance(outPoses, torch.Tensor):
+        raise RuntimeError("mask and outPoses must be torch.Tensors")
+    if not sceneCoordinates.is_cuda or not outPoses.is_cuda or not mask.is_cuda:
+        raise RuntimeError("forward_rgb_masked_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise RuntimeError("mask must be uint8 or bool, got %s" % str(mask.dtype).replace("torch.", ""))
+    if tuple(mask.shape) != (B, Ho, Wo) or not mask.is_contiguous():
+        raise RuntimeError("mask must be a contiguous [B,Ho,Wo] tensor like sceneCoordinates, got %s" % (tuple(mask.shape),))
+    if mask.device != dev or outPoses.device != dev:
+        raise RuntimeError("mask and outPoses must be on the device of sceneCoordinates")
+    if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4) or not outPoses.is_contiguous():
+        raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor")
+    if int(ransacHypotheses) <= 0:
+        raise RuntimeError("ransacHypotheses must be positive")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if focals is not None:
+        focals = focals.to(device=dev, dtype=torch.float32).contiguous()
+        if focals.numel() != B:
+            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    status = torch.empty((B,), dtype=torch.int32, device=dev)                     # (the kernel writes every entry)
+    out = None
+    cells = tries = scores = dbg = None
+    if debug:
+        cells = torch.zeros((B, ransacHypotheses, 4), dtype=torch.int32, device=dev)
+        tries = torch.zeros((B, ransacHypotheses), dtype=torch.int32, device=dev)
+        scores = torch.zeros((B, ransacHypotheses), dtype=torch.float64, device=dev)
+        dbg = torch.zeros((B, 28), dtype=torch.float64, device=dev)
+        out = dict(cells=cells, tries=tries, scores=scores, dbg=dbg, status=status)
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_forward_rgb_masked_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), _ptr(outPoses), _ptr(status),
+            int(ransacHypotheses), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY),
+            float(inlierAlpha), float(maxReproj), int(subSampling), _ptr(focals),
+            int(RANSAC_SEED if seed is None else seed), int(image0), int(image_stride),
+            int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream),
+            _ptr(cells), _ptr(tries), _ptr(scores), _ptr(dbg))
+    _lib.check(rc)
+    return out if debug else status
 
 
 def forward_rgb(sceneCoordinates, outPose, ransacHypotheses, inlierThreshold, focalLength, ppointX, ppointY,

@@ -224,6 +224,77 @@ def _focal_args(focal, n):
     return float(f[0]), f
 
 
+def cell_mask(sigma=None, max_sigma=None, class_map=None, exclude_classes=(), labels=None, nodata_value=-1, sub=8):
+    """The per-cell validity mask of dsacstar.forward_rgb_masked_batch: uint8 [B,Ho,Wo] on the device of its inputs, 1 = usable,
+    the AND of the criteria given (at least one):
+      sigma, max_sigma   sigma [B,Ho,Wo] (e.g. the uncertainty channel pred[:, 3] of an MLE network): usable iff sigma <= max_sigma
+                         (a NaN sigma is not usable)
+      class_map, exclude_classes   integer classes (e.g. the arg-max of the semantics network), [B,Ho,Wo] per cell or full size
+                         [B,Ho*sub,Wo*sub], which is read at the cell centres (sub*x + sub//2, sub*y + sub//2); usable iff the
+                         class is not in exclude_classes.  A map that comes alone is taken per cell.
+      labels, nodata_value   a label map [B,C,Ho,Wo] or [B,Ho,Wo]: usable iff no channel of the cell is nodata_value
+                         (pick_valid_points)
+    Plain torch ops on small tensors: plumbing, not a hot path."""
+    if (sigma is None) != (max_sigma is None):
+        raise RuntimeError("cell_mask: sigma and max_sigma go together")
+    parts, shape = [], None
+    if sigma is not None:
+        if not isinstance(sigma, torch.Tensor) or sigma.dim() != 3:
+            raise RuntimeError("cell_mask: sigma must be a [B,Ho,Wo] tensor")
+        parts.append(sigma <= float(max_sigma))
+        shape = tuple(sigma.shape)
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.dim() not in (3, 4):
+            raise RuntimeError("cell_mask: labels must be a [B,C,Ho,Wo] or [B,Ho,Wo] tensor")
+        lab = labels if labels.dim() == 4 else labels[:, None]
+        has_data = pick_valid_points(lab, nodata_value)
+        if shape is not None and tuple(has_data.shape) != shape:
+            raise RuntimeError("cell_mask: labels %s do not match the %s cells of sigma" % (tuple(labels.shape), shape))
+        parts.append(has_data)
+        shape = tuple(has_data.shape)
+    if class_map is not None:
+        if not isinstance(class_map, torch.Tensor) or class_map.dim() != 3 or class_map.dtype.is_floating_point:
+            raise RuntimeError("cell_mask: class_map must be an integer [B,H,W] tensor")
+        cm = class_map
+        if shape is not None and tuple(cm.shape) != shape:
+            full = (shape[0], shape[1] * int(sub), shape[2] * int(sub))
+            if tuple(cm.shape) != full:
+                raise RuntimeError("cell_mask: class_map %s is neither per cell %s nor full size %s" % (tuple(cm.shape), shape, full))
+            cm = cm[:, int(sub) // 2::int(sub), int(sub) // 2::int(sub)]
+        keep = torch.ones(cm.shape, dtype=torch.bool, device=cm.device)
+        for c in exclude_classes:
+            keep &= cm != int(c)
+        parts.append(keep)
+    if not parts:
+        raise RuntimeError("cell_mask needs at least one criterion: sigma and max_sigma, class_map or labels")
+    out = parts[0]
+    for p in parts[1:]:
+        out = out & p.to(out.device)
+    return out.to(torch.uint8).contiguous()
+
+
+def _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine):
+    """The mask reaches the RGB solver only.  -> whether the masked solver runs"""
+    if mask is None and mask_max_sigma is None:
+        return False
+    if mask is not None and mask_max_sigma is not None:
+        raise RuntimeError("mask and mask_max_sigma: pass one of them (AND a mask of your own with cell_mask(sigma=...))")
+    for name, on in (("depth", depth is not None), ("cam_coords", cam_coords is not None), ("quality", bool(quality)),
+                     ("refine", bool(refine))):
+        if on:
+            raise RuntimeError("mask together with %s is not yet supported: the mask reaches the RGB solver only" % name)
+    return True
+
+
+def _solver_mask(mask, mask_max_sigma, pred, nt):
+    """The mask the solver reads: the caller's, or sigma <= mask_max_sigma on the prediction's uncertainty channel"""
+    if mask is not None:
+        return mask
+    if pred.shape[1] <= nt:
+        raise RuntimeError("mask_max_sigma needs the network's uncertainty channel, and this network has none; pass mask=")
+    return cell_mask(sigma=pred[:, nt], max_sigma=mask_max_sigma)
+
+
 def _is_rgbd_quality(quality):
     return isinstance(quality, str) and quality == "rgbd"
 
@@ -284,7 +355,8 @@ def _refine_rgbd(refine, coords, cam_coords, depth, sg, poses, rgbd_threshold, m
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
                    quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0,
-                   refine=False, sigma=None, sigma_floor_px=1.0, depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01):
+                   refine=False, sigma=None, sigma_floor_px=1.0, depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01,
+                   mask=None, mask_max_sigma=None):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
     (:354) unless `refine="sigma"` asks for it, HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda,
     predictions [B,4,Ho,Wo]).
@@ -311,10 +383,16 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     `rgbd_threshold` and `max_dist_error` in centimetres; `quality=True` still rates the pose by its reprojection residuals.
     `quality="rgbd"` (only with `depth` or `cam_coords`): the RGB-D pose-quality pass (dsacstar.pose_quality_rgbd_batch) runs
     behind the RGB-D solver instead and rates the pose by its metric 3-D residuals; its rows [B,64] are the third value
-    (status and sigma_pos_m in the columns of the RGB row, so selective_accuracy takes either)."""
+    (status and sigma_pos_m in the columns of the RGB row, so selective_accuracy takes either).
+    `mask` (uint8 / bool [B,Ho,Wo], nonzero = usable; see cell_mask) or `mask_max_sigma` (the mask sigma <= mask_max_sigma from
+    the prediction's uncertainty channel; RuntimeError if the network has none): the masked RGB solver
+    (dsacstar.forward_rgb_masked_batch) runs in place of the plain one and its status [B] int32 (1: fewer than four usable
+    cells, identity pose) is appended as the LAST value.  Not yet with `depth` / `cam_coords` / `quality` / `refine`
+    (RuntimeError).  Without a mask nothing changes."""
     import dsacstar
     if depth is not None and cam_coords is not None:
         raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
+    masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine)
     _check_quality_mode(quality, depth, cam_coords)
     refine = _check_refine_mode(refine, depth, cam_coords) and refine
     with torch.no_grad():
@@ -330,6 +408,12 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
                                     image0=image0, image_stride=image_stride, depth=depth, focalLength=f0,
                                     ppointX=float(image_w / 2), ppointY=float(image_h / 2),
                                     subSampling=network.OUTPUT_SUBSAMPLE, focals=focals)
+    elif masked:
+        status = dsacstar.forward_rgb_masked_batch(coords, _solver_mask(mask, mask_max_sigma, pred, nt), poses, n_hyp, threshold,
+                                                   f0, float(image_w / 2), float(image_h / 2), inlier_alpha, max_pixel_error,
+                                                   network.OUTPUT_SUBSAMPLE, image0=image0, image_stride=image_stride,
+                                                   focals=focals)
+        return (poses, pred, status)
     else:
         dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
                                    inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
@@ -409,7 +493,7 @@ class PipelinedLocalizer:
 
     def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False, depth=None,
                cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0, refine=False, sigma=None, sigma_floor_px=1.0,
-               depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01):
+               depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01, mask=None, mask_max_sigma=None):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
         side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
@@ -418,10 +502,13 @@ class PipelinedLocalizer:
         `sigma_floor_px` as in localize_batch: the refinement runs behind the RGB solver on the side stream, the first value
         is the refined poses, its rows [B,64] are the last value, and a `quality=True` pass rates the refined pose.
         `refine` "rgbd_inliers" / "rgbd_sigma" with `depth_sigma`, `depth_rel` and `sigma_floor_m` (only with `depth` or
-        `cam_coords`): the RGB-D refinement runs behind the RGB-D solver on the side stream, as in localize_batch."""
+        `cam_coords`): the RGB-D refinement runs behind the RGB-D solver on the side stream, as in localize_batch.
+        `mask` / `mask_max_sigma` as in localize_batch: the masked RGB solver runs on the side stream and its status [B] int32 is
+        appended as the last value; not yet with `depth` / `cam_coords` / `quality` / `refine`."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
+        masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine)
         _check_quality_mode(quality, depth, cam_coords)
         refine = _check_refine_mode(refine, depth, cam_coords) and refine
         pred, events = self.forward_cnn(images, plant)
@@ -438,6 +525,14 @@ class PipelinedLocalizer:
                                             ppointX=float(self.w / 2), ppointY=float(self.h / 2),
                                             subSampling=self.net.OUTPUT_SUBSAMPLE, focals=focals)
                 (depth if depth is not None else cam_coords).record_stream(self.side)
+            elif masked:
+                f0, focals = _focal_args(self.focal, coords.shape[0])
+                status = dsacstar.forward_rgb_masked_batch(coords, _solver_mask(mask, mask_max_sigma, pred, self.net.num_task_channel),
+                                                           poses, self.n_hyp, self.thr, f0, float(self.w / 2), float(self.h / 2),
+                                                           self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE, image0=image0,
+                                                           image_stride=image_stride, focals=focals)
+                if mask is not None:
+                    mask.record_stream(self.side)
             else:
                 dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
@@ -474,6 +569,9 @@ class PipelinedLocalizer:
         pred.record_stream(self.side)
         poses.record_stream(self.side)
         tail = ()
+        if masked:
+            status.record_stream(torch.cuda.current_stream())    # allocated on the side stream, read by the caller's after finish()
+            return (poses, pred, status)
         if refine:
             # allocated on the side stream, read by the caller's after finish()
             poses.record_stream(torch.cuda.current_stream())

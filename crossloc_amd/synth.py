@@ -108,6 +108,28 @@ def make_hetero_scene(seed, sigma_range=(0.1, 3.0), outlier_ratio=0.3, Ho=IMAGE_
                 focal=float(focal), ppx=float(ppx), ppy=float(ppy), sigma=sigma.astype(np.float32))
 
 
+def make_decoy_scene(seed, decoy=0.6, noise=0.5, Ho=IMAGE_H // SUBSAMPLE, Wo=IMAGE_W // SUBSAMPLE, sub=SUBSAMPLE, focal=FOCAL):
+    """One frame whose larger part is structured garbage: two cameras P and Q are drawn; every cell holds the coordinates camera P
+    sees plus Gaussian noise, then the top round(decoy * Ho) rows take EXACTLY the coordinates camera Q would see there - wrong,
+    but consistent with each other, which the soft-inlier count cannot tell from the truth.  Returns make_scene's dict (pose = P)
+    plus mask [Ho,Wo] uint8 (0 on the decoy rows, 1 elsewhere) and decoy_pose (Q).  A function of its own with a generator of
+    its own: the draws of make_scene do not move."""
+    rng = np.random.default_rng([seed, 0x4443])
+    ppx, ppy = Wo * sub / 2.0, Ho * sub / 2.0
+    pose = random_pose(rng)
+    decoy_pose = random_pose(rng)
+    gt, hit = raycast(pose, Ho, Wo, sub, focal, ppx, ppy)
+    pred = gt + rng.normal(0.0, noise, size=gt.shape) if noise > 0 else gt.copy()
+    rows = int(round(decoy * Ho))
+    other, _ = raycast(decoy_pose, Ho, Wo, sub, focal, ppx, ppy)
+    pred[:, :rows] = other[:, :rows]
+    mask = np.ones((Ho, Wo), np.uint8)
+    mask[:rows] = 0
+    gt_lab = np.where(hit[None], gt, NODATA)
+    return dict(coords=pred.astype(np.float32), gt_coords=gt_lab.astype(np.float32), pose=pose,
+                focal=float(focal), ppx=float(ppx), ppy=float(ppy), mask=mask, decoy_pose=decoy_pose)
+
+
 def camera_from_depth(depth, focal, ppx, ppy, sub=SUBSAMPLE):
     """Camera coordinates [3,Ho,Wo] float32 of a depth map [Ho,Wo] float32: the ray through the centre of every cell times the
     depth, every step in float32 - the formula the RGB-D solver applies to `depth` itself."""

@@ -68,6 +68,42 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
                               int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
 
 /*
+ * The RGB solver over a per-cell validity mask (no reference counterpart): xl_dsac_forward_rgb_batch with the cells the
+ * caller rules out taken away from every stage that chooses the hypothesis.  Same kernels (a template instantiation of
+ * their own), same launch forms (xl_dsac_forward_sub_blocks), same arguments, plus
+ *
+ *   mask_dev       [B,Ho,Wo] uint8, contiguous: nonzero = the cell is usable
+ *   status_dev     optional [B] int32: 0, or 1 for an image with fewer than four usable cells
+ *
+ * stage   the mask is kept in LDS as a bit plane of ceil(Ho*Wo / 32) words beside the coordinate planes (676 B at 60x90);
+ *         the workgroup counts the usable cells.  A grid whose planes fit in 160 KB only without it returns XL_ERR_GRID.
+ * sample  the four cells of a try are drawn exactly as in the unmasked solver (same generator state, same draws).  A try
+ *         that drew a masked-out cell is rejected before P3P: its pose is the identity, like a failed P3P, and it counts as
+ *         a try.  The first accepted try still wins; the expected number of tries grows as (usable fraction)^-4.  After
+ *         max_tries the hypothesis is the last try's result - the identity pose if the mask rejected that try.
+ * score   the sum runs over the usable cells; the term of a masked-out cell is selected away, never multiplied by zero, so
+ *         whatever is stored there (NaN, Inf) reaches neither the sum nor the NaN flag.  The factor stays alpha / Wo / Ho.
+ * select  unchanged.
+ * refine  a cell is an inlier iff it is usable and its error is below thr; the rest of the refinement is unchanged.
+ *
+ * With fewer than four usable cells nothing is sampled: the 4x4 identity is written, status 1, and with debug outputs
+ * tries 0, scores 0, cells -1, dbg [0] -1, [1..3] 0 and the identity pose in [4..15] and [16..27].
+ *
+ * Identity A: with an all-ones mask every output equals xl_dsac_forward_rgb_batch's bit for bit.
+ * Identity B: the values stored at masked-out cells influence no output bit.
+ *
+ * XL_ERR_ARG for a null mask and for everything xl_dsac_forward_rgb_batch refuses, before any HIP call.  Not covered: the
+ * quality and refinement passes, the backward passes, the RGB-D solver and the single-image host entry point take no mask.
+ */
+int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                     int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
+                                     int n_hyp, float thr, float focal, float ppx, float ppy,
+                                     float alpha, float max_reproj, int sub, const float *focals_dev,
+                                     uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                                     void *stream,
+                                     int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
+
+/*
  * Reference-shaped single-image call on HOST memory: same argument meaning as
  * dsacstar.forward_rgb(sceneCoordinates[1,3,Ho,Wo] CPU, outPose[4,4] CPU, ...)
  * (utils/evaluation.py:162-172).  Copies in, runs the batch kernel with B=1 on `stream`,

@@ -1,0 +1,140 @@
+"""Times the masked RGB solver (dsacstar.forward_rgb_masked_batch) against the plain one, with HIP events on warm clocks.  Not
+a test and not part of bench.py; no bound is set on the masked legs.
+
+  95 frames x 256 hypotheses on 60 x 90 (the bench batch) and 1 frame.  Legs:
+    unmasked       forward_rgb_batch on make_scene frames (0.5 m noise, 30 % outliers)
+    all_ones       forward_rgb_masked_batch, all-ones mask, the same frames (the same bits out: what the mask costs by itself)
+    half           forward_rgb_masked_batch, a seeded random 50 % mask, the same frames
+    decoy_band     forward_rgb_masked_batch on make_decoy_scene frames (top 60 % of the rows a second camera's view) with
+                   their band mask - 40 % usable, so about 39 times the tries per hypothesis
+
+The legs run alternately in the same process (rounds of `--iters` calls each) after `--warmup` calls; the figure of a leg is the
+median over rounds of the per-call time, with its spread (max - min over rounds).  The mean tries per hypothesis of every leg
+are reported beside its time, since the masked solver's cost follows them.
+
+`--unmasked_only` times the first leg alone and needs nothing of this commit's interface: run it under a build of the parent
+commit too (XL_TIMING_TREE=<that tree>: the package is imported from there), alternating the two processes, to see that the
+unmasked instantiation did not move.
+This commit's unmasked time may exceed the parent's by no more than the larger of the two spreads.
+
+    python tools/masked_timing.py [--json out.json] [--unmasked_only]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.environ.get("XL_TIMING_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import dsacstar                                                 # noqa: E402
+from crossloc_amd import synth                                  # noqa: E402
+
+ARGS = (10.0, synth.FOCAL, 360.0, 240.0, 100.0, 100.0, 8)       # threshold, focal, ppx, ppy, alpha, max reprojection, subsampling
+
+
+def time_legs(fns, warmup, iters, rounds):
+    """median per-call milliseconds of every leg and their spreads, alternating rounds; a round ends in an event synchronise"""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    out = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(iters):
+                fn()
+            b.record()
+            b.synchronize()
+            out[k].append(a.elapsed_time(b) / iters)
+    return [float(np.median(v)) for v in out], [float(np.max(v) - np.min(v)) for v in out]
+
+
+def mean_tries(out):
+    """mean tries per hypothesis of a debug call (an exhausted hypothesis counts its whole budget)"""
+    return float(out["tries"].abs().to(torch.float64).mean())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--hypotheses", type=int, default=256)
+    ap.add_argument("--unmasked_only", action="store_true")
+    ap.add_argument("--json", type=str, default=None)
+    opt = ap.parse_args()
+    if opt.rounds < 5:
+        raise SystemExit("masked_timing: at least 5 rounds")
+    if not torch.cuda.is_available():
+        raise SystemExit("masked_timing needs the GPU: a timing taken elsewhere says nothing")
+    dev = torch.device("cuda")
+
+    # warm clocks: a second of streaming work before the first timed window
+    x = torch.rand(64 << 20, device=dev)
+    for _ in range(200):
+        x.mul_(1.0000001)
+    torch.cuda.synchronize()
+    del x
+
+    results = []
+    for B in (95, 1):
+        co = torch.from_numpy(np.stack([synth.make_scene(2021 + i)["coords"] for i in range(B)])).to(dev)
+        poses = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+
+        def unmasked(debug=False):
+            return dsacstar.forward_rgb_batch(co, poses, opt.hypotheses, *ARGS, debug=debug)
+
+        row = dict(frames=B, hypotheses=opt.hypotheses, grid=[60, 90],
+                   solver_launch_form=int(dsacstar._lib.lib().xl_dsac_forward_sub_blocks(B, opt.hypotheses)))
+        if opt.unmasked_only:
+            (tu,), (su,) = time_legs((unmasked,), opt.warmup, opt.iters, opt.rounds)
+            row.update(unmasked_ms=tu, unmasked_spread_ms=su, unmasked_mean_tries=mean_tries(unmasked(True)))
+            results.append(row)
+            continue
+
+        decoys = [synth.make_decoy_scene(2021 + i, decoy=0.6) for i in range(B)]
+        dco = torch.from_numpy(np.stack([s["coords"] for s in decoys])).to(dev)
+        band = torch.from_numpy(np.stack([s["mask"] for s in decoys])).to(dev)
+        ones = torch.ones((B, 60, 90), dtype=torch.uint8, device=dev)
+        half = torch.from_numpy((np.random.default_rng(2021).random((B, 60, 90)) < 0.5).astype(np.uint8)).to(dev)
+        mposes = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+
+        def all_ones(debug=False):
+            return dsacstar.forward_rgb_masked_batch(co, ones, mposes, opt.hypotheses, *ARGS, debug=debug)
+
+        def half_mask(debug=False):
+            return dsacstar.forward_rgb_masked_batch(co, half, mposes, opt.hypotheses, *ARGS, debug=debug)
+
+        def decoy_band(debug=False):
+            return dsacstar.forward_rgb_masked_batch(dco, band, mposes, opt.hypotheses, *ARGS, debug=debug)
+
+        unmasked()
+        all_ones()
+        torch.cuda.synchronize()
+        assert torch.equal(poses, mposes), "identity A: the all-ones mask must give the unmasked solver's poses"
+        legs = (("unmasked", unmasked), ("all_ones", all_ones), ("half", half_mask), ("decoy_band", decoy_band))
+        med, spread = time_legs([fn for _, fn in legs], opt.warmup, opt.iters, opt.rounds)
+        for (name, fn), t, s in zip(legs, med, spread):
+            row.update({name + "_ms": t, name + "_spread_ms": s, name + "_mean_tries": mean_tries(fn(True))})
+        gt = np.stack([s["pose"] for s in decoys])
+        decoy_band()
+        torch.cuda.synchronize()
+        row["decoy_band_median_t_err_m"] = float(np.median([synth.pose_error(g, p)[0] for g, p in zip(gt, mposes.cpu().numpy())]))
+        dsacstar.forward_rgb_batch(dco, poses, opt.hypotheses, *ARGS)
+        torch.cuda.synchronize()
+        row["decoy_unmasked_median_t_err_m"] = float(np.median([synth.pose_error(g, p)[0] for g, p in zip(gt, poses.cpu().numpy())]))
+        results.append(row)
+    for r in results:
+        print(json.dumps(r))
+    if opt.json:
+        os.makedirs(os.path.dirname(os.path.abspath(opt.json)), exist_ok=True)
+        with open(opt.json, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
