@@ -22,14 +22,16 @@
 //   write      inverse rigid transform as float 4x4 (pose2trans, dsacstar_util.h:759-770)
 //
 // Arithmetic contract: compiled with -ffp-contract=off; every transcendental is a fixed polynomial in
-// + - * / sqrt; reductions use a fixed order.  What one lane computes on its own (the polynomials, the RNG, projection,
-// quartic, P3P, the Cholesky step, the backward pass's derivatives) lives in xl_dsac_math.h, which the CPU oracle compiles
-// too; this file keeps what is parallel: LDS staging, ballots, wave and block reductions, the LM state machine, the
-// kernels and the host entry points.  The order of a block sum is stated in xl_dsac_reduce.h (block_sum), the 12-double pose form
-// in xl_dsac_math.h (pose_load12 / pose_store12).  tests/test_dsac_gpu.py checks sampled cells, tries, scores, winner and refined pose
-// against oracle/dsac_oracle.c bit for bit - a check of that parallel part and of gcc == hipcc, not of the shared
-// formulas (those: tests/indep_dsac.py and tests/test_oracle_dsac_pin.py).  The oracle includes the header; nothing here
-// includes the oracle.
+// + - * / sqrt; reductions use a fixed order.  What one lane computes on its own lives in xl_dsac_math.h, which the CPU oracle
+// compiles too: the polynomials, the RNG, the camera record (cam_make) and the pixel centre of a cell (cell_px), projection, cell
+// error and the soft-inlier sigmoid (soft_inlier_st), quartic, P3P, the per-cell normal equations (XL_PNP_CELL_ROWS, pnp_cell_normal_eq), the
+// Cholesky step, the LM stop rule and its constants (lm_step_small, XLM_LM_MAX_ITER), the not-NaN test of an LM result
+// (pose_not_nan), the pose forms (pose_load12 / pose_store12, pose_to_c2w16) and the backward pass's derivatives.  This file
+// keeps what is parallel: LDS staging (stage_coords), ballots, wave and block reductions, the LM state machine, the kernels and
+// the host entry points.  The order of a block sum is stated in xl_dsac_reduce.h (block_sum).  tests/test_dsac_gpu.py checks
+// sampled cells, tries, scores, winner and refined pose against oracle/dsac_oracle.c bit for bit - a check of that parallel part
+// and of gcc == hipcc, not of the shared formulas (those: tests/indep_dsac.py and tests/test_oracle_dsac_pin.py).  The oracle
+// includes the header; nothing here includes the oracle.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -45,11 +47,8 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxCellsPerThread = 64;
 constexpr int kMaxCells = kThreads * kMaxCellsPerThread;     // 16384
-constexpr int kLmMaxIter = 20;                               // cv::solvePnP ITERATIVE term criteria
-constexpr double kFltEps = 1.1920928955078125e-07;
 
-// Pose, Cam, V3 and every function one lane evaluates on its own (deterministic exp / sincos / atan2, RNG, projection,
-// quartic, P3P, Cholesky step, the backward pass's derivatives): shared with the CPU oracle, written once
+// Pose, Cam, V3 and every function one lane evaluates on its own (listed at the top): shared with the CPU oracle, written once
 #include "xl_dsac_math.h"
 #include "xl_dsac_reduce.h"             // the canonical block sum (block_sum: the order is stated there) and wave_bcast_pose
 
@@ -88,6 +87,19 @@ struct CellWalk {
     __device__ __forceinline__ void step() { y += sy; x += sx; if (x >= Wo) { x -= Wo; ++y; } }
 };
 
+// scene coordinates of one image (g: its first element; sc, sy, sx: the caller's strides) -> LDS as three planes of Npad floats;
+// serves the forward kernel and the backward kernels, whose parameter records differ
+__device__ __forceinline__ void stage_coords(const float *g, int64_t sc, int64_t sy, int64_t sx, int Wo, int N, int Npad, float *sCo, int tid)
+{
+    for (int i = tid; i < N; i += kThreads) {
+        int y = i / Wo, x = i - y * Wo;
+        const float *q = g + (int64_t)y * sy + (int64_t)x * sx;
+        sCo[i] = q[0];
+        sCo[Npad + i] = q[sc];
+        sCo[2 * Npad + i] = q[2 * sc];
+    }
+}
+
 // one sampling try (dsacstar_util.h:159-219); returns accept flag, pose = try result (identity if P3P failed)
 // MASKED: the same four draws; a try that drew a masked-out cell is rejected before P3P (identity pose, like a failed P3P) and
 // the coordinates of such a cell are never read
@@ -104,8 +116,8 @@ __device__ bool sample_try(const Coords &co, const MaskBits &mb, const Cam &cam,
         int x = draw(st, 2 * j, cam.Wo);
         int y = draw(st, 2 * j + 1, cam.Ho);
         cells[j] = y * cam.Wo + x;
-        px[j] = (float)(x * cam.sub + cam.sub / 2);
-        py[j] = (float)(y * cam.sub + cam.sub / 2);
+        px[j] = cell_px(&cam, x);
+        py[j] = cell_px(&cam, y);
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
         if constexpr (!MASKED) co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
     }
@@ -135,34 +147,25 @@ __device__ bool sample_try(const Coords &co, const MaskBits &mb, const Cam &cam,
 
 // ------------------------------------------------------------------------------ LM pieces
 
-// per-thread accumulation of the normal equations over this thread's inlier cells
-__device__ __forceinline__ void normal_eq_thread(const Coords &co, const Cam &cam, const Pose &p,
+// per-thread accumulation of the normal equations over this thread's inlier cells.  The rows are the shared statement
+// (XL_PNP_CELL_ROWS of xl_dsac_math.h); the six lines that add them up restate pnp_cell_normal_eq here instead of calling it: with the
+// call (force-inlined) hipcc schedules refine_pose differently at equal register figures and the single-frame solve ran 0.2562-0.2565 ms
+// against the parent's 0.2532-0.2540 (+1.25 %, 95 frames +0.15 %: both outside the run-to-run range); expanded here it is at the
+// hand-written loop's time (profiles/rgb_solver_shared_math.txt)
+__device__ __forceinline__ void normal_eq_thread(const Coords &co, const Cam &camRef, const Pose &pose,
                                                  unsigned long long inl, int tid, double (&a)[28])
 {
+    const Cam *cam = &camRef;
+    const Pose *p = &pose;
 #pragma unroll
     for (int k = 0; k < 28; ++k) a[k] = 0.0;
     int j = 0;
-    for (int i = tid; i < cam.N; i += kThreads, ++j) {
+    for (int i = tid; i < cam->N; i += kThreads, ++j) {
         if (!((inl >> j) & 1ull)) continue;
-        int y = i / cam.Wo, x = i - y * cam.Wo;
+        int y = i / cam->Wo, x = i - y * cam->Wo;
         double X, Y, Z;
         co.fetch(i, X, Y, Z);
-        double qx = p.R[0] * X + p.R[1] * Y + p.R[2] * Z;
-        double qy = p.R[3] * X + p.R[4] * Y + p.R[5] * Z;
-        double qz = p.R[6] * X + p.R[7] * Y + p.R[8] * Z;
-        double xc = qx + p.t[0], yc = qy + p.t[1], zc = qz + p.t[2];
-        double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-        double xn = xc * z, yn = yc * z;
-        double ru = (xn * cam.f + cam.cx) - (double)(float)(x * cam.sub + cam.sub / 2);
-        double rv = (yn * cam.f + cam.cy) - (double)(float)(y * cam.sub + cam.sub / 2);
-        double fa = cam.f * z;
-        double fc = -(fa * xn);
-        double fd = -(fa * yn);
-        double Ju[6], Jv[6];
-        Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy);
-        Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc;
-        Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx;
-        Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd;
+        XL_PNP_CELL_ROWS
         int k = 0;
 #pragma unroll
         for (int r = 0; r < 6; ++r)
@@ -265,21 +268,12 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
             }
             if (failed) break;
             lg = (lg - 1 > -16) ? lg - 1 : -16;
-            double dn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-            double pn = (3.0 - (prev.R[0] + prev.R[4] + prev.R[8]))
-                        + prev.t[0] * prev.t[0] + prev.t[1] * prev.t[1] + prev.t[2] * prev.t[2];
             ++iters;
-            if (iters >= kLmMaxIter || dn < kFltEps * kFltEps * pn) break;
+            if (iters >= XLM_LM_MAX_ITER || lm_step_small(d, &prev)) break;
 #pragma unroll
             for (int k = 0; k < 28; ++k) ne[k] = neNew[k];
         }
-        if (!failed) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) if (!(cur.R[i] == cur.R[i])) failed = true;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) if (!(cur.t[i] == cur.t[i])) failed = true;
-        }
-        if (failed) break;
+        if (failed || !pose_not_nan(&cur)) break;              // the solver's test is x == x: an infinite entry passes
         pose = cur;
         finalInl = cnt;
         inlAcc = inl;
@@ -316,23 +310,9 @@ void xl_dsac_forward_kernel(Params P)
     const int nSub = (PHASE == 1) ? P.S : 1;
     const int N = P.Ho * P.Wo;
 
-    Cam cam;
-    cam.f = (double)(P.focals ? P.focals[b] : P.focal);
-    cam.cx = (double)P.ppx; cam.cy = (double)P.ppy;
-    cam.thr = P.thr; cam.alpha = P.alpha; cam.maxReproj = P.maxReproj;
-    cam.sub = P.sub; cam.Ho = P.Ho; cam.Wo = P.Wo; cam.N = N;
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
 
-    // ---- stage coordinates into LDS planes
-    {
-        const float *g = P.coords + (int64_t)b * P.sb;
-        for (int i = tid; i < N; i += kThreads) {
-            int y = i / P.Wo, x = i - y * P.Wo;
-            const float *q = g + (int64_t)y * P.sy + (int64_t)x * P.sx;
-            sCo[i] = q[0];
-            sCo[P.Npad + i] = q[P.sc];
-            sCo[2 * P.Npad + i] = q[2 * P.sc];
-        }
-    }
+    stage_coords(P.coords + (int64_t)b * P.sb, P.sc, P.sy, P.sx, P.Wo, N, P.Npad, sCo, tid);
     // ---- masked: the mask as a bit plane (each wave ballots 64 consecutive cells into two words), usable cells counted per wave
     uint32_t *sMask = reinterpret_cast<uint32_t *>(sCo + 3 * P.Npad);
     if constexpr (MASKED) {
@@ -371,12 +351,15 @@ void xl_dsac_forward_kernel(Params P)
             if (PHASE != 1 && tid == 0) {
                 float *o = P.outPoses + (int64_t)b * 16;
 #pragma unroll
-                for (int i = 0; i < 16; ++i) o[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+                for (int i = 0; i < 16; ++i) o[i] = (i % 5 == 0) ? 1.0f : 0.0f;     // not pose_to_c2w16 of the identity: its translation column is -0.0f
                 if (P.status) P.status[b] = 1;
                 if (P.dbg) {
                     double *q = P.dbg + (int64_t)b * XL_DSAC_DBG_DOUBLES;
                     q[0] = -1.0; q[1] = 0.0; q[2] = 0.0; q[3] = 0.0;
-                    for (int i = 0; i < 12; ++i) { const double v = (i < 9 && i % 4 == 0) ? 1.0 : 0.0; q[4 + i] = v; q[16 + i] = v; }
+                    Pose id;
+                    pose_identity(&id);
+                    pose_store12(&id, q + 4);
+                    pose_store12(&id, q + 16);
                 }
             }
             return;
@@ -434,9 +417,7 @@ void xl_dsac_forward_kernel(Params P)
             } else {
                 e0 = co.err(pose, i, cam); e1 = co.err(pose, i + 64, cam);
             }
-            double st0 = (double)(beta * (e0 - cam.thr)), st1 = (double)(beta * (e1 - cam.thr));
-            st0 = 1.0 / (1.0 + det_exp(-st0));
-            st1 = 1.0 / (1.0 + det_exp(-st1));
+            const double st0 = soft_inlier_st(e0, cam.thr, beta), st1 = soft_inlier_st(e1, cam.thr, beta);
             if constexpr (MASKED) {
                 acc += mb.usable(i) ? 1.0 - st0 : 0.0;
                 acc += mb.usable(i + 64) ? 1.0 - st1 : 0.0;
@@ -446,10 +427,7 @@ void xl_dsac_forward_kernel(Params P)
             }
         }
         for (; i < N; i += 64) {
-            float e = co.err(pose, i, cam);
-            float stf = beta * (e - cam.thr);
-            double st = (double)stf;
-            st = 1.0 / (1.0 + det_exp(-st));
+            const double st = soft_inlier_st(co.err(pose, i, cam), cam.thr, beta);
             if constexpr (MASKED) acc += mb.usable(i) ? 1.0 - st : 0.0;
             else acc += 1.0 - st;
         }
@@ -463,30 +441,14 @@ void xl_dsac_forward_kernel(Params P)
             }
             if (P.tries) P.tries[(int64_t)b * P.nHyp + h] = triesUsed;
             if (P.scores) P.scores[(int64_t)b * P.nHyp + h] = score;
-            if (P.hypPoses) {
-                double *o = P.hypPoses + ((int64_t)b * P.nHyp + h) * 12;
-#pragma unroll
-                for (int i = 0; i < 9; ++i) o[i] = pose.R[i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) o[9 + i] = pose.t[i];
-            }
+            if (P.hypPoses) pose_store12(&pose, P.hypPoses + ((int64_t)b * P.nHyp + h) * 12);
         }
         if (score != score) anyNan = 1;
         bool better = (bestIdx < 0) || (score > bestScore);
-        if (h == 0 && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) S.pose0[i] = pose.R[i];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) S.pose0[9 + i] = pose.t[i];
-        }
+        if (h == 0 && lane == 0) pose_store12(&pose, S.pose0);
         if (better) {
             bestScore = score; bestIdx = h;
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < 9; ++i) S.bestPose[wave][i] = pose.R[i];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) S.bestPose[wave][9 + i] = pose.t[i];
-            }
+            if (lane == 0) pose_store12(&pose, S.bestPose[wave]);
         }
     }
     if (PHASE == 1) {
@@ -528,16 +490,12 @@ void xl_dsac_forward_kernel(Params P)
         const double *src;
         if (PHASE == 2) src = nanAny ? P.part + (int64_t)gridDim.x * nPart * 16 + (int64_t)b * 12 : gPart + winWave * 16 + 3;
         else src = nanAny ? S.pose0 : S.bestPose[winWave];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pose.R[i] = src[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pose.t[i] = src[9 + i];
+        pose_load12(src, &pose);
     }
     if (tid == 0 && P.dbg) {
         double *o = P.dbg + (int64_t)b * XL_DSAC_DBG_DOUBLES;
         o[0] = (double)win;
-        for (int i = 0; i < 9; ++i) o[4 + i] = pose.R[i];
-        for (int i = 0; i < 3; ++i) o[13 + i] = pose.t[i];
+        pose_store12(&pose, o + 4);
     }
 
     // ---- refine (refineHyp, dsacstar_util.h:522-597)
@@ -549,20 +507,12 @@ void xl_dsac_forward_kernel(Params P)
 
     // ---- write (pose2trans): inverse rigid transform, float row-major
     if (tid == 0) {
-        float *o = P.outPoses + (int64_t)b * 16;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) o[4 * i + j] = (float)pose.R[3 * j + i];
-            o[4 * i + 3] = (float)(-(pose.R[i] * pose.t[0] + pose.R[3 + i] * pose.t[1] + pose.R[6 + i] * pose.t[2]));
-        }
-        o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+        pose_to_c2w16(&pose, P.outPoses + (int64_t)b * 16);
         if constexpr (MASKED) if (P.status) P.status[b] = 0;
         if (P.dbg) {
             double *q = P.dbg + (int64_t)b * XL_DSAC_DBG_DOUBLES;
             q[1] = (double)rounds; q[2] = (double)finalInl; q[3] = (double)evals;
-            for (int i = 0; i < 9; ++i) q[16 + i] = pose.R[i];
-            for (int i = 0; i < 3; ++i) q[25 + i] = pose.t[i];
+            pose_store12(&pose, q + 16);
         }
     }
 }
@@ -588,27 +538,6 @@ struct BwdParams {
     float thr, focal, ppx, ppy, alpha, maxReproj, wRot, wTrans, softClamp;
 };
 
-__device__ __forceinline__ void bwd_cam(const BwdParams &P, int b, Cam &cam)
-{
-    cam.f = (double)(P.focals ? P.focals[b] : P.focal);
-    cam.cx = (double)P.ppx; cam.cy = (double)P.ppy;
-    cam.thr = P.thr; cam.alpha = P.alpha; cam.maxReproj = P.maxReproj;
-    cam.sub = P.sub; cam.Ho = P.Ho; cam.Wo = P.Wo; cam.N = P.Ho * P.Wo;
-}
-
-__device__ __forceinline__ void stage_coords(const BwdParams &P, int b, float *sCo, int tid)
-{
-    const int N = P.Ho * P.Wo;
-    const float *g = P.coords + (int64_t)b * P.sb;
-    for (int i = tid; i < N; i += kThreads) {
-        int y = i / P.Wo, x = i - y * P.Wo;
-        const float *q = g + (int64_t)y * P.sy + (int64_t)x * P.sx;
-        sCo[i] = q[0];
-        sCo[P.Npad + i] = q[P.sc];
-        sCo[2 * P.Npad + i] = q[2 * P.sc];
-    }
-}
-
 // K1 (grid nHyp x B): soft-max probability of the hypothesis, refinement if it matters, loss, path-I quantities
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_hyp_kernel(BwdParams P)
@@ -619,8 +548,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
-    Cam cam;
-    bwd_cam(P, b, cam);
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     const int N = cam.N;
 
     // softMax (dsacstar_util.h:684-704), every thread in the same order
@@ -639,7 +567,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     int redSel = 0, cntSel = 0;
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
     if (active) {
-        stage_coords(P, b, sCo, tid);
+        stage_coords(P.coords + (int64_t)b * P.sb, P.sc, P.sy, P.sx, P.Wo, N, P.Npad, sCo, tid);
         __syncthreads();
         refine_pose(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel);
     }
@@ -670,7 +598,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
                 int y = i / cam.Wo, x = i - y * cam.Wo;
                 double X, Y, Z, J6[6];
                 co.fetch(i, X, Y, Z);
-                resid_row(&pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
+                resid_row(&pose, dRr, X, Y, Z, cell_px(&cam, x), cell_px(&cam, y), &cam, J6);
                 int k = 0;
 #pragma unroll
                 for (int r = 0; r < 6; ++r)
@@ -692,7 +620,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
                 int y = i / cam.Wo, x = i - y * cam.Wo;
                 double X, Y, Z, J6[6];
                 co.fetch(i, X, Y, Z);
-                resid_row(&pose, dRr, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
+                resid_row(&pose, dRr, X, Y, Z, cell_px(&cam, x), cell_px(&cam, y), &cam, J6);
                 for (int r = 0; r < 6; ++r) {
                     double u = 0.0;
                     for (int c = 0; c < 6; ++c) u += Ainv[6 * r + c] * J6[c];
@@ -719,8 +647,7 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     if (tid == 0) {
         rec[0] = prob; rec[1] = loss; rec[2] = active ? 1.0 : 0.0; rec[3] = (double)ro.finalInl; rec[4] = (double)clampI;
         rec[5] = 0.0;
-        for (int i = 0; i < 9; ++i) rec[6 + i] = pose.R[i];
-        for (int i = 0; i < 3; ++i) rec[15 + i] = pose.t[i];
+        pose_store12(&pose, rec + 6);
         for (int i = 0; i < 6; ++i) { rec[18 + i] = dLossH[i]; rec[24 + i] = wv[i]; }
         for (int i = 0; i < 12; ++i) rec[30 + i] = 0.0;
         rec[42] = maxJR; rec[43] = 0.0;
@@ -762,10 +689,9 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
     const int h = blockIdx.x, b = blockIdx.y;
     double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
     if (rec[0] < XLM_PROB_THRESH) return;
-    Cam cam;
-    bwd_cam(P, b, cam);
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     const int N = cam.N;
-    stage_coords(P, b, sCo, tid);
+    stage_coords(P.coords + (int64_t)b * P.sb, P.sc, P.sy, P.sx, P.Wo, N, P.Npad, sCo, tid);
     __syncthreads();
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
     Pose init;
@@ -783,12 +709,10 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
         int y = i / cam.Wo, x = i - y * cam.Wo;
         double X, Y, Z, J6[6];
         co.fetch(i, X, Y, Z);
-        float e = co.err(init, i, y, x, cam);
-        float stf = beta * (e - cam.thr);
-        double st = 1.0 / (1.0 + det_exp(-(double)stf));
+        double st = soft_inlier_st(co.err(init, i, y, x, cam), cam.thr, beta);
         double dRep = -st * (1.0 - st) * (double)beta * sog;
         dRep *= (double)facf;
-        resid_row(&init, dRi, X, Y, Z, (float)(x * cam.sub + cam.sub / 2), (float)(y * cam.sub + cam.sub / 2), &cam, J6);
+        resid_row(&init, dRi, X, Y, Z, cell_px(&cam, x), cell_px(&cam, y), &cam, J6);
 #pragma unroll
         for (int k = 0; k < 6; ++k) a[k] += dRep * J6[k];
     }
@@ -806,8 +730,8 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
             const int ci = cells[q];
             const int y = ci / cam.Wo, x = ci - y * cam.Wo;
             pts[q][0] = sCo[ci]; pts[q][1] = sCo[P.Npad + ci]; pts[q][2] = sCo[2 * P.Npad + ci];
-            uv[q][0] = (double)(float)(x * cam.sub + cam.sub / 2);
-            uv[q][1] = (double)(float)(y * cam.sub + cam.sub / 2);
+            uv[q][0] = (double)cell_px(&cam, x);
+            uv[q][1] = (double)cell_px(&cam, y);
         }
         const int col = tid >> 1, back = tid & 1;
         for (int c = 0; c <= col; ++c) {
@@ -864,13 +788,12 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
 {
     const int b = blockIdx.y;
     const int i = blockIdx.x * kThreads + threadIdx.x;
-    Cam cam;
-    bwd_cam(P, b, cam);
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     if (i >= cam.N) return;
     const int y = i / cam.Wo, x = i - y * cam.Wo;
     const float *q = P.coords + (int64_t)b * P.sb + (int64_t)y * P.sy + (int64_t)x * P.sx;
     const double X = (double)q[0], Y = (double)q[P.sc], Z = (double)q[2 * P.sc];
-    const float px = (float)(x * cam.sub + cam.sub / 2), py = (float)(y * cam.sub + cam.sub / 2);
+    const float px = cell_px(&cam, x), py = cell_px(&cam, y);
     float *g = P.grad + (int64_t)b * P.gsb + (int64_t)y * P.gsy + (int64_t)x * P.gsx;
     float acc[3] = { g[0], g[P.gsc], g[2 * P.gsc] };
     const float beta = 5.0f / cam.thr;
@@ -894,9 +817,7 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
             dproject_dobj(&ref, X, Y, Z, px, py, &cam, dNdO);
             for (int k = 0; k < 3; ++k) gI[k] = s * dNdO[k];
         }
-        float e = cell_err(&init, X, Y, Z, y, x, &cam);            // clamped float error under the unrefined hypothesis
-        float stf = beta * (e - cam.thr);
-        double st = 1.0 / (1.0 + det_exp(-(double)stf));
+        double st = soft_inlier_st(cell_err(&init, X, Y, Z, y, x, &cam), cam.thr, beta);   // at the clamped float error under the unrefined hypothesis
         double dRep = -st * (1.0 - st) * (double)beta * rec[5];
         dRep *= (double)facf;
         double dPdO[3];

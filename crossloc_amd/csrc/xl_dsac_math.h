@@ -2,14 +2,18 @@
  * xl_dsac_math.h — the lane-local arithmetic of the DSAC* pose solver, written once.
  *
  * Everything one GPU lane (or one iteration of a CPU loop) computes on its own is here: the deterministic
- * transcendentals, the counter-based RNG, projection and cell error, the Ferrari quartic, P3P with its Newton polish and
- * 4th-point selection, the 6x6 Cholesky step of the Levenberg-Marquardt refinement, and the backward pass's Rodrigues
- * maps, residual rows, pseudo-inverse and pose loss.  Two consumers include it:
+ * transcendentals, the counter-based RNG, the camera record and the pixel centre of a cell (cam_make, cell_px), projection,
+ * cell error and the soft-inlier sigmoid, the Ferrari quartic, P3P with its Newton polish and 4th-point selection, the
+ * pieces of the Levenberg-Marquardt refinement (the per-cell normal equations, plain and weighted, the 6x6 Cholesky step,
+ * the step-size stop and its constants, the not-NaN test of the result), the pose forms (12 doubles, float 4x4
+ * cam->world), and the backward pass's Rodrigues maps, residual rows, pseudo-inverse and pose loss.  Consumers:
  *
  *   crossloc_amd/csrc/xl_dsac.hip   the product: HIP kernels (staging, ballots, wave / block reductions, the LM state machine)
- *   oracle/dsac_oracle.c            test infrastructure: the same orchestration restated serially in C99 for gcc
+ *   xl_dsac_quality_math.h, xl_dsac_refine_math.h and the RGB-D headers, which add their own passes' arithmetic on top
+ *   oracle/dsac_oracle.c, tests/dsac_masked_ref.c and the other CPU restatements: test infrastructure, the same
+ *                                   orchestration restated serially in C99 for gcc
  *
- * The dependency runs from the oracle to this header only; nothing in the product path includes the oracle.
+ * The dependency runs from the restatements to the headers only; nothing in the product path includes the oracle.
  *
  * Language: the common subset of C99 and HIP C++ (structs, pointers for out-parameters; no references, templates or
  * member functions).  hipcc includes it inside the consumer's namespace after <hip/hip_runtime.h>, <stdint.h> and
@@ -46,12 +50,28 @@
 #define XLM_PI_REF 3.1415926           /* dsacstar_util.h:46 (calcAngularDistance) */
 #define XLM_CV_PI 3.1415926535897932384626433832795
 #define XLM_DBL_EPS 2.2204460492503131e-16
+#define XLM_LM_MAX_ITER 20             /* cv::solvePnP ITERATIVE term criteria: iteration cap of every LM loop here ... */
+#define XLM_FLT_EPS 1.1920928955078125e-07     /* ... and its epsilon (FLT_EPSILON), see lm_step_small */
 
 typedef struct { double R[9]; double t[3]; } Pose;                   /* world -> camera */
 typedef struct { double f, cx, cy; float thr, alpha, maxReproj; int sub, Ho, Wo, N; } Cam;
 typedef struct { double x, y, z; } V3;
 typedef struct { V3 e1, e2, e3; } Frame;
 typedef struct { double Rc2w[9]; double C[3]; double R2[9]; double t2[3]; } Gt;   /* ground truth, both forms */
+
+/* the one constructor of Cam.  The intrinsics arrive as the entry points' floats (widened exactly; a kernel passes
+ * focals ? focals[b] : focal) or as the unit-test hooks' doubles */
+XL_MATH_FN Cam cam_make(int Ho, int Wo, float thr, double f, double cx, double cy, float alpha, float maxReproj, int sub)
+{
+    Cam cam;
+    cam.f = f; cam.cx = cx; cam.cy = cy;
+    cam.thr = thr; cam.alpha = alpha; cam.maxReproj = maxReproj;
+    cam.sub = sub; cam.Ho = Ho; cam.Wo = Wo; cam.N = Ho * Wo;
+    return cam;
+}
+
+/* pixel centre of column (or row) i of the cell grid (createSampling, dsacstar_util.h:70-72) */
+XL_MATH_FN float cell_px(const Cam *cam, int i) { return (float)(i * cam->sub + cam->sub / 2); }
 
 /* ------------------------------------------------------------------------------ deterministic math */
 
@@ -176,17 +196,24 @@ XL_MATH_FN void project(const Pose *p, double X, double Y, double Z, const Cam *
     *v = (float)(y * cam->f + cam->cy);
 }
 
-/* reprojection error of the scene coordinate (X, Y, Z) of cell (y, x) against the cell's pixel centre
- * (createSampling, dsacstar_util.h:70-72), clamped: std::min(err, maxReproj) (dsacstar_util.h:438-443) */
+/* reprojection error of the scene coordinate (X, Y, Z) of cell (y, x) against the cell's pixel centre, clamped:
+ * std::min(err, maxReproj) (dsacstar_util.h:438-443) */
 XL_MATH_FN float cell_err(const Pose *p, double X, double Y, double Z, int y, int x, const Cam *cam)
 {
     float u, v;
     project(p, X, Y, Z, cam, &u, &v);
-    float px = (float)(x * cam->sub + cam->sub / 2), py = (float)(y * cam->sub + cam->sub / 2);
-    float dx = px - u, dy = py - v;
+    float dx = cell_px(cam, x) - u, dy = cell_px(cam, y) - v;
     double n = sqrt((double)dx * (double)dx + (double)dy * (double)dy);
     float a = (float)n;
     return (cam->maxReproj < a) ? cam->maxReproj : a;
+}
+
+/* soft-inlier sigmoid of a cell with clamped error e (getHypScores, dsacstar_util.h:316-343; beta = 5 / thr): the score
+ * term of the cell is 1.0 - st, the backward pass's derivative uses st * (1.0 - st) */
+XL_MATH_FN double soft_inlier_st(float e, float thr, float beta)
+{
+    float stf = beta * (e - thr);
+    return 1.0 / (1.0 + det_exp(-(double)stf));
 }
 
 /* ------------------------------------------------------------------------------ quartic (Ferrari) */
@@ -437,6 +464,88 @@ XL_MATH_FN void pose_to_c2w16(const Pose *p, float *o)
         o[4 * i + 3] = (float)(-(p->R[i] * p->t[0] + p->R[3 + i] * p->t[1] + p->R[6 + i] * p->t[2]));
     }
     o[12] = 0.0f; o[13] = 0.0f; o[14] = 0.0f; o[15] = 1.0f;
+}
+
+/* no entry of the pose is NaN: the test the solver makes on an LM result (x == x; an infinite entry passes.  The
+ * stand-alone passes ask for finite entries instead: quality_pose_finite) */
+XL_MATH_FN bool pose_not_nan(const Pose *p)
+{
+    bool ok = true;
+    XL_MATH_UNROLL
+    for (int i = 0; i < 9; ++i) if (!(p->R[i] == p->R[i])) ok = false;
+    XL_MATH_UNROLL
+    for (int i = 0; i < 3; ++i) if (!(p->t[i] == p->t[i])) ok = false;
+    return ok;
+}
+
+/* the per-cell PnP rows at pose p for the cell (y, x) with scene coordinate (X, Y, Z): the residual (ru, rv) of the double
+ * projection against the pixel centre and its Jacobian rows Ju, Jv w.r.t. the increment (w, d) of apply_step.  The one
+ * statement of these formulas: the solver's refinement, the pose-quality pass, the weighted refinement and their CPU
+ * restatements all accumulate it through one of the two functions below; the only other expansion is the solver kernel's
+ * normal_eq_thread (xl_dsac.hip), for the reason given there.
+ * A macro over the names p, X, Y, Z, y, x, cam of the expanding function, not a function: with the rows behind a
+ * force-inlined function (out-pointers or a struct by value alike) hipcc schedules the cell loops differently at equal
+ * register figures - measured on MI355X against the hand-written loops, same session: the weighted refinement alone
+ * 0.548 against 0.525 ms per 95 frames (+4 %), the solver's single-frame call 0.2564 against 0.2541 ms (+0.8 %).  As text
+ * the consumers compile to the instructions of the hand-written loops (tools/kernel_asm_diff.py). */
+#define XL_PNP_CELL_ROWS \
+    double Ju[6], Jv[6], ru, rv; \
+    { \
+        double qx = p->R[0] * X + p->R[1] * Y + p->R[2] * Z; \
+        double qy = p->R[3] * X + p->R[4] * Y + p->R[5] * Z; \
+        double qz = p->R[6] * X + p->R[7] * Y + p->R[8] * Z; \
+        double xc = qx + p->t[0], yc = qy + p->t[1], zc = qz + p->t[2]; \
+        double z = (zc != 0.0) ? 1.0 / zc : 1.0; \
+        double xn = xc * z, yn = yc * z; \
+        ru = (xn * cam->f + cam->cx) - (double)cell_px(cam, x); \
+        rv = (yn * cam->f + cam->cy) - (double)cell_px(cam, y); \
+        double fa = cam->f * z;             /* du/dXc = dv/dYc */ \
+        double fc = -(fa * xn);             /* du/dZc */ \
+        double fd = -(fa * yn);             /* dv/dZc */ \
+        Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy); \
+        Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc; \
+        Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx; \
+        Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd; \
+    }
+
+/* what the cell adds to the 28 normal-equation sums: a[0..20] += upper triangle of Ju Ju^T + Jv Jv^T (row-major),
+ * a[21..26] += J^T r, a[27] += ru^2 + rv^2 */
+XL_MATH_FN void pnp_cell_normal_eq(const Pose *p, double X, double Y, double Z, int y, int x, const Cam *cam, double *a)
+{
+    XL_PNP_CELL_ROWS
+    int k = 0;
+    XL_MATH_UNROLL
+    for (int r = 0; r < 6; ++r)
+        XL_MATH_UNROLL
+        for (int c = r; c < 6; ++c) { a[k] += Ju[r] * Ju[c] + Jv[r] * Jv[c]; ++k; }
+    XL_MATH_UNROLL
+    for (int r = 0; r < 6; ++r) a[21 + r] += Ju[r] * ru + Jv[r] * rv;
+    a[27] += ru * ru + rv * rv;
+}
+
+/* the same with the cell's contribution to each sum multiplied by w.  An accumulator of its own: the solver does not pay
+ * for the multiplications, and since the PRODUCTS are multiplied, not the rows, w == 1.0 gives the unweighted bits */
+XL_MATH_FN void pnp_cell_normal_eq_w(const Pose *p, double X, double Y, double Z, double w, int y, int x, const Cam *cam,
+                                     double *a)
+{
+    XL_PNP_CELL_ROWS
+    int k = 0;
+    XL_MATH_UNROLL
+    for (int r = 0; r < 6; ++r)
+        XL_MATH_UNROLL
+        for (int c = r; c < 6; ++c) { a[k] += w * (Ju[r] * Ju[c] + Jv[r] * Jv[c]); ++k; }
+    XL_MATH_UNROLL
+    for (int r = 0; r < 6; ++r) a[21 + r] += w * (Ju[r] * ru + Jv[r] * rv);
+    a[27] += w * (ru * ru + rv * rv);
+}
+
+/* the step-size stop of every Levenberg-Marquardt loop here: |d|^2 < FLT_EPSILON^2 |param|^2 */
+XL_MATH_FN bool lm_step_small(const double *d, const Pose *prev)
+{
+    double dn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
+    double pn = (3.0 - (prev->R[0] + prev->R[4] + prev->R[8]))
+                + prev->t[0] * prev->t[0] + prev->t[1] * prev->t[1] + prev->t[2] * prev->t[2];
+    return dn < XLM_FLT_EPS * XLM_FLT_EPS * pn;
 }
 
 /* solve (JtJ with diag*(1+lambda)) d = Jtr by Cholesky; false on breakdown */

@@ -50,11 +50,7 @@ void xl_dsac_quality_kernel(QualityParams P)
     const int b = blockIdx.x;
     const int N = P.Ho * P.Wo;
 
-    Cam cam;
-    cam.f = (double)(P.focals ? P.focals[b] : P.focal);
-    cam.cx = (double)P.ppx; cam.cy = (double)P.ppy;
-    cam.thr = P.thr; cam.alpha = P.alpha; cam.maxReproj = P.maxReproj;
-    cam.sub = P.sub; cam.Ho = P.Ho; cam.Wo = P.Wo; cam.N = N;
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
 
     // every thread derives the pose itself (uniform over the workgroup, no broadcast), like the backward pass does
     float p16[16];

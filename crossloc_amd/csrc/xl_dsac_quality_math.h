@@ -4,7 +4,9 @@
  * The pass looks at ONE pose per image (usually the one the solver returned) and reports how far it can be trusted: the
  * inlier statistics at that pose, JtJ of the reprojection residuals over the inliers, and the covariance that follows
  * from it.  Same conventions as xl_dsac_math.h, which this header includes: the common subset of C99 and HIP C++, only
- * + - * / sqrt and comparisons, compiled with -ffp-contract=off on both sides.  Two consumers:
+ * + - * / sqrt and comparisons, compiled with -ffp-contract=off on both sides.  What a cell adds to the sums is the solver's
+ * own arithmetic and lives there (cell_err, soft_inlier_st, pnp_cell_normal_eq, cam_make); this header keeps what only the
+ * quality passes need: the finiteness tests, the 6x6 inverse, the covariance and the row.  Two consumers:
  *
  *   crossloc_amd/csrc/xl_dsac_quality.hip   the product: one 256-thread workgroup per image, the canonical block reduction
  *   tests/pose_quality_ref.c                test infrastructure: the same orchestration restated serially in C99 for gcc
@@ -59,51 +61,22 @@ XL_MATH_CALL_FN void quality_pose_from16(const float *p16, Pose *p)
     for (int i = 0; i < 3; ++i) p->t[i] = g.t2[i];
 }
 
-/* contribution of the cell (y, x) with scene coordinate (X, Y, Z) to the 28 normal-equation sums at pose p:
- * a[0..20] += upper triangle of Ju Ju^T + Jv Jv^T (row-major), a[21..26] += J^T r, a[27] += ru^2 + rv^2.
- * Operation for operation what the refinement accumulates per inlier (normal_eq_thread in xl_dsac.hip). */
+/* the pass's earlier name for the solver's per-cell normal equations, kept for restatements and hooks written against it:
+ * a one-line forward to pnp_cell_normal_eq of xl_dsac_math.h.  quality_cell calls the target itself: through one more
+ * force-inlined layer hipcc orders the kernel's cell loop differently (tools/kernel_asm_diff.py) */
 XL_MATH_FN void quality_cell_normal_eq(const Pose *p, double X, double Y, double Z, int y, int x, const Cam *cam, double *a)
 {
-    double qx = p->R[0] * X + p->R[1] * Y + p->R[2] * Z;
-    double qy = p->R[3] * X + p->R[4] * Y + p->R[5] * Z;
-    double qz = p->R[6] * X + p->R[7] * Y + p->R[8] * Z;
-    double xc = qx + p->t[0], yc = qy + p->t[1], zc = qz + p->t[2];
-    double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-    double xn = xc * z, yn = yc * z;
-    double ru = (xn * cam->f + cam->cx) - (double)(float)(x * cam->sub + cam->sub / 2);
-    double rv = (yn * cam->f + cam->cy) - (double)(float)(y * cam->sub + cam->sub / 2);
-    double fa = cam->f * z;             /* du/dXc = dv/dYc */
-    double fc = -(fa * xn);             /* du/dZc */
-    double fd = -(fa * yn);             /* dv/dZc */
-    double Ju[6], Jv[6];
-    Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy);
-    Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc;
-    Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx;
-    Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd;
-    int k = 0;
-    XL_MATH_UNROLL
-    for (int r = 0; r < 6; ++r)
-        XL_MATH_UNROLL
-        for (int c = r; c < 6; ++c) { a[k] += Ju[r] * Ju[c] + Jv[r] * Jv[c]; ++k; }
-    XL_MATH_UNROLL
-    for (int r = 0; r < 6; ++r) a[21 + r] += Ju[r] * ru + Jv[r] * rv;
-    a[27] += ru * ru + rv * rv;
+    pnp_cell_normal_eq(p, X, Y, Z, y, x, cam, a);
 }
 
-/* soft-inlier term of a cell with clamped error e, as the scoring loop of the solver forms it (beta = 5 / thr) */
-XL_MATH_FN double quality_soft_inlier(float e, float thr, float beta)
-{
-    float stf = beta * (e - thr);
-    return 1.0 - 1.0 / (1.0 + det_exp(-(double)stf));
-}
-
-/* everything one cell adds to the 32 per-thread partials */
+/* everything one cell adds to the 32 per-thread partials: the solver's soft-inlier term (soft_inlier_st) over all cells,
+ * and for an inlier the solver's 28 normal-equation sums (pnp_cell_normal_eq), both of xl_dsac_math.h */
 XL_MATH_FN void quality_cell(const Pose *p, double X, double Y, double Z, int y, int x, const Cam *cam, float beta, double *a)
 {
     float e = cell_err(p, X, Y, Z, y, x, cam);
-    a[XLQ_S_SOFT] += quality_soft_inlier(e, cam->thr, beta);
+    a[XLQ_S_SOFT] += 1.0 - soft_inlier_st(e, cam->thr, beta);
     if (e < cam->thr) {                                  /* the float comparison the refinement makes */
-        quality_cell_normal_eq(p, X, Y, Z, y, x, cam, a);
+        pnp_cell_normal_eq(p, X, Y, Z, y, x, cam, a);
         a[XLQ_S_COUNT] += 1.0;
         a[XLQ_S_ERR] += (double)e;
         a[XLQ_S_ERR2] += (double)e * (double)e;

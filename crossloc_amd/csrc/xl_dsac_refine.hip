@@ -90,11 +90,7 @@ void xl_dsac_refine_kernel(RefineParams P)
     const bool hasSigma = P.sigma != nullptr;
     const double s0sq = (double)P.s0 * (double)P.s0;
 
-    Cam cam;
-    cam.f = (double)(P.focals ? P.focals[b] : P.focal);
-    cam.cx = (double)P.ppx; cam.cy = (double)P.ppy;
-    cam.thr = P.thr; cam.alpha = 0.0f; cam.maxReproj = P.maxReproj;
-    cam.sub = P.sub; cam.Ho = P.Ho; cam.Wo = P.Wo; cam.N = N;
+    const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, 0.0f, P.maxReproj, P.sub);
 
     // every thread derives the pose itself (uniform over the workgroup, no broadcast)
     float p16[16];
@@ -167,7 +163,7 @@ void xl_dsac_refine_kernel(RefineParams P)
             int lg = -3;
             double inv[36];
             bool failed = !quality_inv6(ne, inv);           // J^T W J at the round's pose must be positive definite
-            for (int it = 0; !failed && it < XLR_LM_MAX_ITER; ++it) {
+            for (int it = 0; !failed && it < XLM_LM_MAX_ITER; ++it) {
                 double d[6];
                 prev = cur;
                 if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
@@ -185,7 +181,7 @@ void xl_dsac_refine_kernel(RefineParams P)
                 }
                 if (failed) break;
                 lg = (lg - 1 > -16) ? lg - 1 : -16;
-                if (refine_step_small(d, &prev)) break;
+                if (lm_step_small(d, &prev)) break;
 #pragma unroll
                 for (int k = 0; k < 28; ++k) ne[k] = neNew[k];
             }

@@ -6,7 +6,9 @@
  * equations with the weight w_i = 1 / (s0^2 + (f sigma_i / z_i)^2) - the inverse variance in pixels^2 of its reprojection
  * residual under an isotropic 3-D Gaussian of that sigma at camera depth z_i, floored by the pixel noise s0.  Same conventions
  * as xl_dsac_math.h and xl_dsac_quality_math.h, on which this header sits: the common subset of C99 and HIP C++, only
- * + - * / sqrt and comparisons, compiled with -ffp-contract=off on both sides.  Two consumers:
+ * + - * / sqrt and comparisons, compiled with -ffp-contract=off on both sides.  The weighted per-cell normal equations
+ * (pnp_cell_normal_eq_w), the step-size stop (lm_step_small) and the LM constants are the solver's, in xl_dsac_math.h; this
+ * header keeps the weight, the row and what the rounds report.  Two consumers:
  *
  *   crossloc_amd/csrc/xl_dsac_refine.hip   the product: one 256-thread workgroup per image, the canonical block reduction
  *   tests/pose_refine_ref.c                test infrastructure: the same orchestration restated serially in C99 for gcc
@@ -24,9 +26,7 @@
 
 #define XLR_ROW 64                     /* doubles per output row */
 #define XLR_MAX_ROUNDS 16              /* upper limit of the max_rounds argument */
-#define XLR_LM_MAX_ITER 20             /* LM iterations per round: the solver's cap (cv::solvePnP ITERATIVE) */
 #define XLR_LG_RAISES 34               /* damping raises per iteration: lg climbs from >= -16 to 17 at most */
-#define XLR_FLT_EPS 1.1920928955078125e-07
 #define XLR_STATUS_OK 0.0
 #define XLR_STATUS_FEW_INLIERS 1.0     /* fewer than 4 inliers at the input pose */
 #define XLR_STATUS_FIRST_ROUND 2.0     /* the first round failed: not positive definite / LM breakdown / pose not finite */
@@ -36,7 +36,7 @@
 XL_MATH_FN bool refine_sigma_bad(double sigma) { return !quality_finite(sigma) || sigma < 0.0; }
 
 /* weight of a cell with scene coordinate (X, Y, Z) and standard deviation sigma at the round's pose pk; s0sq = s0 * s0.
- * The inverse depth is formed as quality_cell_normal_eq forms it (z == 0 is read as 1).  sigma == 0 with s0 == 1 gives
+ * The inverse depth is formed as XL_PNP_CELL_ROWS forms it (z == 0 is read as 1).  sigma == 0 with s0 == 1 gives
  * exactly 1.0. */
 XL_MATH_FN double refine_weight(const Pose *pk, double X, double Y, double Z, double sigma, double s0sq, const Cam *cam)
 {
@@ -47,36 +47,16 @@ XL_MATH_FN double refine_weight(const Pose *pk, double X, double Y, double Z, do
     return 1.0 / (s0sq + g * g);
 }
 
-/* quality_cell_normal_eq with the cell's contribution to each of the 28 sums multiplied by w.  The PRODUCTS are multiplied,
- * not the Jacobian rows: w == 1.0 reproduces the unweighted sums bit for bit. */
+/* the weighted per-cell normal equations, the step-size stop and the iteration cap under the names this pass had for them,
+ * kept for restatements and hooks written against those: one-line forwards to xl_dsac_math.h (pnp_cell_normal_eq_w,
+ * lm_step_small, XLM_LM_MAX_ITER), which the kernels and refine_cell use directly */
+#define XLR_LM_MAX_ITER XLM_LM_MAX_ITER
 XL_MATH_FN void refine_cell_normal_eq(const Pose *p, double X, double Y, double Z, double w, int y, int x, const Cam *cam,
                                       double *a)
 {
-    double qx = p->R[0] * X + p->R[1] * Y + p->R[2] * Z;
-    double qy = p->R[3] * X + p->R[4] * Y + p->R[5] * Z;
-    double qz = p->R[6] * X + p->R[7] * Y + p->R[8] * Z;
-    double xc = qx + p->t[0], yc = qy + p->t[1], zc = qz + p->t[2];
-    double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-    double xn = xc * z, yn = yc * z;
-    double ru = (xn * cam->f + cam->cx) - (double)(float)(x * cam->sub + cam->sub / 2);
-    double rv = (yn * cam->f + cam->cy) - (double)(float)(y * cam->sub + cam->sub / 2);
-    double fa = cam->f * z;             /* du/dXc = dv/dYc */
-    double fc = -(fa * xn);             /* du/dZc */
-    double fd = -(fa * yn);             /* dv/dZc */
-    double Ju[6], Jv[6];
-    Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy);
-    Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc;
-    Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx;
-    Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd;
-    int k = 0;
-    XL_MATH_UNROLL
-    for (int r = 0; r < 6; ++r)
-        XL_MATH_UNROLL
-        for (int c = r; c < 6; ++c) { a[k] += w * (Ju[r] * Ju[c] + Jv[r] * Jv[c]); ++k; }
-    XL_MATH_UNROLL
-    for (int r = 0; r < 6; ++r) a[21 + r] += w * (Ju[r] * ru + Jv[r] * rv);
-    a[27] += w * (ru * ru + rv * rv);
+    pnp_cell_normal_eq_w(p, X, Y, Z, w, y, x, cam, a);
 }
+XL_MATH_FN bool refine_step_small(const double *d, const Pose *prev) { return lm_step_small(d, prev); }
 
 /* everything an inlier cell adds to a thread's 28 partials in one evaluation: the weight from the round's pose pk (1.0 without
  * a sigma map), the normal equations at the moving pose p */
@@ -84,16 +64,7 @@ XL_MATH_FN void refine_cell(const Pose *pk, const Pose *p, double X, double Y, d
                             int y, int x, const Cam *cam, double *a)
 {
     double w = hasSigma ? refine_weight(pk, X, Y, Z, sigma, s0sq, cam) : 1.0;
-    refine_cell_normal_eq(p, X, Y, Z, w, y, x, cam, a);
-}
-
-/* the step-size stop of the solver's Levenberg-Marquardt loop: |d|^2 < FLT_EPSILON^2 |param|^2 */
-XL_MATH_FN bool refine_step_small(const double *d, const Pose *prev)
-{
-    double dn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-    double pn = (3.0 - (prev->R[0] + prev->R[4] + prev->R[8]))
-                + prev->t[0] * prev->t[0] + prev->t[1] * prev->t[1] + prev->t[2] * prev->t[2];
-    return dn < XLR_FLT_EPS * XLR_FLT_EPS * pn;
+    pnp_cell_normal_eq_w(p, X, Y, Z, w, y, x, cam, a);
 }
 
 /* [61], [62] of the row: the angle of Rout Rin^T in degrees and the distance of the two camera centres C = -R^T t */

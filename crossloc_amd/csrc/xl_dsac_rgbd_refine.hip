@@ -147,7 +147,7 @@ void xl_dsac_rgbd_refine_kernel(RgbdRefineParams P)
             }
             int lg = -3;
             bool failed = !rgbdr_well_posed(ne);            // J^T W J at the round's pose must have a sound Cholesky factor
-            for (int it = 0; !failed && it < XLR_LM_MAX_ITER; ++it) {
+            for (int it = 0; !failed && it < XLM_LM_MAX_ITER; ++it) {
                 double d[6];
                 prev = cur;
                 if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
@@ -165,7 +165,7 @@ void xl_dsac_rgbd_refine_kernel(RgbdRefineParams P)
                 }
                 if (failed) break;
                 lg = (lg - 1 > -16) ? lg - 1 : -16;
-                if (refine_step_small(d, &prev)) break;
+                if (lm_step_small(d, &prev)) break;
 #pragma unroll
                 for (int k = 0; k < 28; ++k) ne[k] = neNew[k];
             }

@@ -153,8 +153,8 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
                         int y = i / Wo, x = i - y * Wo;
                         double X[3], J6[6];
                         xo_fetch(&co, x, y, X);
-                        resid_row(&ref[h], dRref + (size_t)h * 27, X[0], X[1], X[2], (float)(x * sub + sub / 2),
-                                  (float)(y * sub + sub / 2), &cam, J6);
+                        resid_row(&ref[h], dRref + (size_t)h * 27, X[0], X[1], X[2], cell_px(&cam, x), cell_px(&cam, y),
+                                  &cam, J6);
                         int k = 0;
                         for (int r = 0; r < 6; ++r)
                             for (int c = r; c < 6; ++c) a[k++] += J6[r] * J6[c];
@@ -174,8 +174,8 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
                     int y = i / Wo, x = i - y * Wo;
                     double X[3], J6[6];
                     xo_fetch(&co, x, y, X);
-                    resid_row(&ref[h], dRref + (size_t)h * 27, X[0], X[1], X[2], (float)(x * sub + sub / 2),
-                              (float)(y * sub + sub / 2), &cam, J6);
+                    resid_row(&ref[h], dRref + (size_t)h * 27, X[0], X[1], X[2], cell_px(&cam, x), cell_px(&cam, y),
+                              &cam, J6);
                     for (int r = 0; r < 6; ++r) {
                         double u = 0.0;
                         for (int c = 0; c < 6; ++c) u += Ainv[6 * r + c] * J6[c];
@@ -194,8 +194,7 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
         if (recs) {
             double *q = recs + (size_t)h * XO_BWD_REC;
             q[0] = probs[h]; q[1] = losses[h]; q[2] = (double)active; q[3] = (double)nAcc[h]; q[4] = (double)clampI[h];
-            for (int i = 0; i < 9; ++i) q[6 + i] = ref[h].R[i];
-            for (int i = 0; i < 3; ++i) q[15 + i] = ref[h].t[i];
+            pose_store12(&ref[h], q + 6);
             for (int i = 0; i < 6; ++i) { q[18 + i] = dLossH[i]; q[24 + i] = wv[(size_t)h * 6 + i]; }
             q[42] = maxJR;
             for (int i = 0; i < 3; ++i) q[50 + i] = rv[i];
@@ -227,10 +226,8 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
                 int y = i / Wo, x = i - y * Wo;
                 double X[3], J6[6];
                 xo_fetch(&co, x, y, X);
-                float px = (float)(x * sub + sub / 2), py = (float)(y * sub + sub / 2);
-                float e = cell_err(&init[h], X[0], X[1], X[2], y, x, &cam);
-                float stf = beta * (e - thr);
-                double st = 1.0 / (1.0 + det_exp(-(double)stf));
+                float px = cell_px(&cam, x), py = cell_px(&cam, y);
+                double st = soft_inlier_st(cell_err(&init[h], X[0], X[1], X[2], y, x, &cam), thr, beta);
                 double dRep = -st * (1.0 - st) * (double)beta * sog[h];
                 dRep *= (double)facf;
                 resid_row(&init[h], dRinit + (size_t)h * 27, X[0], X[1], X[2], px, py, &cam, J6);
@@ -248,8 +245,8 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
             int y = cidx / Wo, x = cidx - y * Wo;
             const float *p = co.base + (int64_t)y * co.sy + (int64_t)x * co.sx;
             obj[j][0] = p[0]; obj[j][1] = p[co.sc]; obj[j][2] = p[2 * co.sc];
-            uv[j][0] = (double)(float)(x * sub + sub / 2);
-            uv[j][1] = (double)(float)(y * sub + sub / 2);
+            uv[j][0] = (double)cell_px(&cam, x);
+            uv[j][1] = (double)cell_px(&cam, y);
         }
         double J[72], maxH = 0.0;
         xo_dpnp(obj, uv, &cam, J);
@@ -274,7 +271,7 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
         int y = i / Wo, x = i - y * Wo;
         double X[3];
         xo_fetch(&co, x, y, X);
-        float px = (float)(x * sub + sub / 2), py = (float)(y * sub + sub / 2);
+        float px = cell_px(&cam, x), py = cell_px(&cam, y);
         float *g = grad + (int64_t)y * gsy + (int64_t)x * gsx;
         float acc[3] = { g[0], g[gsc], g[2 * gsc] };
         for (int h = 0; h < nHyp; ++h) {
@@ -289,9 +286,7 @@ int xo_dsac_backward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx
                 dproject_dobj(&ref[h], X[0], X[1], X[2], px, py, &cam, dNdO);
                 for (int k = 0; k < 3; ++k) gI[k] = s * dNdO[k];
             }
-            float e = cell_err(&init[h], X[0], X[1], X[2], y, x, &cam);
-            float stf = beta * (e - thr);
-            double st = 1.0 / (1.0 + det_exp(-(double)stf));
+            double st = soft_inlier_st(cell_err(&init[h], X[0], X[1], X[2], y, x, &cam), thr, beta);
             double dRep = -st * (1.0 - st) * (double)beta * sog[h];
             dRep *= (double)facf;
             double dPdO[3];

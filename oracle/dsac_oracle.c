@@ -5,9 +5,11 @@
  * may include, link or call this file; only tests/, __graft_entry__.smoke() and
  * bench.py's cpu_baseline leg use it, as the checker / reported CPU baseline.
  *
- * The dependency runs the other way, and only to one file: the lane-local arithmetic (deterministic exp / sincos / atan2,
- * RNG, projection and cell error, quartic, P3P, Cholesky step, the backward pass's derivatives) is the product's
- * crossloc_amd/csrc/xl_dsac_math.h, compiled here by gcc as C99.  This file restates serially what the kernels do in
+ * The dependency runs the other way, and only to the product's headers: the lane-local arithmetic (deterministic exp /
+ * sincos / atan2, RNG, the camera record, projection, cell error and the soft-inlier sigmoid, quartic, P3P, the per-cell
+ * normal equations, Cholesky step, the LM stop rule and its constants, the float 4x4 write, the backward pass's
+ * derivatives) is the product's crossloc_amd/csrc/xl_dsac_math.h, compiled here by gcc as C99; the round limit is the public
+ * header's.  This file restates serially what the kernels do in
  * parallel around it: the try loop (first accepted try), the lane-strided partial sums and the xor-butterfly, the
  * 256-thread reduction of the normal equations (block_sum of xl_dsac_reduce.h, where the order is stated), the LM state machine, refinement, both drivers.  So bitwise GPU == oracle
  * checks that orchestration and that gcc and hipcc agree on the same IEEE operations; it does NOT check the shared
@@ -65,10 +67,7 @@
 
 #include "xl_dsac_math.h"             /* crossloc_amd/csrc: the lane-local arithmetic, shared with the kernels */
 #include "xl_dsac_reduce.h"           /* the canonical block sum and its order (plain-C half) */
-
-#define XO_MAX_REF_STEPS 100          /* dsacstar.cpp:47 */
-#define XO_LM_MAX_ITER 20             /* cv::solvePnP ITERATIVE term criteria */
-#define XO_FLT_EPSILON 1.1920928955078125e-07
+#include "../../include/crossloc_dsac.h"      /* beside crossloc_amd/csrc, as the kernels include it: XL_DSAC_MAX_REF_STEPS */
 
 /* ------------------------------------------------------------------ small helpers */
 
@@ -87,19 +86,13 @@ static void xo_fetch(const xo_coords *c, int x, int y, double X[3])
 
 static Cam xo_cam(int Ho, int Wo, float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub)
 {
-    Cam cam;
-    cam.f = (double)focal; cam.cx = (double)ppx; cam.cy = (double)ppy;
-    cam.thr = thr; cam.alpha = alpha; cam.maxReproj = maxReproj;
-    cam.sub = sub; cam.Ho = Ho; cam.Wo = Wo; cam.N = Ho * Wo;
-    return cam;
+    return cam_make(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
 }
 
 /* the unit-test hooks pass the intrinsics as doubles and no grid */
 static Cam xo_test_cam(double f, double cx, double cy, float maxReproj)
 {
-    Cam cam = xo_cam(0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, maxReproj, 0);
-    cam.f = f; cam.cx = cx; cam.cy = cy;
-    return cam;
+    return cam_make(0, 0, 0.0f, f, cx, cy, 0.0f, maxReproj, 0);
 }
 
 /* clamped reprojection error of cell i */
@@ -127,8 +120,8 @@ static bool xo_sample_try(const xo_coords *co, const Cam *cam, uint64_t imageKey
         int y = draw(st, 2 * j + 1, cam->Ho);
         double X[3];
         cells[j] = y * cam->Wo + x;
-        px[j] = (float)(x * cam->sub + cam->sub / 2);       /* createSampling, dsacstar_util.h:70-72 */
-        py[j] = (float)(y * cam->sub + cam->sub / 2);
+        px[j] = cell_px(cam, x);
+        py[j] = cell_px(cam, y);
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
         xo_fetch(co, x, y, X);
         P[j].x = X[0]; P[j].y = X[1]; P[j].z = X[2];
@@ -166,11 +159,7 @@ static double xo_score(const xo_coords *co, const Pose *pose, const Cam *cam)
     for (int l = 0; l < 64; ++l) {
         double acc = 0.0;
         for (int i = l; i < cam->N; i += 64) {
-            float e = xo_cell_err(co, pose, i, cam);
-            float stf = beta * (e - cam->thr);
-            double st = (double)stf;
-            st = 1.0 / (1.0 + det_exp(-st));
-            acc += 1.0 - st;
+            acc += 1.0 - soft_inlier_st(xo_cell_err(co, pose, i, cam), cam->thr, beta);
         }
         part[l] = acc;
     }
@@ -190,8 +179,6 @@ typedef struct { double v[28]; } xo_vec28;
  * out[0..20] upper triangle of JtJ (row-major), out[21..26] Jt r, out[27] sum r^2 */
 static void xo_normal_eq(const xo_coords *co, const unsigned char *inl, const Pose *p, const Cam *cam, double out[28])
 {
-    const double f = cam->f, cx = cam->cx, cy = cam->cy;
-    const int sub = cam->sub;
     xo_vec28 *part = (xo_vec28 *)malloc(sizeof(xo_vec28) * XO_T);
     for (int tdx = 0; tdx < XO_T; ++tdx) {
         double a[28];
@@ -201,28 +188,7 @@ static void xo_normal_eq(const xo_coords *co, const unsigned char *inl, const Po
             int y = i / co->Wo, x = i - y * co->Wo;
             double X[3];
             xo_fetch(co, x, y, X);
-            double qx = p->R[0] * X[0] + p->R[1] * X[1] + p->R[2] * X[2];
-            double qy = p->R[3] * X[0] + p->R[4] * X[1] + p->R[5] * X[2];
-            double qz = p->R[6] * X[0] + p->R[7] * X[1] + p->R[8] * X[2];
-            double xc = qx + p->t[0], yc = qy + p->t[1], zc = qz + p->t[2];
-            double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-            double xn = xc * z, yn = yc * z;
-            double ru = (xn * f + cx) - (double)(float)(x * sub + sub / 2);
-            double rv = (yn * f + cy) - (double)(float)(y * sub + sub / 2);
-            double fa = f * z;               /* du/dXc */
-            double fc = -(fa * xn);          /* du/dZc */
-            double fd = -(fa * yn);          /* dv/dZc */
-            double Ju[6], Jv[6];
-            Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy);
-            Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc;
-            Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx;
-            Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd;
-            int k = 0;
-            for (int r = 0; r < 6; ++r)
-                for (int c = r; c < 6; ++c)
-                    a[k++] += Ju[r] * Ju[c] + Jv[r] * Jv[c];
-            for (int r = 0; r < 6; ++r) a[21 + r] += Ju[r] * ru + Jv[r] * rv;
-            a[27] += ru * ru + rv * rv;
+            pnp_cell_normal_eq(p, X[0], X[1], X[2], y, x, cam, a);
         }
         for (int k = 0; k < 28; ++k) part[tdx].v[k] = a[k];
     }
@@ -257,15 +223,11 @@ static int xo_lm_pnp(const xo_coords *co, const unsigned char *inl, const Cam *c
             } else break;
         }
         lg = (lg - 1 > -16) ? lg - 1 : -16;
-        double dn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        double pn = (3.0 - (prev.R[0] + prev.R[4] + prev.R[8]))
-                    + prev.t[0] * prev.t[0] + prev.t[1] * prev.t[1] + prev.t[2] * prev.t[2];
         ++iters;
-        if (iters >= XO_LM_MAX_ITER || dn < XO_FLT_EPSILON * XO_FLT_EPSILON * pn) break;
+        if (iters >= XLM_LM_MAX_ITER || lm_step_small(d, &prev)) break;
         memcpy(ne, ne_new, sizeof(ne));
     }
-    for (int i = 0; i < 9; ++i) if (!(cur.R[i] == cur.R[i])) return 0;
-    for (int i = 0; i < 3; ++i) if (!(cur.t[i] == cur.t[i])) return 0;
+    if (!pose_not_nan(&cur)) return 0;
     *pose = cur;
     return 1;
 }
@@ -282,7 +244,7 @@ static void xo_refine(const xo_coords *co, const Cam *cam, Pose *pose, unsigned 
     if (inlAcc) memset(inlAcc, 0, (size_t)N);
     unsigned best = 4, finalInl = 0;
     int rounds = 0, evals = 0;
-    for (int step = 0; step < XO_MAX_REF_STEPS; ++step) {
+    for (int step = 0; step < XL_DSAC_MAX_REF_STEPS; ++step) {
         unsigned cnt = 0;
         for (int i = 0; i < N; ++i) { inl[i] = (errs[i] < cam->thr) ? 1 : 0; cnt += inl[i]; }
         if (cnt <= best) break;
@@ -344,30 +306,21 @@ int xo_dsac_forward_rgb(const float *coords, int64_t sc, int64_t sy, int64_t sx,
     Pose pose = hyps[win];
     if (dbg) {
         dbg[0] = (double)win;
-        for (int i = 0; i < 9; ++i) dbg[4 + i] = pose.R[i];
-        for (int i = 0; i < 3; ++i) dbg[13 + i] = pose.t[i];
+        pose_store12(&pose, dbg + 4);
     }
 
     int rounds = 0, evals = 0;
     unsigned finalInl = 0;
     xo_refine(&co, &cam, &pose, NULL, &finalInl, &rounds, &evals);
 
-    /* pose2trans: inverse of [R t; 0 1], stored float row-major */
-    double Ti[16];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) Ti[4 * i + j] = pose.R[3 * j + i];
-        Ti[4 * i + 3] = -(pose.R[i] * pose.t[0] + pose.R[3 + i] * pose.t[1] + pose.R[6 + i] * pose.t[2]);
-    }
-    Ti[12] = 0.0; Ti[13] = 0.0; Ti[14] = 0.0; Ti[15] = 1.0;
-    for (int i = 0; i < 16; ++i) out_pose16[i] = (float)Ti[i];
+    pose_to_c2w16(&pose, out_pose16);     /* pose2trans: inverse of [R t; 0 1], stored float row-major */
 
     if (out_cells) memcpy(out_cells, cells, sizeof(int32_t) * 4 * (size_t)nHyp);
     if (out_tries) memcpy(out_tries, tries, sizeof(int32_t) * (size_t)nHyp);
     if (out_scores) memcpy(out_scores, scores, sizeof(double) * (size_t)nHyp);
     if (dbg) {
         dbg[1] = (double)rounds; dbg[2] = (double)finalInl; dbg[3] = (double)evals;
-        for (int i = 0; i < 9; ++i) dbg[16 + i] = pose.R[i];
-        for (int i = 0; i < 3; ++i) dbg[25 + i] = pose.t[i];
+        pose_store12(&pose, dbg + 16);
     }
     free(hyps); free(scores); free(cells); free(tries);
     return 0;
@@ -386,10 +339,7 @@ int xo_test_p3p(const double *P12, const double *uv8, double f, double cx, doubl
     const Cam cam = xo_test_cam(f, cx, cy, 0.0f);
     Pose p;
     int ok = p3p(P[0], P[1], P[2], P[3], uv, &cam, &p);
-    if (ok) {
-        for (int i = 0; i < 9; ++i) Rt12[i] = p.R[i];
-        for (int i = 0; i < 3; ++i) Rt12[9 + i] = p.t[i];
-    }
+    if (ok) pose_store12(&p, Rt12);
     return ok;
 }
 

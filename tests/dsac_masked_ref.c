@@ -2,9 +2,10 @@
  * tests/dsac_masked_ref.c — CPU restatement of the masked RGB DSAC* solver (xl_dsac_forward_rgb_masked_batch,
  * crossloc_amd/csrc/xl_dsac.hip with MASKED = true).
  *
- * TEST INFRASTRUCTURE ONLY.  The lane-local arithmetic is the product's xl_dsac_math.h and the order of the sums is
- * xl_dsac_reduce.h, compiled here by gcc as C99 with -ffp-contract=off.  This file restates serially what the kernel does in
- * parallel around them, in the manner of oracle/dsac_oracle.c (with which it shares no code, only the two headers): the tries of
+ * TEST INFRASTRUCTURE ONLY.  The lane-local arithmetic (per-cell normal equations, LM stop rule, soft-inlier term and pose
+ * write included) is the product's xl_dsac_math.h and the order of the sums is xl_dsac_reduce.h, compiled here by gcc as
+ * C99 with -ffp-contract=off.  This file restates serially what the kernel does in
+ * parallel around them, in the manner of oracle/dsac_oracle.c (with which it shares no code, only the product's headers): the tries of
  * a hypothesis in ascending order (the kernel's ballot picks the lowest accepted lane), lane l summing cells l, l + 64, ... and
  * the xor butterfly (the order of xo_score), first-maximum-wins selection, the 256 virtual threads of the normal equations (the
  * order of xo_normal_eq) and the LM state machine.  The mask enters at the four points include/crossloc_dsac.h names: a try
@@ -23,10 +24,8 @@
 
 #include "xl_dsac_math.h"
 #include "xl_dsac_reduce.h"
+#include "../../include/crossloc_dsac.h"      /* beside crossloc_amd/csrc, as the kernels include it: XL_DSAC_MAX_REF_STEPS */
 
-#define XM_MAX_REF_STEPS 100
-#define XM_LM_MAX_ITER 20
-#define XM_FLT_EPSILON 1.1920928955078125e-07
 #define XM_DBG 28
 #define XM_MAX_CELLS 16384
 #define XM_T XL_BLOCK_THREADS
@@ -64,8 +63,8 @@ static int xm_sample_try(const xm_image *im, const Cam *cam, uint64_t imageKey, 
         const int x = draw(st, 2 * j, cam->Wo);
         const int y = draw(st, 2 * j + 1, cam->Ho);
         cells[j] = y * cam->Wo + x;
-        px[j] = (float)(x * cam->sub + cam->sub / 2);
-        py[j] = (float)(y * cam->sub + cam->sub / 2);
+        px[j] = cell_px(cam, x);
+        py[j] = cell_px(cam, y);
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
         if (!im->mask[cells[j]]) usable = 0;
     }
@@ -95,11 +94,7 @@ static double xm_score(const xm_image *im, const Pose *pose, const Cam *cam)
         double acc = 0.0;
         for (int i = l; i < cam->N; i += 64) {
             if (!im->mask[i]) continue;
-            const float e = xm_cell_err(im, pose, i, cam);
-            const float stf = beta * (e - cam->thr);
-            double st = (double)stf;
-            st = 1.0 / (1.0 + det_exp(-st));
-            acc += 1.0 - st;
+            acc += 1.0 - soft_inlier_st(xm_cell_err(im, pose, i, cam), cam->thr, beta);
         }
         part[l] = acc;
     }
@@ -111,8 +106,6 @@ static double xm_score(const xm_image *im, const Pose *pose, const Cam *cam)
 /* normal equations over the inlier set at pose p: thread t accumulates cells t, t + 256, ..., then the canonical block sum */
 static void xm_normal_eq(const xm_image *im, const unsigned char *inl, const Pose *p, const Cam *cam, double out[28])
 {
-    const double f = cam->f, cx = cam->cx, cy = cam->cy;
-    const int sub = cam->sub;
     double *part = (double *)malloc(sizeof(double) * 28 * XM_T);
     for (int tdx = 0; tdx < XM_T; ++tdx) {
         double a[28];
@@ -122,28 +115,7 @@ static void xm_normal_eq(const xm_image *im, const unsigned char *inl, const Pos
             const int y = i / cam->Wo, x = i - y * cam->Wo;
             double X[3];
             xm_fetch(im, i, X);
-            const double qx = p->R[0] * X[0] + p->R[1] * X[1] + p->R[2] * X[2];
-            const double qy = p->R[3] * X[0] + p->R[4] * X[1] + p->R[5] * X[2];
-            const double qz = p->R[6] * X[0] + p->R[7] * X[1] + p->R[8] * X[2];
-            const double xc = qx + p->t[0], yc = qy + p->t[1], zc = qz + p->t[2];
-            const double z = (zc != 0.0) ? 1.0 / zc : 1.0;
-            const double xn = xc * z, yn = yc * z;
-            const double ru = (xn * f + cx) - (double)(float)(x * sub + sub / 2);
-            const double rv = (yn * f + cy) - (double)(float)(y * sub + sub / 2);
-            const double fa = f * z;
-            const double fc = -(fa * xn);
-            const double fd = -(fa * yn);
-            double Ju[6], Jv[6];
-            Ju[0] = fc * qy;            Ju[1] = fa * qz - fc * qx;  Ju[2] = -(fa * qy);
-            Ju[3] = fa;                 Ju[4] = 0.0;                Ju[5] = fc;
-            Jv[0] = fd * qy - fa * qz;  Jv[1] = -(fd * qx);         Jv[2] = fa * qx;
-            Jv[3] = 0.0;                Jv[4] = fa;                 Jv[5] = fd;
-            int k = 0;
-            for (int r = 0; r < 6; ++r)
-                for (int c = r; c < 6; ++c)
-                    a[k++] += Ju[r] * Ju[c] + Jv[r] * Jv[c];
-            for (int r = 0; r < 6; ++r) a[21 + r] += Ju[r] * ru + Jv[r] * rv;
-            a[27] += ru * ru + rv * rv;
+            pnp_cell_normal_eq(p, X[0], X[1], X[2], y, x, cam, a);
         }
         for (int k = 0; k < 28; ++k) part[tdx * 28 + k] = a[k];
     }
@@ -176,19 +148,16 @@ static int xm_lm_pnp(const xm_image *im, const unsigned char *inl, const Cam *ca
             } else break;
         }
         lg = (lg - 1 > -16) ? lg - 1 : -16;
-        const double dn = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
-        const double pn = (3.0 - (prev.R[0] + prev.R[4] + prev.R[8]))
-                          + prev.t[0] * prev.t[0] + prev.t[1] * prev.t[1] + prev.t[2] * prev.t[2];
         ++iters;
-        if (iters >= XM_LM_MAX_ITER || dn < XM_FLT_EPSILON * XM_FLT_EPSILON * pn) break;
+        if (iters >= XLM_LM_MAX_ITER || lm_step_small(d, &prev)) break;
         memcpy(ne, neNew, sizeof(ne));
     }
-    for (int i = 0; i < 9; ++i) if (!(cur.R[i] == cur.R[i])) return 0;
-    for (int i = 0; i < 3; ++i) if (!(cur.t[i] == cur.t[i])) return 0;
+    if (!pose_not_nan(&cur)) return 0;
     *pose = cur;
     return 1;
 }
 
+/* the dead image's pose as the kernel writes it: not pose_to_c2w16 of the identity, whose translation column is -0.0f */
 static void xm_identity16(float *pose16)
 {
     for (int i = 0; i < 16; ++i) pose16[i] = (i % 5 == 0) ? 1.0f : 0.0f;
@@ -207,10 +176,7 @@ int xm_forward_rgb_masked(const float *coords, int64_t sc, int64_t sy, int64_t s
     const int N = Ho * Wo;
     if (N > XM_MAX_CELLS) return -2;
     const xm_image im = { coords, sc, sy, sx, mask, Ho, Wo };
-    Cam cam;
-    cam.f = (double)focal; cam.cx = (double)ppx; cam.cy = (double)ppy;
-    cam.thr = thr; cam.alpha = alpha; cam.maxReproj = maxReproj;
-    cam.sub = sub; cam.Ho = Ho; cam.Wo = Wo; cam.N = N;
+    const Cam cam = cam_make(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     const uint64_t imageKey = image_key(seed, image);
 
     int nUsable = 0;
@@ -263,7 +229,7 @@ int xm_forward_rgb_masked(const float *coords, int64_t sc, int64_t sy, int64_t s
     unsigned char *inl = (unsigned char *)malloc((size_t)N);
     unsigned best = 4, finalInl = 0;
     int rounds = 0, evals = 0;
-    for (int step = 0; step < XM_MAX_REF_STEPS; ++step) {
+    for (int step = 0; step < XL_DSAC_MAX_REF_STEPS; ++step) {
         unsigned cnt = 0;
         for (int i = 0; i < N; ++i) {
             inl[i] = (mask[i] && xm_cell_err(&im, &pose, i, &cam) < cam.thr) ? 1 : 0;
@@ -280,11 +246,7 @@ int xm_forward_rgb_masked(const float *coords, int64_t sc, int64_t sy, int64_t s
     free(inl);
 
     /* ---- write (pose2trans): inverse rigid transform, float row-major */
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) pose16[4 * i + j] = (float)pose.R[3 * j + i];
-        pose16[4 * i + 3] = (float)(-(pose.R[i] * pose.t[0] + pose.R[3 + i] * pose.t[1] + pose.R[6 + i] * pose.t[2]));
-    }
-    pose16[12] = 0.0f; pose16[13] = 0.0f; pose16[14] = 0.0f; pose16[15] = 1.0f;
+    pose_to_c2w16(&pose, pose16);
     if (status) *status = 0;
     if (dbg) {
         dbg[1] = (double)rounds; dbg[2] = (double)finalInl; dbg[3] = (double)evals;

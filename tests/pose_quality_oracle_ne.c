@@ -3,8 +3,8 @@
  * oracle/dsac_oracle.c, the serial restatement of normal_eq_thread + block_sum in xl_dsac.hip) at a given pose over the
  * inlier set the refinement would form there (clamped float error < thr).  The oracle keeps that function static, so this file
  * compiles the oracle's translation unit and adds one entry point; tests/test_pose_quality_cpu.py holds the first 28 sums of the
- * pose-quality pass to its result bit for bit, which ties quality_cell_normal_eq to the solver's accumulation operation for
- * operation, order of the additions included.
+ * pose-quality pass to its result bit for bit.  Both sides accumulate pnp_cell_normal_eq of xl_dsac_math.h per inlier, so the
+ * comparison is of what surrounds it: the inlier set, the walk of the threads over the cells and the order of the additions.
  */
 #include "../oracle/dsac_oracle.c"
 

@@ -18,15 +18,6 @@
 
 #define XQ_T XL_BLOCK_THREADS         /* threads of the kernel's workgroup: 4 waves of 64 */
 
-static Cam xq_cam(int Ho, int Wo, float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub)
-{
-    Cam cam;
-    cam.f = (double)focal; cam.cx = (double)ppx; cam.cy = (double)ppy;
-    cam.thr = thr; cam.alpha = alpha; cam.maxReproj = maxReproj;
-    cam.sub = sub; cam.Ho = Ho; cam.Wo = Wo; cam.N = Ho * Wo;
-    return cam;
-}
-
 /* the kernel from its pose on: per-thread partials, canonical reduction, final step */
 static void xq_sums(const float *coords, int64_t sc, int64_t sy, int64_t sx, const Cam *cam, const Pose *pose, bool poseOk,
                     double *s)
@@ -60,7 +51,7 @@ int xq_pose_quality(const float *coords, int64_t sc, int64_t sy, int64_t sx, int
                     float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *row)
 {
     if (!coords || !pose16 || !row || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
-    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    const Cam cam = cam_make(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     const bool poseOk = quality_pose16_finite(pose16);
     Pose pose;
     if (poseOk) quality_pose_from16(pose16, &pose);
@@ -75,7 +66,7 @@ int xq_pose_quality_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx,
                         float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *row)
 {
     if (!coords || !Rt12 || !row || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
-    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    const Cam cam = cam_make(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     Pose pose;
     pose_load12(Rt12, &pose);
     const bool poseOk = quality_pose_finite(&pose);
@@ -89,7 +80,7 @@ int xq_test_sums_w2c(const float *coords, int64_t sc, int64_t sy, int64_t sx, in
                      float thr, float focal, float ppx, float ppy, float alpha, float maxReproj, int sub, double *sums32)
 {
     if (!coords || !Rt12 || !sums32 || Ho <= 0 || Wo <= 0 || sub <= 0) return -1;
-    const Cam cam = xq_cam(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
+    const Cam cam = cam_make(Ho, Wo, thr, focal, ppx, ppy, alpha, maxReproj, sub);
     Pose pose;
     pose_load12(Rt12, &pose);
     xq_sums(coords, sc, sy, sx, &cam, &pose, true, sums32);

@@ -80,9 +80,7 @@ int xr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, cons
     XrIn in;
     in.coords = coords; in.sc = sc; in.sy = sy; in.sx = sx;
     in.sigma = sigma; in.gy = gy; in.gx = gx;
-    in.cam.f = (double)focal; in.cam.cx = (double)ppx; in.cam.cy = (double)ppy;
-    in.cam.thr = thr; in.cam.alpha = 0.0f; in.cam.maxReproj = maxReproj;
-    in.cam.sub = sub; in.cam.Ho = Ho; in.cam.Wo = Wo; in.cam.N = Ho * Wo;
+    in.cam = cam_make(Ho, Wo, thr, focal, ppx, ppy, 0.0f, maxReproj, sub);
     in.s0sq = (double)s0 * (double)s0;
     const int N = in.cam.N;
 
@@ -118,7 +116,7 @@ int xr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, cons
         int lg = -3;
         double inv[36];
         bool failed = !quality_inv6(ne, inv);           /* J^T W J at the round's pose must be positive definite */
-        for (int it = 0; !failed && it < XLR_LM_MAX_ITER; ++it) {
+        for (int it = 0; !failed && it < XLM_LM_MAX_ITER; ++it) {
             double d[6];
             prev = cur;
             if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
@@ -134,7 +132,7 @@ int xr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, cons
             }
             if (failed) break;
             lg = (lg - 1 > -16) ? lg - 1 : -16;
-            if (refine_step_small(d, &prev)) break;
+            if (lm_step_small(d, &prev)) break;
             for (int k = 0; k < 28; ++k) ne[k] = neNew[k];
         }
         if (!failed && !quality_pose_finite(&cur)) failed = true;
@@ -160,28 +158,24 @@ int xr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, cons
 
 /* --- hooks for the header-piece tests: thin calls into the shared headers --- */
 
-/* the 28 sums one cell adds at pose Rt12: weighted with w through refine_cell_normal_eq (out28w), and through
- * quality_cell_normal_eq (out28q) */
+/* the 28 sums one cell adds at pose Rt12: weighted with w through pnp_cell_normal_eq_w (out28w), and through the
+ * unweighted pnp_cell_normal_eq (out28q) */
 void xr_test_cell_normal_eq(const double *Rt12, const double *xyz, double w, int y, int x, float focal, float ppx, float ppy, int sub,
                             double *out28w, double *out28q)
 {
     Pose p;
     pose_load12(Rt12, &p);
-    Cam cam;
-    memset(&cam, 0, sizeof(cam));
-    cam.f = (double)focal; cam.cx = (double)ppx; cam.cy = (double)ppy; cam.sub = sub;
+    const Cam cam = cam_make(0, 0, 0.0f, focal, ppx, ppy, 0.0f, 0.0f, sub);
     for (int k = 0; k < 28; ++k) { out28w[k] = 0.0; out28q[k] = 0.0; }
-    refine_cell_normal_eq(&p, xyz[0], xyz[1], xyz[2], w, y, x, &cam, out28w);
-    quality_cell_normal_eq(&p, xyz[0], xyz[1], xyz[2], y, x, &cam, out28q);
+    pnp_cell_normal_eq_w(&p, xyz[0], xyz[1], xyz[2], w, y, x, &cam, out28w);
+    pnp_cell_normal_eq(&p, xyz[0], xyz[1], xyz[2], y, x, &cam, out28q);
 }
 
 double xr_test_weight(const double *Rt12, const double *xyz, double sigma, double s0, float focal)
 {
     Pose p;
     pose_load12(Rt12, &p);
-    Cam cam;
-    memset(&cam, 0, sizeof(cam));
-    cam.f = (double)focal;
+    const Cam cam = cam_make(0, 0, 0.0f, focal, 0.0, 0.0, 0.0f, 0.0f, 0);
     return refine_weight(&p, xyz[0], xyz[1], xyz[2], sigma, s0 * s0, &cam);
 }
 

@@ -63,7 +63,7 @@ class Ref:
         return out.reshape(4, 4), row, w2c, mask.reshape(Ho, Wo).astype(bool)
 
     def cell_normal_eq(self, R, t, xyz, w, y, x, focal, ppx, ppy, sub):
-        """(the 28 sums of one cell through refine_cell_normal_eq with weight w, the same through quality_cell_normal_eq)"""
+        """(the 28 sums of one cell through pnp_cell_normal_eq_w with weight w, the same through pnp_cell_normal_eq)"""
         a, q = np.zeros(28, np.float64), np.zeros(28, np.float64)
         xyz = np.ascontiguousarray(xyz, np.float64)
         self.L.xr_test_cell_normal_eq(_ptr(rt12(R, t)), _ptr(xyz), float(w), int(y), int(x), float(focal), float(ppx), float(ppy),

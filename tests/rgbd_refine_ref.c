@@ -129,7 +129,7 @@ int xrr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, con
         }
         int lg = -3;
         bool failed = !rgbdr_well_posed(ne);
-        for (int it = 0; !failed && it < XLR_LM_MAX_ITER; ++it) {
+        for (int it = 0; !failed && it < XLM_LM_MAX_ITER; ++it) {
             double d[6];
             prev = cur;
             if (!solve6(ne, lambda_of(lg), d)) { failed = true; break; }
@@ -145,7 +145,7 @@ int xrr_refine_pose(const float *coords, int64_t sc, int64_t sy, int64_t sx, con
             }
             if (failed) break;
             lg = (lg - 1 > -16) ? lg - 1 : -16;
-            if (refine_step_small(d, &prev)) break;
+            if (lm_step_small(d, &prev)) break;
             for (int k = 0; k < 28; ++k) ne[k] = neNew[k];
         }
         if (!failed && !quality_pose_finite(&cur)) failed = true;

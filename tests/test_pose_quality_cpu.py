@@ -122,10 +122,11 @@ def test_inlier_count_and_sums_against_the_oracle(qref, oracle):
 
 
 def test_normal_equation_sums_are_the_solvers_bit_for_bit(qref, oracle, tmp_path):
-    """quality_cell_normal_eq restates what the refinement accumulates per inlier (normal_eq_thread in xl_dsac.hip, xo_normal_eq
-    in the oracle - which the solver kernels match bitwise).  Held together here: the pass's 28 normal-equation sums equal the
-    oracle's own xo_normal_eq over the refinement's inlier set at the same pose, bit for bit, order of the additions included -
-    at ground truth and at the oracle's refined pose, with outliers, on a full and on a ragged grid."""
+    """The pass and the solver's refinement accumulate the same function per inlier (pnp_cell_normal_eq of xl_dsac_math.h), so
+    the per-cell arithmetic agrees by construction.  What is held together here is what each builds on top of it: the inlier
+    set, the walk of the 256 virtual threads over the cells and the order of the additions.  The pass's 28 normal-equation sums
+    equal the oracle's own xo_normal_eq (which the solver kernels match bitwise) over the refinement's inlier set at the same
+    pose, bit for bit - at ground truth and at the oracle's refined pose, with outliers, on a full and on a ragged grid."""
     ne = pose_quality_ref.load_oracle_normal_eq(tmp_path)
     for seed, Ho, Wo in ((5, 60, 90), (6, 37, 53), (7, 7, 9)):
         sc = synth.make_scene(seed, noise=0.5, outlier_ratio=0.3, Ho=Ho, Wo=Wo)

@@ -118,6 +118,9 @@ def test_covariance_is_calibrated_when_neither_the_gate_nor_the_floor_bites(ref)
 
 
 def test_weight_one_gives_the_bits_of_the_unweighted_normal_equations(ref):
+    """The weighted and the unweighted accumulator (pnp_cell_normal_eq_w, pnp_cell_normal_eq of xl_dsac_math.h) form the rows
+    with one function; what is checked is what they add on top of it: the weight multiplies each product, not the rows, so
+    w == 1.0 gives the unweighted bits and a power of two scales exactly.  And the weight itself against its formula."""
     sc = rc.hetero(21)
     R, t = rc.w2c(sc["pose"])
     for (y, x) in ((0, 0), (5, 17), (23, 35), (11, 2)):
