@@ -21,6 +21,8 @@ Round 4 - the BASELINE sizes and the backward pass (inputs regenerated from seed
   grads_full.npz  (round 5) the same step at 480x720, batch 1, float64 network
   losses_b16.npz  loss/coord.py:87-188, loss/depth.py:7-76, loss/normal.py:8-127 at [16,*,60,90]: value, rate, gradient
                   moments and strided samples
+  loss_branches.npz  the same three losses and loss/semantics.py:44-91 on the scenes of tests/loss_branch_cases.py (every
+                  branch in every workgroup), fp32 and float64: inputs, per-image and mean values, rate, full gradients
 """
 import builtins
 import os
@@ -418,8 +420,80 @@ def loss_b16_goldens():
     _print("losses_b16.npz", {k: (v.shape if v.ndim else float(v)) for k, v in out.items()})
 
 
+def loss_branch_goldens():
+    """The four losses on the branch scenes of tests/loss_branch_cases.py (every branch of loss/coord.py:87-188,
+    loss/depth.py:7-76, loss/normal.py:8-127 and loss/semantics.py:44-91 in every workgroup): inputs, and per run - fp32 and
+    float64, MLE and plain, both clamp pairs for coord - the per-image losses (reduction None), the mean, the rate and the
+    gradients of the per-image losses weighted by linspace(0.5, 1.5, B)."""
+    from loss.semantics import semantics_classification_loss, CrossEntropyLoss2d
+    sys.path.insert(0, os.path.dirname(HERE))
+    import loss_branch_cases as bc
+    pixel_grid = get_pixel_grid(int(bc.SUB))
+    out = {}
+
+    def record(pre, fn, leaves, dt):
+        """fn(reduction) -> (loss, rate) on fresh leaves; stores <pre>_{loss_none, loss_mean, rate, dpred[, dunc]}."""
+        p, u = leaves()
+        loss, rate = quiet(fn, p, u, None)
+        w = torch.linspace(0.5, 1.5, loss.shape[0], dtype=dt)
+        (loss * w).sum().backward()
+        out[pre + "_loss_none"] = loss.detach().double().numpy()
+        out[pre + "_rate"] = np.array(float(rate))
+        out[pre + "_dpred"] = p.grad.numpy().copy()
+        if u is not None and u.grad is not None:
+            out[pre + "_dunc"] = u.grad.numpy().copy()
+        p, u = leaves()
+        mean, rate_mean = quiet(fn, p, u, 'mean')
+        assert float(rate_mean) == float(rate)
+        out[pre + "_loss_mean"] = np.array(mean.item(), np.float64)
+
+    for shape in bc.SHAPES:
+        B, Ho, Wo = shape
+        I = {l: bc.BUILD[l](shape) for l in ("coord", "depth", "normal")}
+        for C in bc.SEM_CHANNELS:
+            I["sem%d" % C] = bc.build_sem(shape, C)
+        for l, inp in I.items():
+            for k, v in inp.items():
+                out[bc.key(l, shape, k)] = v
+        # the pose inverse as this host's MKL rounds it (tests/test_loss_branches_cpu.py pins the fp32 oracle to it on other hosts)
+        out[bc.key("coord", shape, "poses_inv")] = torch.linalg.inv(torch.tensor(I["coord"]["poses"])).numpy()
+        f, cx, cy = bc.coord_intrinsics(shape)
+        cam_mat = get_cam_mat(2 * cx, 2 * cy, f)
+        for dt, dn in ((torch.float32, "f32"), (torch.float64, "f64")):
+            torch.set_default_dtype(dt)
+            pg, cm = pixel_grid.to(dt), cam_mat.to(dt)
+
+            def T(l, name, grad=False):
+                return torch.tensor(I[l][name], dtype=dt, requires_grad=grad)
+            for mode in bc.MODES:
+                for ci, (soft, hard) in enumerate(bc.COORD_CLAMPS):
+                    record(bc.key("coord", shape, bc.run_tag("coord", mode, ci), dn),
+                           lambda p, u, red: scene_coords_regression_loss(
+                               bc.MIN_DEPTH, soft, hard, bc.TOL, mode, pg, bc.NODATA, cm, p, u, T("coord", "poses"),
+                               T("coord", "gt"), red),
+                           lambda: (T("coord", "pred", True), T("coord", "unc", True)), dt)
+                record(bc.key("depth", shape, bc.run_tag("depth", mode), dn),
+                       lambda p, u, red: depth_regression_loss(bc.MIN_DEPTH, bc.DEPTH_HARD, mode, bc.NODATA, p, u,
+                                                               T("depth", "gt"), red),
+                       lambda: (T("depth", "pred", True), T("depth", "unc", True)), dt)
+                record(bc.key("normal", shape, bc.run_tag("normal", mode), dn),
+                       lambda p, u, red: normal_regression_loss(bc.NORMAL_HARD, mode, bc.NODATA, p, u, T("normal", "gt"), red),
+                       lambda: (T("normal", "logits", True), T("normal", "unc", True)), dt)
+            for C in bc.SEM_CHANNELS:
+                l = "sem%d" % C
+                record(bc.key(l, shape, dn),
+                       lambda p, u, red: semantics_classification_loss(None, p, None, T(l, "labels"), CrossEntropyLoss2d(), red),
+                       lambda: (T(l, "logits", True), None), dt)
+        torch.set_default_dtype(torch.float32)
+    bc.pack_clamp_runs(out)
+    np.savez_compressed(os.path.join(HERE, "loss_branches.npz"), **out)
+    _print("loss_branches.npz", len(out), "arrays,", os.path.getsize(os.path.join(HERE, "loss_branches.npz")), "bytes")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["net", "net4", "loss", "semantics", "full", "grads", "loss16", "gradsfull", "tiny"]
+    which = sys.argv[1:] or ["net", "net4", "loss", "semantics", "full", "grads", "loss16", "gradsfull", "tiny", "lossbranches"]
+    if "lossbranches" in which:
+        loss_branch_goldens()
     if "tiny" in which:
         tiny_goldens()
     if "gradsfull" in which:
