@@ -77,6 +77,14 @@ struct Coords {
 struct MaskBits {
     const uint32_t *w;
     __device__ __forceinline__ bool usable(int i) const { return (w[i >> 5] >> (i & 31)) & 1u; }
+    // thread tid's slice of the mask in the layout of an inlier word (RefineOut::inlAcc): bit j <-> cell tid + 256 j
+    __device__ __forceinline__ unsigned long long slice(int tid, int N) const
+    {
+        unsigned long long u = 0ull;
+        int j = 0;
+        for (int i = tid; i < N; i += kThreads, ++j) if (usable(i)) u |= (1ull << j);
+        return u;
+    }
 };
 
 // row / column of a cell index that advances by a constant stride: one division at the start, then adds and compares (an integer
@@ -98,6 +106,26 @@ __device__ __forceinline__ void stage_coords(const float *g, int64_t sc, int64_t
         sCo[Npad + i] = q[sc];
         sCo[2 * Npad + i] = q[2 * sc];
     }
+}
+
+// validity mask of one image (gm: its N bytes, nonzero = usable) -> LDS as a bit plane of ceil(N / 32) words: each wave ballots 64
+// consecutive cells into two words.  Returns the usable cells this wave counted (the same in all of its lanes); the caller adds
+// the four up after its barrier.  Serves the forward kernel and the backward kernels K1 and K3.
+__device__ __forceinline__ int stage_mask(const uint8_t *gm, int N, uint32_t *sMask, int wave, int lane)
+{
+    const int nWords = (N + 31) >> 5;
+    int cnt = 0;
+    for (int base = wave * 64; base < N; base += kThreads) {
+        const int i = base + lane;
+        const bool u = (i < N) && gm[i] != 0;
+        const unsigned long long m = __ballot(u);
+        cnt += __popcll(m);
+        if (lane == 0) {
+            sMask[base >> 5] = (uint32_t)m;
+            if ((base >> 5) + 1 < nWords) sMask[(base >> 5) + 1] = (uint32_t)(m >> 32);
+        }
+    }
+    return cnt;
 }
 
 // one sampling try (dsacstar_util.h:159-219); returns accept flag, pose = try result (identity if P3P failed)
@@ -316,19 +344,7 @@ void xl_dsac_forward_kernel(Params P)
     // ---- masked: the mask as a bit plane (each wave ballots 64 consecutive cells into two words), usable cells counted per wave
     uint32_t *sMask = reinterpret_cast<uint32_t *>(sCo + 3 * P.Npad);
     if constexpr (MASKED) {
-        const uint8_t *gm = P.mask + (int64_t)b * N;
-        const int nWords = (N + 31) >> 5;
-        int cnt = 0;
-        for (int base = wave * 64; base < N; base += kThreads) {
-            const int i = base + lane;
-            const bool u = (i < N) && gm[i] != 0;
-            const unsigned long long m = __ballot(u);
-            cnt += __popcll(m);
-            if (lane == 0) {
-                sMask[base >> 5] = (uint32_t)m;
-                if ((base >> 5) + 1 < nWords) sMask[(base >> 5) + 1] = (uint32_t)(m >> 32);
-            }
-        }
+        const int cnt = stage_mask(P.mask + (int64_t)b * N, N, sMask, wave, lane);
         if (lane == 0) S.pad[wave] = cnt;
     }
     __syncthreads();
@@ -364,9 +380,7 @@ void xl_dsac_forward_kernel(Params P)
             }
             return;
         }
-        usable = 0ull;
-        int j = 0;
-        for (int i = tid; i < N; i += kThreads, ++j) if (mb.usable(i)) usable |= (1ull << j);
+        usable = mb.slice(tid, N);
     }
 
     const uint64_t imageIdx = P.image0 + (uint64_t)b * P.imageStride;
@@ -536,9 +550,23 @@ struct BwdParams {
     double *rec; unsigned long long *masks; double *outLoss;
     int nHyp, Ho, Wo, sub, Npad;
     float thr, focal, ppx, ppy, alpha, maxReproj, wRot, wTrans, softClamp;
+    const uint8_t *mask;          // masked backward: [B][Ho*Wo], nonzero = usable cell
+    int32_t *status;              // masked backward: [B], 1 = dead image (fewer than four usable cells), else 0; never null there.
+                                  // Written by the h == 0 workgroup of K1, read by K2, K3 and K4 (later launches on the same stream)
 };
 
+// MASKED (xl_dsac_backward_rgb_masked_batch), the forward's rules carried over.  K1 and K3 stage the mask as the forward kernel's bit
+// plane behind the coordinate planes.  K1 refines over the usable cells (refine_pose<true>), so the inlier words it leaves in
+// P.masks hold usable cells only and the two inlier walks need nothing more.  K3 sums path II over the usable cells (a masked-out
+// cell's term is selected away, never multiplied by zero) and gives a hypothesis that carries a masked-out cell - tries exhausted
+// on a mask-rejected try: identity pose, the last draws - the zero dPNP of a failed solve without reading that cell.  K4 leaves
+// the gradient of a masked-out cell as it came in, without reading its coordinates.  A dead image (fewer than four usable cells;
+// xl_dsac_forward_kernel<1, true> has then written neither poses nor cells) gets loss 0, status 1, zero records and an untouched
+// gradient: K1 decides that on its own count before it reads a score and publishes it in P.status, on which K2, K3 and K4 return
+// before they read anything of that image's workspace.
+
 // K1 (grid nHyp x B): soft-max probability of the hypothesis, refinement if it matters, loss, path-I quantities
+template <bool MASKED = false>
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_hyp_kernel(BwdParams P)
 {
@@ -550,6 +578,20 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     const int h = blockIdx.x, b = blockIdx.y;
     const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     const int N = cam.N;
+    MaskBits mb{ reinterpret_cast<const uint32_t *>(sCo + 3 * P.Npad) };
+    if constexpr (MASKED) {
+        const int cnt = stage_mask(P.mask + (int64_t)b * N, N, reinterpret_cast<uint32_t *>(sCo + 3 * P.Npad), wave, lane);
+        if (lane == 0) S.pad[wave] = cnt;
+        __syncthreads();
+        const bool dead = S.pad[0] + S.pad[1] + S.pad[2] + S.pad[3] < 4;          // uniform over the workgroups of the image
+        if (h == 0 && tid == 0) P.status[b] = dead ? 1 : 0;
+        if (dead) {
+            // nothing of this image was sampled: the record is all zero, and neither a score nor a pose is read
+            double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
+            for (int i = tid; i < kRec; i += kThreads) rec[i] = 0.0;
+            return;
+        }
+    }
 
     // softMax (dsacstar_util.h:684-704), every thread in the same order
     const double *sc = P.scores + (int64_t)b * P.nHyp;
@@ -569,7 +611,8 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
     if (active) {
         stage_coords(P.coords + (int64_t)b * P.sb, P.sc, P.sy, P.sx, P.Wo, N, P.Npad, sCo, tid);
         __syncthreads();
-        refine_pose(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel);
+        if constexpr (MASKED) refine_pose<true>(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel, mb.slice(tid, N));
+        else refine_pose(co, cam, S, tid, wave, lane, pose, ro, redSel, cntSel);
     }
     Gt gt;
     gt_from_pose16(P.gt + (int64_t)b * 16, &gt);
@@ -657,10 +700,16 @@ void xl_dsac_bwd_hyp_kernel(BwdParams P)
 }
 
 // K2 (grid B): expected loss and the gradient of the soft-max selection (dsacstar_derivative.h:345-356)
+template <bool MASKED = false>
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_expect_kernel(BwdParams P)
 {
     const int b = blockIdx.x, tid = threadIdx.x;
+    if constexpr (MASKED)
+        if (P.status[b]) {                                      // dead image (K1 wrote the flag): loss 0, no record walk
+            if (tid == 0) P.outLoss[b] = 0.0;
+            return;
+        }
     double *rec = P.rec + (int64_t)b * P.nHyp * kRec;
     if (tid == 0) {
         double e = 0.0;
@@ -678,6 +727,7 @@ void xl_dsac_bwd_expect_kernel(BwdParams P)
 
 // K3 (grid nHyp x B): path II per hypothesis — g6 = sum_c dRepro(c) J_init(c), dPNP by central differences,
 // support-point gradients (dsacstar_derivative.h:209-320)
+template <bool MASKED = false>
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_score_kernel(BwdParams P)
 {
@@ -687,11 +737,16 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
+    // dead image: K1 has counted the mask and written the flag; nothing of the image's workspace is read, rec[0] included (an
+    // inactive hypothesis of a live image then leaves as early as in the unmasked kernel, without staging anything)
+    if constexpr (MASKED) if (P.status[b]) return;
     double *rec = P.rec + ((int64_t)b * P.nHyp + h) * kRec;
     if (rec[0] < XLM_PROB_THRESH) return;
     const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     const int N = cam.N;
     stage_coords(P.coords + (int64_t)b * P.sb, P.sc, P.sy, P.sx, P.Wo, N, P.Npad, sCo, tid);
+    MaskBits mb{ reinterpret_cast<const uint32_t *>(sCo + 3 * P.Npad) };
+    if constexpr (MASKED) (void)stage_mask(P.mask + (int64_t)b * N, N, reinterpret_cast<uint32_t *>(sCo + 3 * P.Npad), wave, lane);
     __syncthreads();
     Coords co{ sCo, sCo + P.Npad, sCo + 2 * P.Npad };
     Pose init;
@@ -713,8 +768,15 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
         double dRep = -st * (1.0 - st) * (double)beta * sog;
         dRep *= (double)facf;
         resid_row(&init, dRi, X, Y, Z, cell_px(&cam, x), cell_px(&cam, y), &cam, J6);
+        if constexpr (MASKED) {
+            // whatever a masked-out cell holds was fetched and differentiated above; none of it reaches a[]
+            const bool u = mb.usable(i);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) a[k] += dRep * J6[k];
+            for (int k = 0; k < 6; ++k) a[k] += u ? dRep * J6[k] : 0.0;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a[k] += dRep * J6[k];
+        }
     }
     block_sum(a, S.red[0], wave, lane);
 
@@ -722,7 +784,11 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
     // += eps sequence of the earlier columns is replayed so every solve sees the points the serial code would
     double *sol = S.red[1];                                  // [18][7]: rvec, tvec, ok
     const int32_t *cells = P.cells + ((int64_t)b * P.nHyp + h) * 4;
-    if (tid < 18) {
+    // masked: a hypothesis whose tries ran out on a mask-rejected try carries masked-out cells; their coordinates are not read,
+    // the 18 solves are skipped and J is the zero of a failed solve (the same decision in every thread: it is read off the plane)
+    bool skip = false;
+    if constexpr (MASKED) skip = !(mb.usable(cells[0]) && mb.usable(cells[1]) && mb.usable(cells[2]) && mb.usable(cells[3]));
+    if (!skip && tid < 18) {
         const float eps = 0.001f;
         float pts[4][3];
         double uv[4][2];
@@ -756,7 +822,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
         double J[72];
         for (int k = 0; k < 72; ++k) J[k] = 0.0;
         const double den = (double)(2 * 0.001f);
-        bool fail = false;
+        bool fail = skip;
         for (int col = 0; col < 9 && !fail; ++col) {
             const double *f = sol + (2 * col) * 7, *bk = sol + (2 * col + 1) * 7;
             if (f[6] == 0.0 || bk[6] == 0.0) { fail = true; break; }
@@ -783,6 +849,7 @@ void xl_dsac_bwd_score_kernel(BwdParams P)
 
 // K4 (grid ceil(N/256) x B): assemble the gradient per cell, hypotheses in ascending order, float accumulation
 // like the reference's tensor += (dsacstar.cpp:462-480)
+template <bool MASKED = false>
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_bwd_assemble_kernel(BwdParams P)
 {
@@ -790,6 +857,9 @@ void xl_dsac_bwd_assemble_kernel(BwdParams P)
     const int i = blockIdx.x * kThreads + threadIdx.x;
     const Cam cam = cam_make(P.Ho, P.Wo, P.thr, P.focals ? P.focals[b] : P.focal, P.ppx, P.ppy, P.alpha, P.maxReproj, P.sub);
     if (i >= cam.N) return;
+    // masked: a dead image (K1's flag) and a masked-out cell (its byte in global memory: this kernel uses no LDS) keep the incoming
+    // gradient bit for bit - it is neither read nor written - and their coordinates are not read
+    if constexpr (MASKED) if (P.status[b] || P.mask[(int64_t)b * cam.N + i] == 0) return;
     const int y = i / cam.Wo, x = i - y * cam.Wo;
     const float *q = P.coords + (int64_t)b * P.sb + (int64_t)y * P.sy + (int64_t)x * P.sx;
     const double X = (double)q[0], Y = (double)q[P.sc], Z = (double)q[2 * P.sc];
@@ -922,6 +992,100 @@ int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t 
     return XL_OK;
 }
 
+// sub-blocks per image of the backward pass's sample + score launch (it fills the chip further than the forward's: ~4 workgroups per CU)
+int backward_sub_blocks(int B, int n_hyp)
+{
+    int S = 1;
+    while (S * 2 * kWaves <= n_hyp && (long long)B * S * 2 <= 1024) S *= 2;
+    return S;
+}
+
+// the launch sequence of both backward passes: MASKED adds the mask and the status vector, the bit plane to the LDS carve, and
+// launches the masked instantiations (which keep an LDS limit of their own).  Everything is validated before the first HIP call.
+template <bool MASKED>
+int backward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                        int B, int Ho, int Wo, const uint8_t *mask_dev,
+                        float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                        const float *gt_poses_dev, double *out_loss_dev, int32_t *status_dev,
+                        int n_hyp, float thr, float focal, float ppx, float ppy,
+                        float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
+                        const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
+                        uint32_t max_tries, void *stream, double *rec_dev)
+{
+    if (!coords_dev || !grad_dev || !gt_poses_dev || !out_loss_dev || B <= 0 || Ho <= 0 || Wo <= 0 || n_hyp <= 0 ||
+        sub <= 0 || max_tries == 0)
+        return XL_ERR_ARG;
+    if (MASKED && !mask_dev) return XL_ERR_ARG;
+    const int N = Ho * Wo;
+    if (N > kMaxCells) return XL_ERR_GRID;
+    const int Npad = (N + 3) & ~3;
+    size_t lds = ((sizeof(Smem) + 15) & ~size_t(15)) + (size_t)3 * Npad * sizeof(float);
+    if (MASKED) lds += sizeof(uint32_t) * (size_t)((N + 31) / 32);          // the bit plane: 676 B at 60x90
+    if (lds > 160 * 1024) return XL_ERR_GRID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nh = (size_t)B * n_hyp;
+
+    // workspace: every hypothesis' pose, score and sampled cells; per-hypothesis records and inlier masks; masked, without a
+    // status vector of the caller's: the dead-image flags
+    const int S = backward_sub_blocks(B, n_hyp);
+    const size_t bPoses = sizeof(double) * nh * 12, bScores = sizeof(double) * nh, bCells = sizeof(int32_t) * nh * 4;
+    const size_t bRec = rec_dev ? 0 : sizeof(double) * nh * kRec, bMasks = sizeof(unsigned long long) * nh * kThreads;
+    const size_t bPart = sizeof(double) * ((size_t)B * S * kWaves * 16 + (size_t)B * 12);
+    const size_t bFlags = (MASKED && !status_dev) ? sizeof(int32_t) * (size_t)B : 0;
+    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
+    unsigned char *ws = nullptr;
+    XL_HIP(hipMallocAsync((void **)&ws, up(bPoses) + up(bScores) + up(bCells) + up(bRec) + up(bMasks) + up(bPart) + up(bFlags), st));
+    unsigned char *cur = ws;
+    double *hypPoses = (double *)cur; cur += up(bPoses);
+    double *scores = (double *)cur; cur += up(bScores);
+    int32_t *cells = (int32_t *)cur; cur += up(bCells);
+    double *rec = rec_dev ? rec_dev : (double *)cur; cur += up(bRec);
+    unsigned long long *masks = (unsigned long long *)cur; cur += up(bMasks);
+    double *part = (double *)cur; cur += up(bPart);
+    int32_t *flags = status_dev ? status_dev : (int32_t *)cur;
+
+    Params P;
+    P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
+    P.outPoses = nullptr; P.focals = focals_dev;
+    P.cells = cells; P.tries = nullptr; P.scores = scores; P.dbg = nullptr; P.hypPoses = hypPoses;
+    P.seed = seed; P.image0 = image0; P.imageStride = image_stride; P.maxTries = max_tries;
+    P.nHyp = n_hyp; P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = Npad;
+    P.thr = thr; P.focal = focal; P.ppx = ppx; P.ppy = ppy; P.alpha = alpha; P.maxReproj = max_reproj;
+    P.part = part; P.S = S;
+    P.pairCells = 1; P.cellWalk = 1;
+    P.mask = mask_dev; P.status = nullptr;                     // (the sample + score phase writes no status: K1 does)
+    BwdParams Q;
+    Q.coords = coords_dev; Q.sb = sb; Q.sc = sc; Q.sy = sy; Q.sx = sx;
+    Q.grad = grad_dev; Q.gsb = gsb; Q.gsc = gsc; Q.gsy = gsy; Q.gsx = gsx;
+    Q.gt = gt_poses_dev; Q.focals = focals_dev;
+    Q.hypPoses = hypPoses; Q.scores = scores; Q.cells = cells; Q.rec = rec; Q.masks = masks; Q.outLoss = out_loss_dev;
+    Q.nHyp = n_hyp; Q.Ho = Ho; Q.Wo = Wo; Q.sub = sub; Q.Npad = P.Npad;
+    Q.thr = thr; Q.focal = focal; Q.ppx = ppx; Q.ppy = ppy; Q.alpha = alpha; Q.maxReproj = max_reproj;
+    Q.wRot = w_rot; Q.wTrans = w_trans; Q.softClamp = soft_clamp;
+    Q.mask = mask_dev; Q.status = MASKED ? flags : nullptr;
+
+    static XlLdsLimit configured;
+    int cfgDev;
+    if (configured.needs(lds, &cfgDev)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASKED>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_hyp_kernel<MASKED>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_score_kernel<MASKED>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "hipFuncSetAttribute(backward_rgb)"); }
+        configured.done(lds, cfgDev);
+    }
+    hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASKED>), dim3(S, B), dim3(kThreads), lds, st, P);
+    hipLaunchKernelGGL((xl_dsac_bwd_hyp_kernel<MASKED>), dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
+    hipLaunchKernelGGL((xl_dsac_bwd_expect_kernel<MASKED>), dim3(B), dim3(kThreads), 0, st, Q);
+    hipLaunchKernelGGL((xl_dsac_bwd_score_kernel<MASKED>), dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
+    hipLaunchKernelGGL((xl_dsac_bwd_assemble_kernel<MASKED>), dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, Q);
+    XL_HIP(hipFreeAsync(ws, st));
+    XL_HIP(hipGetLastError());
+    return XL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1035,6 +1199,11 @@ done:
     return rc;
 }
 
+int xl_dsac_backward_sub_blocks(int B, int n_hyp)
+{
+    return (B <= 0 || n_hyp <= 0) ? 0 : backward_sub_blocks(B, n_hyp);
+}
+
 int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                int B, int Ho, int Wo,
                                float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
@@ -1044,71 +1213,23 @@ int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                uint32_t max_tries, void *stream, double *rec_dev)
 {
-    if (!coords_dev || !grad_dev || !gt_poses_dev || !out_loss_dev || B <= 0 || Ho <= 0 || Wo <= 0 || n_hyp <= 0 ||
-        sub <= 0 || max_tries == 0)
-        return XL_ERR_ARG;
-    const int N = Ho * Wo;
-    if (N > kMaxCells) return XL_ERR_GRID;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nh = (size_t)B * n_hyp;
+    return backward_rgb_launch<false>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev,
+                                      out_loss_dev, nullptr, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans, soft_clamp, alpha,
+                                      max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream, rec_dev);
+}
 
-    // workspace: every hypothesis' pose, score and sampled cells; per-hypothesis records and inlier masks
-    int S = 1;
-    while (S * 2 * kWaves <= n_hyp && (long long)B * S * 2 <= 1024) S *= 2;
-    const size_t bPoses = sizeof(double) * nh * 12, bScores = sizeof(double) * nh, bCells = sizeof(int32_t) * nh * 4;
-    const size_t bRec = rec_dev ? 0 : sizeof(double) * nh * kRec, bMasks = sizeof(unsigned long long) * nh * kThreads;
-    const size_t bPart = sizeof(double) * ((size_t)B * S * kWaves * 16 + (size_t)B * 12);
-    auto up = [](size_t v) { return (v + 255) & ~size_t(255); };
-    unsigned char *ws = nullptr;
-    XL_HIP(hipMallocAsync((void **)&ws, up(bPoses) + up(bScores) + up(bCells) + up(bRec) + up(bMasks) + up(bPart), st));
-    unsigned char *cur = ws;
-    double *hypPoses = (double *)cur; cur += up(bPoses);
-    double *scores = (double *)cur; cur += up(bScores);
-    int32_t *cells = (int32_t *)cur; cur += up(bCells);
-    double *rec = rec_dev ? rec_dev : (double *)cur; cur += up(bRec);
-    unsigned long long *masks = (unsigned long long *)cur; cur += up(bMasks);
-    double *part = (double *)cur;
-
-    Params P;
-    P.coords = coords_dev; P.sb = sb; P.sc = sc; P.sy = sy; P.sx = sx;
-    P.outPoses = nullptr; P.focals = focals_dev;
-    P.cells = cells; P.tries = nullptr; P.scores = scores; P.dbg = nullptr; P.hypPoses = hypPoses;
-    P.seed = seed; P.image0 = image0; P.imageStride = image_stride; P.maxTries = max_tries;
-    P.nHyp = n_hyp; P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = (N + 3) & ~3;
-    P.thr = thr; P.focal = focal; P.ppx = ppx; P.ppy = ppy; P.alpha = alpha; P.maxReproj = max_reproj;
-    P.part = part; P.S = S;
-    P.pairCells = 1; P.cellWalk = 1;
-    P.mask = nullptr; P.status = nullptr;
-    BwdParams Q;
-    Q.coords = coords_dev; Q.sb = sb; Q.sc = sc; Q.sy = sy; Q.sx = sx;
-    Q.grad = grad_dev; Q.gsb = gsb; Q.gsc = gsc; Q.gsy = gsy; Q.gsx = gsx;
-    Q.gt = gt_poses_dev; Q.focals = focals_dev;
-    Q.hypPoses = hypPoses; Q.scores = scores; Q.cells = cells; Q.rec = rec; Q.masks = masks; Q.outLoss = out_loss_dev;
-    Q.nHyp = n_hyp; Q.Ho = Ho; Q.Wo = Wo; Q.sub = sub; Q.Npad = P.Npad;
-    Q.thr = thr; Q.focal = focal; Q.ppx = ppx; Q.ppy = ppy; Q.alpha = alpha; Q.maxReproj = max_reproj;
-    Q.wRot = w_rot; Q.wTrans = w_trans; Q.softClamp = soft_clamp;
-
-    size_t lds = ((sizeof(Smem) + 15) & ~size_t(15)) + (size_t)3 * P.Npad * sizeof(float);
-    if (lds > 160 * 1024) { (void)hipFreeAsync(ws, st); return XL_ERR_GRID; }
-    static XlLdsLimit configured;
-    int cfgDev;
-    if (configured.needs(lds, &cfgDev)) {
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_hyp_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_score_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        configured.done(lds, cfgDev);
-    }
-    hipLaunchKernelGGL(xl_dsac_forward_kernel<1>, dim3(S, B), dim3(kThreads), lds, st, P);
-    hipLaunchKernelGGL(xl_dsac_bwd_hyp_kernel, dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
-    hipLaunchKernelGGL(xl_dsac_bwd_expect_kernel, dim3(B), dim3(kThreads), 0, st, Q);
-    hipLaunchKernelGGL(xl_dsac_bwd_score_kernel, dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
-    hipLaunchKernelGGL(xl_dsac_bwd_assemble_kernel, dim3((N + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, Q);
-    XL_HIP(hipFreeAsync(ws, st));
-    XL_HIP(hipGetLastError());
-    return XL_OK;
+int xl_dsac_backward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                      int B, int Ho, int Wo, const uint8_t *mask_dev,
+                                      float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                                      const float *gt_poses_dev, double *out_loss_dev, int32_t *status_dev,
+                                      int n_hyp, float thr, float focal, float ppx, float ppy,
+                                      float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
+                                      const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
+                                      uint32_t max_tries, void *stream, double *rec_dev)
+{
+    return backward_rgb_launch<true>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev,
+                                     out_loss_dev, status_dev, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans, soft_clamp, alpha,
+                                     max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream, rec_dev);
 }
 
 int xl_dsac_forward_rgbd(void) { return XL_ERR_UNSUPPORTED; }

@@ -16,7 +16,9 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
   * `forward_rgb_masked_batch` is forward_rgb_batch over a per-cell validity mask (uint8 / bool [B,Ho,Wo], nonzero = usable; build
     one with crossloc_amd.evaluation.cell_mask): masked-out cells are never sampled, scored or counted as inliers, and what is
     stored there cannot influence the result.  It returns a status per image (1: fewer than four usable cells, identity pose).
-    The mask reaches the solver only: not the quality / refinement passes, the backward passes, the RGB-D solver or forward_rgb.
+    `backward_rgb_masked_batch` is backward_rgb_batch over the same mask: masked-out cells are no evidence and get no gradient.
+    The mask reaches these two only: not the quality / refinement passes, the RGB-D solver and its backward pass, forward_rgb or
+    backward_rgb.
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
     form `backward_rgb_batch` run on the GPU as well.
   * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
@@ -74,6 +76,24 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _check_mask(fn, sceneCoordinates, mask, out, out_name):
+    """The mask checks of the masked entry points (`out`: the tensor the call writes next to it), before any device work: uint8 or
+    bool, [B,Ho,Wo] contiguous CUDA on the device of sceneCoordinates.  Returns the mask as uint8 (a bool mask is viewed)."""
+    if not isinstance(mask, torch.Tensor) or not isinstance(out, torch.Tensor):
+        raise RuntimeError("mask and %s must be torch.Tensors" % out_name)
+    if not sceneCoordinates.is_cuda or not out.is_cuda or not mask.is_cuda:
+        raise RuntimeError("%s needs CUDA(HIP) tensors; there is no CPU fallback" % fn)
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise RuntimeError("mask must be uint8 or bool, got %s" % str(mask.dtype).replace("torch.", ""))
+    if tuple(mask.shape) != (B, Ho, Wo) or not mask.is_contiguous():
+        raise RuntimeError("mask must be a contiguous [B,Ho,Wo] tensor like sceneCoordinates, got %s" % (tuple(mask.shape),))
+    if mask.device != dev or out.device != dev:
+        raise RuntimeError("mask and %s must be on the device of sceneCoordinates" % out_name)
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 def forward_rgb_batch(sceneCoordinates, outPoses, ransacHypotheses, inlierThreshold, focalLength, ppointX,
                       ppointY, inlierAlpha, maxReproj, subSampling, image0=0, image_stride=1, focals=None,
                       seed=None, max_tries=None, debug=False):
@@ -124,27 +144,16 @@ def forward_rgb_masked_batch(sceneCoordinates, mask, outPoses, ransacHypotheses,
     forward_rgb_batch's bit for bit.  An image with fewer than four usable cells gets the 4x4 identity and status 1 (with
     debug: tries 0, scores 0, cells -1, winner -1).  Returns status, int32 [B] on the device (asynchronous on the current stream);
     with debug=True the debug dict of forward_rgb_batch with `status` in it.  Shape, dtype and device mismatches raise
-    RuntimeError before any device work.  The quality and refinement passes, the backward passes, the RGB-D solver and the
-    single-image forward_rgb take no mask."""
+    RuntimeError before any device work.  The backward pass over the same mask is backward_rgb_masked_batch; the quality and
+    refinement passes, the RGB-D solver and its backward pass and the single-image forward_rgb take no mask."""
     _check_coords(sceneCoordinates, True)
-    if not isinstance(mask, torch.Tensor) or not isinstance(outPoses, torch.Tensor):
-        raise RuntimeError("mask and outPoses must be torch.Tensors")
-    if not sceneCoordinates.is_cuda or not outPoses.is_cuda or not mask.is_cuda:
-        raise RuntimeError("forward_rgb_masked_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+    mask = _check_mask("forward_rgb_masked_batch", sceneCoordinates, mask, outPoses, "outPoses")
     B, _, Ho, Wo = sceneCoordinates.shape
     dev = sceneCoordinates.device
-    if mask.dtype not in (torch.uint8, torch.bool):
-        raise RuntimeError("mask must be uint8 or bool, got %s" % str(mask.dtype).replace("torch.", ""))
-    if tuple(mask.shape) != (B, Ho, Wo) or not mask.is_contiguous():
-        raise RuntimeError("mask must be a contiguous [B,Ho,Wo] tensor like sceneCoordinates, got %s" % (tuple(mask.shape),))
-    if mask.device != dev or outPoses.device != dev:
-        raise RuntimeError("mask and outPoses must be on the device of sceneCoordinates")
     if outPoses.dtype != torch.float32 or tuple(outPoses.shape) != (B, 4, 4) or not outPoses.is_contiguous():
         raise RuntimeError("outPoses must be a contiguous float32 [B,4,4] tensor")
     if int(ransacHypotheses) <= 0:
         raise RuntimeError("ransacHypotheses must be positive")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
     if focals is not None:
         focals = focals.to(device=dev, dtype=torch.float32).contiguous()
         if focals.numel() != B:
@@ -350,6 +359,48 @@ def backward_rgb_batch(sceneCoordinates, outSceneCoordinatesGrad, gtPoses, ransa
             int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream), _ptr(rec))
     _lib.check(rc)
     return (loss, rec) if debug else loss
+
+
+def backward_rgb_masked_batch(sceneCoordinates, mask, outSceneCoordinatesGrad, gtPoses, ransacHypotheses, inlierThreshold,
+                              focalLength, ppointX, ppointY, wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj,
+                              subSampling, randomSeed, image0=0, image_stride=1, focals=None, max_tries=None, debug=False):
+    """backward_rgb_batch over the cells `mask` admits (mask: as in forward_rgb_masked_batch, the other arguments as in
+    backward_rgb_batch): the hypotheses, scores and soft-max distribution are the masked forward solver's, every hypothesis is
+    refined over usable cells only, the score path sums usable cells only, and the gradient at a masked-out cell keeps the
+    caller's incoming value bit for bit.  The values stored at masked-out cells (NaN and Inf included) influence no bit of loss,
+    record or gradient, and with an all-ones mask all three are backward_rgb_batch's.  An image with fewer than four usable cells
+    gets loss 0.0, status 1, zero records and an untouched gradient.  Returns (losses float64 [B], status int32 [B]) on the device
+    (asynchronous on the current stream); with debug=True (losses, rec, status).  Shape, dtype and device mismatches raise
+    RuntimeError before any device work."""
+    _check_coords(sceneCoordinates, True)
+    g = outSceneCoordinatesGrad
+    mask = _check_mask("backward_rgb_masked_batch", sceneCoordinates, mask, g, "outSceneCoordinatesGrad")
+    if g.dtype != torch.float32 or tuple(g.shape) != tuple(sceneCoordinates.shape):
+        raise RuntimeError("outSceneCoordinatesGrad must be float32 with the shape of sceneCoordinates")
+    if int(ransacHypotheses) <= 0:
+        raise RuntimeError("ransacHypotheses must be positive")
+    B, _, Ho, Wo = sceneCoordinates.shape
+    dev = sceneCoordinates.device
+    gt = gtPoses.to(device=dev, dtype=torch.float32).reshape(B, 16).contiguous()
+    if focals is not None:
+        focals = focals.to(device=dev, dtype=torch.float32).contiguous()
+        if focals.numel() != B:
+            raise RuntimeError("expected %d focal lengths, got %d" % (B, focals.numel()))
+    loss = torch.zeros((B,), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)                     # (the first backward kernel writes every entry)
+    rec = torch.zeros((B, ransacHypotheses, BWD_REC), dtype=torch.float64, device=dev) if debug else None
+    sb, sc, sy, sx = sceneCoordinates.stride()
+    gb, gc, gy, gx = g.stride()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _lib.lib().xl_dsac_backward_rgb_masked_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), _ptr(g), gb, gc, gy, gx, _ptr(gt), _ptr(loss),
+            _ptr(status), int(ransacHypotheses), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY),
+            float(wLossRot), float(wLossTrans), float(softClamp), float(inlierAlpha), float(maxReproj),
+            int(subSampling), _ptr(focals), int(randomSeed), int(image0), int(image_stride),
+            int(MAX_HYPOTHESES_TRIES if max_tries is None else max_tries), ctypes.c_void_p(stream), _ptr(rec))
+    _lib.check(rc)
+    return (loss, rec, status) if debug else (loss, status)
 
 
 def backward_rgb(sceneCoordinates, outSceneCoordinatesGrad, gtPose, ransacHypotheses, inlierThreshold, focalLength,

@@ -20,7 +20,9 @@ does not); its depth label rotates like any label map (fill -1: nothing measured
 what an in-plane rotation leaves unchanged.  --aug_canvas: fixed-size augmentation (CamLocDataset(canvas=True),
 data.batch_canvas) - every frame draws its own scale and, with --aug_rotation DEG, its own angle (at 0: scale only), and is
 warped onto a canvas of its own size; the solver and the --init_weight coord term read one focal length per frame.  The
-label grid stays 60 x 90, so --mode rgbd keeps the scale range 2/3 - 3/2 with it.
+label grid stays 60 x 90, so --mode rgbd keeps the scale range 2/3 - 3/2 with it.  --mask labels (--mode rgb): the cells whose
+coord label is the scene's nodata value - sky, water, the empty border --aug_canvas and --aug_rotation leave around a warped
+frame - are masked out of the solver's backward pass, as --mode rgbd drops depth holes by itself.
 
 See crossloc_amd/training.py (make_e2e_step, Trainer) and loss.expected_pose_loss_and_output_gradient.
 """
@@ -47,6 +49,9 @@ def _parser():
                    help='weight of the coord loss kept in the step (0: the pose loss alone)')
     p.add_argument('--aug_rotation', type=float, default=0.0, metavar='DEG',
                    help='rotate each frame by its own angle in +-DEG, and its ground-truth pose with it (0: no rotation)')
+    p.add_argument('--mask', type=str, default='none', choices=('none', 'labels'),
+                   help='labels: cells whose coord label is nodata (sky, water, the empty border of a warped frame) are no '
+                        'evidence for the solver and get no pose gradient (--mode rgb)')
     p.add_argument('--seed', type=int, default=RANSAC_SEED, help="the sampler's seed; step k draws with seed + k")
     return p
 
@@ -62,6 +67,8 @@ def _config_parser(argv=None):
         p.error("--fullsize: the solver works on the 8x subsampled grid")
     if opt.aug_rotation < 0:
         p.error("--aug_rotation is the half width of the angle range: it cannot be negative")
+    if opt.mask == 'labels' and opt.mode == 'rgbd':
+        p.error("--mask labels is for --mode rgb: the RGB-D solver drops depth holes itself and takes no mask")
     if opt.real_only:
         assert opt.sim_data_chunk == 0
     return opt
@@ -96,6 +103,8 @@ def get_output_path(opt):
         b += '-rot{:g}'.format(opt.aug_rotation)
     if opt.aug_canvas:
         b += '-canvas'
+    if opt.mask != 'none':
+        b += '-mask' + opt.mask
     if opt.tiny:
         b += '-tiny'
     if opt.debug:

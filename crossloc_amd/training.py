@@ -204,8 +204,14 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
     rgbd, 'depth') -> (mean expected pose loss, summary row of loss.E2E_SUMMARY_FIELDS), device tensors; nothing
     synchronises.  Forward, [the coord loss's output gradient times opt.init_weight,] the solver's backward pass and the
     finishing op added onto it, backward, gradient all-reduce, fused Adam.  `opt`: the options of train_e2e.py.  With
-    opt.aug_canvas the frames carry their own scale: the coord term then reads one focal length per frame."""
+    opt.aug_canvas the frames carry their own scale: the coord term then reads one focal length per frame.  With
+    opt.mask == 'labels' (--mode rgb) every step builds evaluation.cell_mask from its coord labels: the cells whose label is the
+    scene's nodata value - sky, water, the empty border of a warped frame - are no evidence for the solver and get no pose
+    gradient (dsacstar.backward_rgb_masked_batch)"""
     rgbd = opt.mode == 'rgbd'
+    label_mask = getattr(opt, 'mask', 'none') == 'labels'
+    if label_mask and rgbd:
+        raise RuntimeError("--mask labels is for --mode rgb: the RGB-D solver drops depth holes itself and takes no mask")
     canvas = bool(getattr(opt, 'aug_canvas', False))
     joint = opt.init_weight > 0
     sub = network.OUTPUT_SUBSAMPLE
@@ -228,12 +234,16 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
             beta = opt.init_weight
         # the depth label is -1 where nothing was measured; the RGB-D solver takes 0 for that
         depth = gt_labels['depth'][:, 0].clamp_min(0.0) if rgbd else None
+        mask = None
+        if label_mask:
+            from .evaluation import cell_mask
+            mask = cell_mask(labels=gt_labels['coord'] if isinstance(gt_labels, dict) else gt_labels, nodata_value=nodata_value)
         seed, image0 = e2e_keys(opt.seed, (image0,), step_index)     # image0: the first frame's dataset index
         loss, stats, grad = xl_loss.expected_pose_loss_and_output_gradient(
             predictions, gt_poses, focals, image_h, image_w, opt.hypotheses, opt.threshold, opt.inlieralpha,
             opt.maxpixelerror, opt.weightrot, opt.weighttrans, opt.softclamp, seed, image0=image0,
             clip_norm=opt.clip_norm, weight=1.0, grad=grad, beta=beta, depth=depth, rgbd_threshold=opt.threshold,
-            max_dist_error=opt.maxpixelerror, subsample=sub)
+            max_dist_error=opt.maxpixelerror, subsample=sub, mask=mask)
         predictions.backward(grad)
         if world_size > 1:
             allreduce_flat_gradients(network, world_size, group, host_reduce)

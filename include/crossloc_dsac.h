@@ -93,7 +93,8 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
  * Identity B: the values stored at masked-out cells influence no output bit.
  *
  * XL_ERR_ARG for a null mask and for everything xl_dsac_forward_rgb_batch refuses, before any HIP call.  Not covered: the
- * quality and refinement passes, the backward passes, the RGB-D solver and the single-image host entry point take no mask.
+ * quality and refinement passes, the RGB-D solver and its backward pass and the single-image host entry point take no mask
+ * (the RGB backward pass does: xl_dsac_backward_rgb_masked_batch).
  */
 int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                      int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
@@ -142,6 +143,43 @@ int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
                                const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                uint32_t max_tries, void *stream, double *rec_dev);
+
+/* sub-blocks per image of the backward passes' sample + score launch (0 for a non-positive argument); the results do not depend on it */
+int xl_dsac_backward_sub_blocks(int B, int n_hyp);
+
+/*
+ * xl_dsac_backward_rgb_batch over the per-cell validity mask of xl_dsac_forward_rgb_masked_batch: the same five launches in
+ * template instantiations of their own, the same arguments, plus
+ *
+ *   mask_dev       [B,Ho,Wo] uint8, contiguous: nonzero = the cell is usable
+ *   status_dev     optional [B] int32: 0, or 1 for an image with fewer than four usable cells
+ *
+ * sample, score   the masked forward solver's (above): the hypotheses, their scores and so the soft-max distribution are the
+ *                 ones xl_dsac_forward_rgb_masked_batch chooses from.
+ * refine (K1)     a cell is an inlier iff it is usable and below thr, so path I runs over usable cells only.
+ * path II (K3)    g6 = sum_c dRepro(c) J_init(c) runs over the usable cells; a masked-out cell's term is selected away, never
+ *                 multiplied by zero.  A hypothesis whose tries ran out on a mask-rejected try (identity pose, the last
+ *                 draws) carries masked-out cells: their coordinates are not read, the perturbed P3P solves are skipped and
+ *                 its dPNP is the zero of a failed solve (rec [30..41] and [43] are 0).
+ * assemble (K4)   the gradient of a masked-out cell is neither read nor written; its coordinates are not read.
+ * dead image      fewer than four usable cells: out_loss 0, status 1, grad untouched, and with rec_dev the image's records
+ *                 all zero.
+ *
+ * Identity A: with an all-ones mask loss, records and gradient equal xl_dsac_backward_rgb_batch's bit for bit.
+ * Identity B: the values stored at masked-out cells influence no bit of loss, record or gradient.
+ * Identity C: the gradient at a masked-out cell is the caller's incoming value, bit for bit.
+ *
+ * XL_ERR_ARG for a null mask and for everything xl_dsac_backward_rgb_batch refuses, XL_ERR_GRID for a grid whose planes fit
+ * in 160 KB only without the bit plane; both before any HIP call.  Not covered: the RGB-D backward pass takes no mask.
+ */
+int xl_dsac_backward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                      int B, int Ho, int Wo, const uint8_t *mask_dev,
+                                      float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                                      const float *gt_poses_dev, double *out_loss_dev, int32_t *status_dev,
+                                      int n_hyp, float thr, float focal, float ppx, float ppy,
+                                      float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
+                                      const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
+                                      uint32_t max_tries, void *stream, double *rec_dev);
 
 /*
  * Per-frame pose quality (no reference counterpart): how far the pose of an image can be trusted.  A stand-alone pass over
