@@ -79,9 +79,16 @@ def lib():
         L.xl_dsac_pose_quality_batch.restype = c_i32
         L.xl_dsac_pose_quality_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
                                                  c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_vp]
+        L.xl_dsac_pose_quality_masked_batch.restype = c_i32
+        L.xl_dsac_pose_quality_masked_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp,
+                                                        c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_vp, c_vp]
         L.xl_dsac_refine_pose_batch.restype = c_i32
         L.xl_dsac_refine_pose_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
                                                 c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_f, c_i32, c_vp]
+        L.xl_dsac_refine_pose_masked_batch.restype = c_i32
+        L.xl_dsac_refine_pose_masked_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                                       c_i32, c_i32, c_i32, c_vp,
+                                                       c_vp, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp, c_f, c_i32, c_vp]
         # where an RGB-D image comes from (coords, camera tensor, depth with their strides; B, Ho, Wo) and the intrinsics tail
         # (focal, ppx, ppy, sub, focals): the same in the three entry points
         rgbd_in = [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32]

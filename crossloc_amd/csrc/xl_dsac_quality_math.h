@@ -26,6 +26,7 @@
 #define XLQ_S_ERR2 31                  /* sum of e^2 over the inliers */
 
 #define XLQ_ROW 64                     /* doubles per output row; layout: include/crossloc_dsac.h */
+#define XLQ_COL_N_MASKED 58            /* masked passes: the cells the mask ruled out (0.0 in the unmasked row) */
 #define XLQ_STATUS_OK 0.0
 #define XLQ_STATUS_FEW_INLIERS 1.0     /* fewer than 4 inliers */
 #define XLQ_STATUS_NOT_PD 2.0          /* JtJ is not positive definite */
@@ -213,6 +214,14 @@ XL_MATH_CALL_FN void quality_row(const double *s, const Pose *pose, const Cam *c
             for (int c = r; c < 6; ++c) row[31 + k++] = S[6 * r + c];
     }
     quality_center_tail(S, pose, row);
+}
+
+/* the masked passes' one change to a finished row (quality_row: col XLQ_COL_N_MASKED, refine_row: XLR_COL_N_MASKED): the
+ * number of masked-out cells in place of the unmasked row's 0.0; with status 3 the column stays NaN like its neighbours
+ * (both rows keep their status in [6], and XLR_STATUS_BAD_POSE == XLQ_STATUS_BAD_POSE) */
+XL_MATH_FN void quality_row_n_masked(double *row, int col, double nMasked)
+{
+    if (row[6] != XLQ_STATUS_BAD_POSE) row[col] = nMasked;
 }
 
 #endif  /* XL_DSAC_QUALITY_MATH_H */

@@ -19,6 +19,13 @@
 // broadcasts.  Every loop is bounded by a constant or by max_rounds.  Arithmetic contract as in xl_dsac.hip:
 // -ffp-contract=off, fixed reduction order; tests/pose_refine_ref.c compiles the same header with gcc and restates this file's
 // orchestration serially, and tests/test_pose_refine_gpu.py compares poses and rows bit for bit.
+//
+// MASKED (xl_dsac_refine_pose_masked_batch): the same pass over the cells a per-cell validity mask admits, the masked solver's
+// rules carried over.  The LDS holds no fifth plane (the exported cell limit stays): thread tid reads its own mask bytes once
+// into a 64-bit word `usable` in the layout of its inlier word (bit j <-> cell tid + 256 j).  A masked-out cell is not staged,
+// and the marking loop of every round passes it by before the sigma check and before cell_err, so it is neither an unusable
+// sigma nor an inlier; the evaluations walk the inlier word and need nothing more.  The count of masked-out cells rides the
+// round's block sum in its free fourth slot.  The unmasked instantiation is the kernel as it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -58,6 +65,7 @@ struct RefineParams {
     double *w2c;                                  // optional [B][12]
     int Ho, Wo, sub, Npad, maxRounds;
     float thr, focal, ppx, ppy, maxReproj, s0;
+    const uint8_t *mask;                          // masked pass: [B][Ho*Wo], nonzero = usable cell
 };
 
 struct Planes { const float *x, *y, *z, *s; };
@@ -76,6 +84,7 @@ __device__ __forceinline__ void normal_eq_thread(const Planes &pl, const Cam &ca
     }
 }
 
+template <bool MASKED = false>
 __global__ __launch_bounds__(kThreads)
 void xl_dsac_refine_kernel(RefineParams P)
 {
@@ -107,14 +116,31 @@ void xl_dsac_refine_kernel(RefineParams P)
 #pragma unroll
     for (int k = 0; k < 28; ++k) neOut[k] = 0.0;
     double n0 = 0.0, bad = 0.0, cost0 = 0.0, nLast = 0.0;
+    double nMasked = 0.0;                                       // masked: the cells the mask ruled out
     int rounds = 0, evals = 0, converged = 0;
 
     if (poseOk) {
+        // ---- masked: this thread's slice of the mask, bit j <-> cell tid + 256 j, and how many of its cells are ruled out
+        unsigned long long usable = ~0ull;
+        double myMasked = 0.0;
+        if constexpr (MASKED) {
+            const uint8_t *gm = P.mask + (int64_t)b * N;
+            usable = 0ull;
+            int j = 0;
+            for (int i = tid; i < N; i += kThreads, ++j) {
+                if (gm[i] != 0) usable |= (1ull << j);
+                else myMasked += 1.0;
+            }
+        }
         // ---- stage the four planes (a NULL sigma map is staged as zeros; its values are never used: every weight is 1)
         {
             const float *g = P.coords + (int64_t)b * P.sb;
             const float *gs = hasSigma ? P.sigma + (int64_t)b * P.gb : nullptr;
-            for (int i = tid; i < N; i += kThreads) {
+            int j = 0;
+            for (int i = tid; i < N; i += kThreads, ++j) {
+                if constexpr (MASKED) {
+                    if (!((usable >> j) & 1ull)) continue;      // not read; its LDS slots are never read either
+                }
                 const int y = i / P.Wo, x = i - y * P.Wo;
                 const float *q = g + (int64_t)y * P.sy + (int64_t)x * P.sx;
                 sCo[i] = q[0];
@@ -135,6 +161,9 @@ void xl_dsac_refine_kernel(RefineParams P)
             {
                 int j = 0;
                 for (int i = tid; i < N; i += kThreads, ++j) {
+                    if constexpr (MASKED) {
+                        if (!((usable >> j) & 1ull)) continue;
+                    }
                     if (hasSigma && refine_sigma_bad((double)pl.s[i])) { c4[1] += 1.0; continue; }
                     const int y = i / cam.Wo, x = i - y * cam.Wo;
                     const float e = cell_err(&pose, (double)pl.x[i], (double)pl.y[i], (double)pl.z[i], y, x, &cam);
@@ -143,6 +172,7 @@ void xl_dsac_refine_kernel(RefineParams P)
             }
             c4[0] = (double)__popcll(inl);
             c4[2] = (inl != prevInl) ? 1.0 : 0.0;       // the OR over the workgroup, as a sum of flags
+            if constexpr (MASKED) c4[3] = myMasked;
             block_sum(c4, S.red[redSel], wave, lane); redSel ^= 1;
             const double cnt = c4[0];
             if (r > 0 && c4[2] == 0.0) { converged = 1; break; }
@@ -156,6 +186,7 @@ void xl_dsac_refine_kernel(RefineParams P)
             block_sum(ne, S.red[redSel], wave, lane); redSel ^= 1; ++evals;
             if (r == 0) {
                 n0 = cnt; bad = c4[1]; cost0 = ne[27]; nLast = cnt;
+                if constexpr (MASKED) nMasked = c4[3];
 #pragma unroll
                 for (int k = 0; k < 28; ++k) neOut[k] = ne[k];
                 if (cnt < 4.0) { status = XLR_STATUS_FEW_INLIERS; break; }
@@ -202,6 +233,7 @@ void xl_dsac_refine_kernel(RefineParams P)
     if (tid != 0) return;
     double row[XLR_ROW];
     refine_row(status, &cam, n0, bad, cost0, nLast, neOut, rounds, evals, converged, &poseIn, &pose, row);
+    if constexpr (MASKED) quality_row_n_masked(row, XLR_COL_N_MASKED, nMasked);
     double *o = P.rows + (int64_t)b * XLR_ROW;
     for (int i = 0; i < XLR_ROW; ++i) o[i] = row[i];
     float *op = P.outPoses + (int64_t)b * 16;
@@ -219,16 +251,18 @@ void xl_dsac_refine_kernel(RefineParams P)
     }
 }
 
-}  // namespace
-
-extern "C" int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
-                                         const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
-                                         int B, int Ho, int Wo, const float *poses_dev, float *out_poses_dev,
-                                         double *rows_dev, double *w2c_dev,
-                                         float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
-                                         const float *focals_dev, float s0, int max_rounds, void *stream)
+// the launch of both entry points: MASKED adds the mask and launches the masked instantiation (which keeps an LDS limit of its
+// own).  Everything is validated before the first HIP call.
+template <bool MASKED>
+int refine_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                  const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                  int B, int Ho, int Wo, const uint8_t *mask_dev, const float *poses_dev, float *out_poses_dev,
+                  double *rows_dev, double *w2c_dev,
+                  float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
+                  const float *focals_dev, float s0, int max_rounds, void *stream)
 {
     if (!coords_dev || !poses_dev || !out_poses_dev || !rows_dev || B <= 0 || Ho <= 0 || Wo <= 0 || sub <= 0) return XL_ERR_ARG;
+    if (MASKED && !mask_dev) return XL_ERR_ARG;
     if (!(s0 > 0.0f) || max_rounds < 1 || max_rounds > XL_DSAC_REFINE_MAX_ROUNDS) return XL_ERR_ARG;
     if ((int64_t)Ho * (int64_t)Wo > (int64_t)XL_DSAC_REFINE_MAX_CELLS) return XL_ERR_GRID;
     const int N = Ho * Wo;
@@ -238,11 +272,36 @@ extern "C" int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, in
     P.poses = poses_dev; P.focals = focals_dev; P.outPoses = out_poses_dev; P.rows = rows_dev; P.w2c = w2c_dev;
     P.Ho = Ho; P.Wo = Wo; P.sub = sub; P.Npad = (N + 3) & ~3; P.maxRounds = max_rounds;
     P.thr = thr; P.focal = focal; P.ppx = ppx; P.ppy = ppy; P.maxReproj = max_reproj; P.s0 = s0;
+    P.mask = mask_dev;
 
     const size_t lds = kSmemBytes + (size_t)4 * P.Npad * sizeof(float);
     if (lds > kLdsLimit) return XL_ERR_GRID;
     static XlLdsLimit configured;
-    if (configured.configure(reinterpret_cast<const void *>(xl_dsac_refine_kernel), lds) != XL_OK) return XL_ERR_HIP;
-    hipLaunchKernelGGL(xl_dsac_refine_kernel, dim3(B), dim3(kThreads), lds, (hipStream_t)stream, P);
+    if (configured.configure(reinterpret_cast<const void *>(xl_dsac_refine_kernel<MASKED>), lds) != XL_OK) return XL_ERR_HIP;
+    hipLaunchKernelGGL((xl_dsac_refine_kernel<MASKED>), dim3(B), dim3(kThreads), lds, (hipStream_t)stream, P);
     return hipGetLastError() == hipSuccess ? XL_OK : XL_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                         const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                                         int B, int Ho, int Wo, const float *poses_dev, float *out_poses_dev,
+                                         double *rows_dev, double *w2c_dev,
+                                         float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
+                                         const float *focals_dev, float s0, int max_rounds, void *stream)
+{
+    return refine_launch<false>(coords_dev, sb, sc, sy, sx, sigma_dev, gb, gy, gx, B, Ho, Wo, nullptr, poses_dev, out_poses_dev,
+                                rows_dev, w2c_dev, thr, focal, ppx, ppy, max_reproj, sub, focals_dev, s0, max_rounds, stream);
+}
+
+extern "C" int xl_dsac_refine_pose_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                                const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                                                int B, int Ho, int Wo, const uint8_t *mask_dev, const float *poses_dev,
+                                                float *out_poses_dev, double *rows_dev, double *w2c_dev,
+                                                float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
+                                                const float *focals_dev, float s0, int max_rounds, void *stream)
+{
+    return refine_launch<true>(coords_dev, sb, sc, sy, sx, sigma_dev, gb, gy, gx, B, Ho, Wo, mask_dev, poses_dev, out_poses_dev,
+                               rows_dev, w2c_dev, thr, focal, ppx, ppy, max_reproj, sub, focals_dev, s0, max_rounds, stream);
 }

@@ -25,6 +25,7 @@
 #include "xl_dsac_quality_math.h"
 
 #define XLR_ROW 64                     /* doubles per output row */
+#define XLR_COL_N_MASKED 63            /* masked pass: the cells the mask ruled out (quality_row_n_masked; 0.0 in the unmasked row) */
 #define XLR_MAX_ROUNDS 16              /* upper limit of the max_rounds argument */
 #define XLR_LG_RAISES 34               /* damping raises per iteration: lg climbs from >= -16 to 17 at most */
 #define XLR_STATUS_OK 0.0

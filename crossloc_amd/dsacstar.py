@@ -17,8 +17,9 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
     one with crossloc_amd.evaluation.cell_mask): masked-out cells are never sampled, scored or counted as inliers, and what is
     stored there cannot influence the result.  It returns a status per image (1: fewer than four usable cells, identity pose).
     `backward_rgb_masked_batch` is backward_rgb_batch over the same mask: masked-out cells are no evidence and get no gradient.
-    The mask reaches these two only: not the quality / refinement passes, the RGB-D solver and its backward pass, forward_rgb or
-    backward_rgb.
+    `pose_quality_masked_batch` and `refine_pose_masked_batch` carry the mask through the two passes behind the solver: a
+    masked-out cell is never read, is never an inlier and is counted in `n_masked` only.  The mask does not reach the RGB-D solver
+    and its passes, forward_rgb or backward_rgb.
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
     form `backward_rgb_batch` run on the GPU as well.
   * `forward_rgbd_batch` is the RGB-D solver (dsacstar.cpp:495-612) for B images per launch, from a camera-coordinate
@@ -144,8 +145,9 @@ def forward_rgb_masked_batch(sceneCoordinates, mask, outPoses, ransacHypotheses,
     forward_rgb_batch's bit for bit.  An image with fewer than four usable cells gets the 4x4 identity and status 1 (with
     debug: tries 0, scores 0, cells -1, winner -1).  Returns status, int32 [B] on the device (asynchronous on the current stream);
     with debug=True the debug dict of forward_rgb_batch with `status` in it.  Shape, dtype and device mismatches raise
-    RuntimeError before any device work.  The backward pass over the same mask is backward_rgb_masked_batch; the quality and
-    refinement passes, the RGB-D solver and its backward pass and the single-image forward_rgb take no mask."""
+    RuntimeError before any device work.  The backward pass over the same mask is backward_rgb_masked_batch, the passes behind
+    the solver are pose_quality_masked_batch and refine_pose_masked_batch; the RGB-D solver and its backward pass and the
+    single-image forward_rgb take no mask."""
     _check_coords(sceneCoordinates, True)
     mask = _check_mask("forward_rgb_masked_batch", sceneCoordinates, mask, outPoses, "outPoses")
     B, _, Ho, Wo = sceneCoordinates.shape
@@ -219,20 +221,18 @@ QUALITY_DOUBLES = 64                     # XL_DSAC_QUALITY_DOUBLES: doubles per 
 QUALITY_FIELDS = {
     "n_cells": 0, "n_inliers": 1, "soft_score": 2, "sum_err": 3, "sum_err2": 4, "sse": 5, "status": 6,
     "sigma_px": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
-    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58), "reserved": slice(58, 64),
+    "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58), "n_masked": 58, "reserved": slice(59, 64),
 }
 
 
-def pose_quality_batch(sceneCoordinates, poses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha, maxReproj,
-                       subSampling, focals=None):
-    """How far the poses of B images can be trusted: inlier statistics, JtJ of the reprojection residuals over the inliers
-    and the pose covariance, at the given pose of each image (usually what forward_rgb_batch wrote; enqueue this behind it
-    on the same stream).  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, any grid size), poses [B,4,4] float32 CUDA
-    contiguous cam->world; the other arguments as in forward_rgb_batch.  Returns a float64 CUDA tensor [B,64]
-    (QUALITY_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+def _pose_quality(fn, sceneCoordinates, mask, poses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha, maxReproj,
+                  subSampling, focals):
+    """pose_quality_batch (mask None) and pose_quality_masked_batch: the checks, the row tensor and the call"""
     _check_coords(sceneCoordinates, True)
+    if fn == "pose_quality_masked_batch":                                          # (a mask of None is refused there)
+        mask = _check_mask(fn, sceneCoordinates, mask, poses, "poses")
     if not sceneCoordinates.is_cuda or not isinstance(poses, torch.Tensor) or not poses.is_cuda:
-        raise RuntimeError("pose_quality_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+        raise RuntimeError("%s needs CUDA(HIP) tensors; there is no CPU fallback" % fn)
     B, _, Ho, Wo = sceneCoordinates.shape
     if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
         raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
@@ -244,14 +244,40 @@ def pose_quality_batch(sceneCoordinates, poses, inlierThreshold, focalLength, pp
         assert focals.numel() == B
     rows = torch.empty((B, QUALITY_DOUBLES), dtype=torch.float64, device=dev)      # (the kernel writes all 64 of every row)
     sb, sc, sy, sx = sceneCoordinates.stride()
+    tail = (_ptr(poses), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY), float(inlierAlpha),
+            float(maxReproj), int(subSampling), _ptr(focals), _ptr(rows))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = _lib.lib().xl_dsac_pose_quality_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(poses), float(inlierThreshold), float(focalLength),
-            float(ppointX), float(ppointY), float(inlierAlpha), float(maxReproj), int(subSampling), _ptr(focals),
-            _ptr(rows), ctypes.c_void_p(stream))
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if mask is None:
+            rc = _lib.lib().xl_dsac_pose_quality_batch(_ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, *tail, stream)
+        else:
+            rc = _lib.lib().xl_dsac_pose_quality_masked_batch(_ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), *tail,
+                                                              stream)
     _lib.check(rc)
     return rows
+
+
+def pose_quality_batch(sceneCoordinates, poses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha, maxReproj,
+                       subSampling, focals=None):
+    """How far the poses of B images can be trusted: inlier statistics, JtJ of the reprojection residuals over the inliers
+    and the pose covariance, at the given pose of each image (usually what forward_rgb_batch wrote; enqueue this behind it
+    on the same stream).  sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, any grid size), poses [B,4,4] float32 CUDA
+    contiguous cam->world; the other arguments as in forward_rgb_batch.  Returns a float64 CUDA tensor [B,64]
+    (QUALITY_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    return _pose_quality("pose_quality_batch", sceneCoordinates, None, poses, inlierThreshold, focalLength, ppointX, ppointY,
+                         inlierAlpha, maxReproj, subSampling, focals)
+
+
+def pose_quality_masked_batch(sceneCoordinates, mask, poses, inlierThreshold, focalLength, ppointX, ppointY, inlierAlpha,
+                              maxReproj, subSampling, focals=None):
+    """pose_quality_batch over the cells `mask` admits - usually behind forward_rgb_masked_batch, on the same mask.  mask: uint8
+    or bool [B,Ho,Wo] CUDA contiguous on the device of sceneCoordinates, nonzero = usable; the other arguments and the returned
+    rows as in pose_quality_batch.  A masked-out cell is not read: it is no inlier, adds nothing to `soft_score` (which sums the
+    usable cells with the same factor, like the masked solver's score) or to any other sum, and is counted in `n_masked` only;
+    `n_cells` stays Ho*Wo.  The values stored at masked-out cells (NaN and Inf included) influence no output bit, and with an
+    all-ones mask every output is pose_quality_batch's bit for bit.  Mask mismatches raise RuntimeError before any device work."""
+    return _pose_quality("pose_quality_masked_batch", sceneCoordinates, mask, poses, inlierThreshold, focalLength, ppointX,
+                         ppointY, inlierAlpha, maxReproj, subSampling, focals)
 
 
 REFINE_DOUBLES = 64                      # XL_DSAC_REFINE_DOUBLES: doubles per row of refine_pose_batch
@@ -263,23 +289,18 @@ REFINE_FIELDS = {
     "n_cells": 0, "n_inliers": 1, "n_inliers_in": 2, "cost_in": 3, "cost_out": 4, "n_bad_sigma": 5, "status": 6,
     "chi": 7, "sigma_pos_m": 8, "sigma_rot_deg": 9,
     "JtJ": slice(10, 31), "cov": slice(31, 52), "cov_center": slice(52, 58),
-    "rounds": 58, "evals": 59, "converged": 60, "moved_rot_deg": 61, "moved_pos_m": 62, "reserved": 63,
+    "rounds": 58, "evals": 59, "converged": 60, "moved_rot_deg": 61, "moved_pos_m": 62, "n_masked": 63,
 }
 
 
-def refine_pose_batch(sceneCoordinates, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY, maxReproj, subSampling,
-                      sigmaFloorPx=1.0, maxRounds=8, focals=None, outPoses=None, w2c=None):
-    """Re-fit the poses of B images over their inliers, every cell weighted by its predicted standard deviation: iteratively
-    re-weighted Levenberg-Marquardt with the weights 1 / (sigmaFloorPx^2 + (f sigma / z)^2) (model: include/crossloc_dsac.h),
-    from the given pose of each image - usually what forward_rgb_batch wrote; enqueue this behind it on the same stream.
-    sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, Ho*Wo <= REFINE_MAX_CELLS); sigma [B,Ho,Wo] float32 CUDA (any strides,
-    metres; e.g. the channel view pred[:, 3] of the network output) or None for the unweighted re-fit; poses [B,4,4] float32 CUDA
-    contiguous cam->world.  outPoses (float32 [B,4,4], may be `poses`) and w2c (float64 [B,12], the refined world->camera pose)
-    are optional CUDA contiguous outputs.  Returns (outPoses, rows): the refined poses and a float64 CUDA tensor [B,64]
-    (REFINE_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+def _refine_pose(fn, sceneCoordinates, mask, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY, maxReproj, subSampling,
+                 sigmaFloorPx, maxRounds, focals, outPoses, w2c):
+    """refine_pose_batch (mask None) and refine_pose_masked_batch: the checks, the output tensors and the call"""
     _check_coords(sceneCoordinates, True)
+    if fn == "refine_pose_masked_batch":                                           # (a mask of None is refused there)
+        mask = _check_mask(fn, sceneCoordinates, mask, poses, "poses")
     if not sceneCoordinates.is_cuda or not isinstance(poses, torch.Tensor) or not poses.is_cuda:
-        raise RuntimeError("refine_pose_batch needs CUDA(HIP) tensors; there is no CPU fallback")
+        raise RuntimeError("%s needs CUDA(HIP) tensors; there is no CPU fallback" % fn)
     B, _, Ho, Wo = sceneCoordinates.shape
     if poses.dtype != torch.float32 or tuple(poses.shape) != (B, 4, 4) or not poses.is_contiguous():
         raise RuntimeError("poses must be a contiguous float32 [B,4,4] tensor")
@@ -292,8 +313,8 @@ def refine_pose_batch(sceneCoordinates, sigma, poses, inlierThreshold, focalLeng
         if sigma.device != dev:
             raise RuntimeError("sigma must be on the device of sceneCoordinates")
     if Ho * Wo > REFINE_MAX_CELLS:
-        raise RuntimeError("refine_pose_batch stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
-                           % (Ho * Wo, REFINE_MAX_CELLS))
+        raise RuntimeError("%s stages an image in the LDS of one CU: Ho*Wo = %d cells exceed the limit of %d"
+                           % (fn, Ho * Wo, REFINE_MAX_CELLS))
     if not float(sigmaFloorPx) > 0.0:
         raise RuntimeError("sigmaFloorPx must be positive")
     if not 1 <= int(maxRounds) <= REFINE_MAX_ROUNDS:
@@ -312,14 +333,45 @@ def refine_pose_batch(sceneCoordinates, sigma, poses, inlierThreshold, focalLeng
     rows = torch.empty((B, REFINE_DOUBLES), dtype=torch.float64, device=dev)       # (the kernel writes all 64 of every row)
     sb, sc, sy, sx = sceneCoordinates.stride()
     gb, gy, gx = sigma.stride() if sigma is not None else (0, 0, 0)
+    tail = (_ptr(poses), _ptr(outPoses), _ptr(rows), _ptr(w2c), float(inlierThreshold), float(focalLength), float(ppointX),
+            float(ppointY), float(maxReproj), int(subSampling), _ptr(focals), float(sigmaFloorPx), int(maxRounds))
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-        rc = _lib.lib().xl_dsac_refine_pose_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(sigma), gb, gy, gx, B, Ho, Wo, _ptr(poses), _ptr(outPoses), _ptr(rows),
-            _ptr(w2c), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY), float(maxReproj),
-            int(subSampling), _ptr(focals), float(sigmaFloorPx), int(maxRounds), ctypes.c_void_p(stream))
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if mask is None:
+            rc = _lib.lib().xl_dsac_refine_pose_batch(_ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(sigma), gb, gy, gx, B, Ho, Wo,
+                                                      *tail, stream)
+        else:
+            rc = _lib.lib().xl_dsac_refine_pose_masked_batch(_ptr(sceneCoordinates), sb, sc, sy, sx, _ptr(sigma), gb, gy, gx,
+                                                             B, Ho, Wo, _ptr(mask), *tail, stream)
     _lib.check(rc)
     return outPoses, rows
+
+
+def refine_pose_batch(sceneCoordinates, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY, maxReproj, subSampling,
+                      sigmaFloorPx=1.0, maxRounds=8, focals=None, outPoses=None, w2c=None):
+    """Re-fit the poses of B images over their inliers, every cell weighted by its predicted standard deviation: iteratively
+    re-weighted Levenberg-Marquardt with the weights 1 / (sigmaFloorPx^2 + (f sigma / z)^2) (model: include/crossloc_dsac.h),
+    from the given pose of each image - usually what forward_rgb_batch wrote; enqueue this behind it on the same stream.
+    sceneCoordinates [B,3,Ho,Wo] float32 CUDA (any strides, Ho*Wo <= REFINE_MAX_CELLS); sigma [B,Ho,Wo] float32 CUDA (any strides,
+    metres; e.g. the channel view pred[:, 3] of the network output) or None for the unweighted re-fit; poses [B,4,4] float32 CUDA
+    contiguous cam->world.  outPoses (float32 [B,4,4], may be `poses`) and w2c (float64 [B,12], the refined world->camera pose)
+    are optional CUDA contiguous outputs.  Returns (outPoses, rows): the refined poses and a float64 CUDA tensor [B,64]
+    (REFINE_FIELDS names the columns), asynchronous on the current stream.  There is no CPU fallback."""
+    return _refine_pose("refine_pose_batch", sceneCoordinates, None, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY,
+                        maxReproj, subSampling, sigmaFloorPx, maxRounds, focals, outPoses, w2c)
+
+
+def refine_pose_masked_batch(sceneCoordinates, mask, sigma, poses, inlierThreshold, focalLength, ppointX, ppointY, maxReproj,
+                             subSampling, sigmaFloorPx=1.0, maxRounds=8, focals=None, outPoses=None, w2c=None):
+    """refine_pose_batch over the cells `mask` admits - usually behind forward_rgb_masked_batch, on the same mask.  mask: uint8 or
+    bool [B,Ho,Wo] CUDA contiguous on the device of sceneCoordinates, nonzero = usable; the other arguments and the returns as in
+    refine_pose_batch.  A masked-out cell is in no round's inlier set and neither its coordinate nor its sigma enters any
+    arithmetic: `n_bad_sigma` counts usable cells only and the masked-out cells are counted in `n_masked`.  The values stored at
+    masked-out cells (NaN and Inf included, in the coordinates and in sigma) influence no output bit, and with an all-ones mask
+    every output is refine_pose_batch's bit for bit.  An image with fewer than four usable cells has status 1 and keeps its input
+    pose bit for bit (behind the masked solver: the identity).  Mask mismatches raise RuntimeError before any device work."""
+    return _refine_pose("refine_pose_masked_batch", sceneCoordinates, mask, sigma, poses, inlierThreshold, focalLength, ppointX,
+                        ppointY, maxReproj, subSampling, sigmaFloorPx, maxRounds, focals, outPoses, w2c)
 
 
 BWD_REC = 128                            # XL_DSAC_BWD_REC: doubles per hypothesis in the debug record

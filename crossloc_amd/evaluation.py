@@ -273,16 +273,36 @@ def cell_mask(sigma=None, max_sigma=None, class_map=None, exclude_classes=(), la
     return out.to(torch.uint8).contiguous()
 
 
+# the passes behind the masked RGB solver, over the mask it read (dsacstar.refine_pose_masked_batch: the plain re-fit over the
+# inliers and the sigma-weighted one; dsacstar.pose_quality_masked_batch)
+MASKED_REFINE_MODES = ("masked_inliers", "masked_sigma")
+
+
+def _is_masked_quality(quality):
+    return isinstance(quality, str) and quality == "masked"
+
+
 def _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine):
-    """The mask reaches the RGB solver only.  -> whether the masked solver runs"""
+    """The mask reaches the RGB solver and, through the masked modes, the two passes behind it.  -> whether the masked solver
+    runs"""
+    asked = [("quality", quality)] if _is_masked_quality(quality) else []
+    if isinstance(refine, str) and refine in MASKED_REFINE_MODES:
+        asked.append(("refine", refine))
     if mask is None and mask_max_sigma is None:
+        for name, mode in asked:
+            raise RuntimeError("%s=%r runs behind the masked RGB solver: it needs mask= or mask_max_sigma=" % (name, mode))
         return False
     if mask is not None and mask_max_sigma is not None:
         raise RuntimeError("mask and mask_max_sigma: pass one of them (AND a mask of your own with cell_mask(sigma=...))")
-    for name, on in (("depth", depth is not None), ("cam_coords", cam_coords is not None), ("quality", bool(quality)),
-                     ("refine", bool(refine))):
+    for name, on in (("depth", depth is not None), ("cam_coords", cam_coords is not None)):
         if on:
-            raise RuntimeError("mask together with %s is not yet supported: the mask reaches the RGB solver only" % name)
+            raise RuntimeError("mask together with %s is not supported: the mask reaches the RGB solver and its passes only" % name)
+    if quality and not _is_masked_quality(quality):
+        raise RuntimeError("mask together with quality=%r: that pass reads every cell; the pass over the mask is "
+                           "quality=\"masked\"" % (quality,))
+    if refine and not (isinstance(refine, str) and refine in MASKED_REFINE_MODES):
+        raise RuntimeError("mask together with refine=%r: that pass reads every cell; the passes over the mask are "
+                           "refine=\"masked_inliers\" and refine=\"masked_sigma\"" % (refine,))
     return True
 
 
@@ -300,24 +320,29 @@ def _is_rgbd_quality(quality):
 
 
 def _check_quality_mode(quality, depth, cam_coords):
-    """`quality`: False, True (the reprojection pass) or "rgbd" (the 3-D pass, which needs the RGB-D solver's inputs)"""
-    if isinstance(quality, str) and quality != "rgbd":
-        raise RuntimeError("quality must be False, True or \"rgbd\", got %r" % (quality,))
+    """`quality`: False, True (the reprojection pass), "rgbd" (the 3-D pass, which needs the RGB-D solver's inputs) or "masked"
+    (the reprojection pass over the solver's mask; _check_mask_mode has seen to the mask)"""
+    if isinstance(quality, str) and quality not in ("rgbd", "masked"):
+        raise RuntimeError("quality must be False, True or one of \"rgbd\" and \"masked\", got %r" % (quality,))
     if _is_rgbd_quality(quality) and depth is None and cam_coords is None:
         raise RuntimeError("quality=\"rgbd\" rates the RGB-D solver's pose: it needs depth or cam_coords")
 
 
 def _check_refine_mode(refine, depth, cam_coords):
     """`refine`: False, "inliers" (unweighted re-fit over the inliers) or "sigma" (weighted by the predicted uncertainty);
-    the pass re-fits the RGB solver's pose by its reprojection residuals, so it does not go with the RGB-D solver"""
+    the pass re-fits the RGB solver's pose by its reprojection residuals, so it does not go with the RGB-D solver.
+    "masked_inliers" / "masked_sigma": the same two over the masked solver's mask (_check_mask_mode has seen to the mask)"""
     if refine is False or refine is None:
         return False
     if refine in RGBD_REFINE_MODES:
         if depth is None and cam_coords is None:
             raise RuntimeError("refine=%r re-fits the RGB-D solver's pose: it needs depth or cam_coords" % (refine,))
         return True
+    if refine in MASKED_REFINE_MODES:
+        return True
     if refine not in ("inliers", "sigma"):
-        raise RuntimeError("refine must be False, \"inliers\", \"sigma\", \"rgbd_inliers\" or \"rgbd_sigma\", got %r" % (refine,))
+        raise RuntimeError("refine must be False, \"inliers\", \"sigma\", \"rgbd_inliers\", \"rgbd_sigma\", \"masked_inliers\" or "
+                           "\"masked_sigma\", got %r" % (refine,))
     if depth is not None or cam_coords is not None:
         raise RuntimeError("refine=%r re-fits the RGB solver's pose: it does not take depth or cam_coords" % (refine,))
     return True
@@ -329,9 +354,9 @@ RGBD_REFINE_MODES = ("rgbd_inliers", "rgbd_sigma")
 
 
 def _refine_sigma(refine, sigma, pred, nt):
-    """The sigma map the refinement reads: None for "inliers" / "rgbd_inliers"; for "sigma" / "rgbd_sigma" the side input if
-    given, otherwise the uncertainty channel of the prediction (a strided channel view, read in place)"""
-    if refine not in ("sigma", "rgbd_sigma"):
+    """The sigma map the refinement reads: None for the "..inliers" modes; for "sigma" / "rgbd_sigma" / "masked_sigma" the side
+    input if given, otherwise the uncertainty channel of the prediction (a strided channel view, read in place)"""
+    if refine not in ("sigma", "rgbd_sigma", "masked_sigma"):
         return None
     if sigma is not None:
         return sigma
@@ -350,6 +375,20 @@ def _refine_rgbd(refine, coords, cam_coords, depth, sg, poses, rgbd_threshold, m
     return dsacstar.refine_pose_rgbd_batch(coords, cam_coords, sg, poses, rgbd_threshold, max_dist_error,
                                            depthSigma=depth_sigma if weighted else None,
                                            depthRel=depth_rel if weighted else 0.0, sigmaFloorM=sigma_floor_m, depth=depth, **intr)
+
+
+def _masked_passes(refine, quality, coords, m, sg, poses, thr, f0, ppx, ppy, alpha, max_err, sub, sigma_floor_px, focals):
+    """The passes behind the masked RGB solver on the current stream, all over the mask `m` it read: the refinement, then the
+    quality pass, which rates the refined pose.  -> (poses, tail) with tail = ([quality rows][, refine rows])"""
+    import dsacstar
+    tail = ()
+    if refine:
+        poses, refine_rows = dsacstar.refine_pose_masked_batch(coords, m, sg, poses, thr, f0, ppx, ppy, max_err, sub,
+                                                               sigmaFloorPx=sigma_floor_px, focals=focals)
+        tail = (refine_rows,)
+    if quality:
+        tail = (dsacstar.pose_quality_masked_batch(coords, m, poses, thr, f0, ppx, ppy, alpha, max_err, sub, focals=focals),) + tail
+    return poses, tail
 
 
 def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, image_stride=1,
@@ -387,8 +426,12 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     `mask` (uint8 / bool [B,Ho,Wo], nonzero = usable; see cell_mask) or `mask_max_sigma` (the mask sigma <= mask_max_sigma from
     the prediction's uncertainty channel; RuntimeError if the network has none): the masked RGB solver
     (dsacstar.forward_rgb_masked_batch) runs in place of the plain one and its status [B] int32 (1: fewer than four usable
-    cells, identity pose) is appended as the LAST value.  Not yet with `depth` / `cam_coords` / `quality` / `refine`
-    (RuntimeError).  Without a mask nothing changes."""
+    cells, identity pose) is appended as the LAST value.  The passes behind it take the same mask tensor through modes of their
+    own: `refine="masked_inliers"` / `"masked_sigma"` (dsacstar.refine_pose_masked_batch, on the solver's stream) and
+    `quality="masked"` (dsacstar.pose_quality_masked_batch, behind the refinement: it rates the refined pose); the return is
+    then (poses, pred[, quality rows][, refine rows], status) with the refined poses first.  These modes need a mask
+    (RuntimeError without); a mask with `depth` / `cam_coords`, with `quality=True` / `"rgbd"` or with an unmasked `refine` mode
+    raises RuntimeError (those passes read every cell).  Without a mask nothing changes."""
     import dsacstar
     if depth is not None and cam_coords is not None:
         raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
@@ -409,11 +452,15 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
                                     ppointX=float(image_w / 2), ppointY=float(image_h / 2),
                                     subSampling=network.OUTPUT_SUBSAMPLE, focals=focals)
     elif masked:
-        status = dsacstar.forward_rgb_masked_batch(coords, _solver_mask(mask, mask_max_sigma, pred, nt), poses, n_hyp, threshold,
+        m = _solver_mask(mask, mask_max_sigma, pred, nt)                      # built once, read by the solver and its passes
+        status = dsacstar.forward_rgb_masked_batch(coords, m, poses, n_hyp, threshold,
                                                    f0, float(image_w / 2), float(image_h / 2), inlier_alpha, max_pixel_error,
                                                    network.OUTPUT_SUBSAMPLE, image0=image0, image_stride=image_stride,
                                                    focals=focals)
-        return (poses, pred, status)
+        poses, tail = _masked_passes(refine, quality, coords, m, _refine_sigma(refine, sigma, pred, nt), poses, threshold, f0,
+                                     float(image_w / 2), float(image_h / 2), inlier_alpha, max_pixel_error,
+                                     network.OUTPUT_SUBSAMPLE, sigma_floor_px, focals)
+        return (poses, pred) + tail + (status,)
     else:
         dsacstar.forward_rgb_batch(coords, poses, n_hyp, threshold, f0, float(image_w / 2), float(image_h / 2),
                                    inlier_alpha, max_pixel_error, network.OUTPUT_SUBSAMPLE,
@@ -504,7 +551,9 @@ class PipelinedLocalizer:
         `refine` "rgbd_inliers" / "rgbd_sigma" with `depth_sigma`, `depth_rel` and `sigma_floor_m` (only with `depth` or
         `cam_coords`): the RGB-D refinement runs behind the RGB-D solver on the side stream, as in localize_batch.
         `mask` / `mask_max_sigma` as in localize_batch: the masked RGB solver runs on the side stream and its status [B] int32 is
-        appended as the last value; not yet with `depth` / `cam_coords` / `quality` / `refine`."""
+        appended as the last value; `refine="masked_inliers"` / `"masked_sigma"` and `quality="masked"` run the passes over the
+        same mask behind it on the side stream, returned as (poses, pred[, quality rows][, refine rows], status).  Not with
+        `depth` / `cam_coords` or the unmasked `quality` / `refine` modes."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
@@ -527,17 +576,26 @@ class PipelinedLocalizer:
                 (depth if depth is not None else cam_coords).record_stream(self.side)
             elif masked:
                 f0, focals = _focal_args(self.focal, coords.shape[0])
-                status = dsacstar.forward_rgb_masked_batch(coords, _solver_mask(mask, mask_max_sigma, pred, self.net.num_task_channel),
-                                                           poses, self.n_hyp, self.thr, f0, float(self.w / 2), float(self.h / 2),
-                                                           self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE, image0=image0,
-                                                           image_stride=image_stride, focals=focals)
-                if mask is not None:
-                    mask.record_stream(self.side)
+                m = _solver_mask(mask, mask_max_sigma, pred, self.net.num_task_channel)     # built once, on the side stream
+                solved = poses
+                status = dsacstar.forward_rgb_masked_batch(coords, m, solved, self.n_hyp, self.thr, f0, float(self.w / 2),
+                                                           float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
+                                                           image0=image0, image_stride=image_stride, focals=focals)
+                poses, masked_tail = _masked_passes(refine, quality, coords, m,
+                                                    _refine_sigma(refine, sigma, pred, self.net.num_task_channel), solved, self.thr,
+                                                    f0, float(self.w / 2), float(self.h / 2), self.alpha, self.maxerr,
+                                                    self.net.OUTPUT_SUBSAMPLE, sigma_floor_px, focals)
+                solved.record_stream(self.side)
+                for side_input in (mask, sigma if refine else None):
+                    if side_input is not None:
+                        side_input.record_stream(self.side)
             else:
                 dsacstar.forward_rgb_batch(coords, poses, self.n_hyp, self.thr, self.focal, float(self.w / 2),
                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
                                            image0=image0, image_stride=image_stride)
-            if refine in RGBD_REFINE_MODES:
+            if masked:
+                pass                                        # its passes ran above, over the solver's mask
+            elif refine in RGBD_REFINE_MODES:
                 sg = _refine_sigma(refine, sigma, pred, self.net.num_task_channel)
                 solved = poses
                 intr = dict(focalLength=f0, ppointX=float(self.w / 2), ppointY=float(self.h / 2),
@@ -558,7 +616,9 @@ class PipelinedLocalizer:
                 solved.record_stream(self.side)
                 if sigma is not None:
                     sigma.record_stream(self.side)
-            if _is_rgbd_quality(quality):
+            if masked:
+                pass
+            elif _is_rgbd_quality(quality):
                 rows = dsacstar.pose_quality_rgbd_batch(coords, cam_coords, poses, rgbd_threshold, self.alpha, max_dist_error,
                                                         depth=depth, focalLength=f0, ppointX=float(self.w / 2),
                                                         ppointY=float(self.h / 2), subSampling=self.net.OUTPUT_SUBSAMPLE,
@@ -570,8 +630,10 @@ class PipelinedLocalizer:
         poses.record_stream(self.side)
         tail = ()
         if masked:
-            status.record_stream(torch.cuda.current_stream())    # allocated on the side stream, read by the caller's after finish()
-            return (poses, pred, status)
+            # allocated on the side stream, read by the caller's after finish()
+            for t in (poses, status) + masked_tail:
+                t.record_stream(torch.cuda.current_stream())
+            return (poses, pred) + masked_tail + (status,)
         if refine:
             # allocated on the side stream, read by the caller's after finish()
             poses.record_stream(torch.cuda.current_stream())

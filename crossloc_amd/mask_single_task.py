@@ -19,6 +19,12 @@ Every option of test_single_task is accepted and means the same.  Added:
                             mask (needs --decoy); `sigma`: cells whose predicted standard deviation is at most --mask_max_sigma
                             (needs a network with an uncertainty channel)
   --mask_max_sigma S        metres (default 1.0)
+  --refine {none,inliers,sigma}  default `none`: the report is unchanged character for character.  Otherwise the refinement runs
+                            behind the solver of every batch and the report is about the refined poses: with a --mask other than
+                            `none` over the solver's mask (localize_batch's refine="masked_inliers" / "masked_sigma"), with
+                            `--mask none` over every cell ("inliers" / "sigma"), so one command line compares the two.  `sigma`
+                            weights by the network's uncertainty channel (the options of crossloc_amd.refine_single_task that
+                            shape synthetic sigma maps are not taken here).
 A frame the solver reports as dead (fewer than four usable cells) keeps the identity pose it wrote, and counts as such.
 """
 import argparse
@@ -51,16 +57,18 @@ class _SynthWithDecoy:
 class _EvaluationWithMask:
     """crossloc_amd.evaluation as test_single_task.main() sees it during a masked run (see the module docstring)."""
 
-    def __init__(self, mode, max_sigma, scenes):
-        self.mode, self.max_sigma, self.scenes = mode, max_sigma, scenes
+    def __init__(self, mode, max_sigma, scenes, refine='none'):
+        self.mode, self.max_sigma, self.scenes, self.refine = mode, max_sigma, scenes, refine
 
     def __getattr__(self, name):
         return getattr(evaluation, name)
 
     def localize_batch(self, network, images, *args, **kwargs):
         kept, self.scenes.kept = self.scenes.kept, []
+        if self.refine != 'none':                       # out[0] is then the refined poses, masked or not
+            kwargs["refine"] = self.refine if self.mode == 'none' else "masked_" + self.refine
         if self.mode == 'none':
-            return evaluation.localize_batch(network, images, *args, **kwargs)
+            return evaluation.localize_batch(network, images, *args, **kwargs)[:2]
         if self.mode == 'sigma':
             out = evaluation.localize_batch(network, images, *args, mask_max_sigma=self.max_sigma, **kwargs)
         else:
@@ -76,11 +84,12 @@ def main():
     own.add_argument('--decoy', type=float, default=None, metavar='FRAC')
     own.add_argument('--mask', choices=['none', 'truth', 'sigma'], default='none')
     own.add_argument('--mask_max_sigma', type=float, default=1.0)
+    own.add_argument('--refine', choices=['none', 'inliers', 'sigma'], default='none')
     opt, rest = own.parse_known_args()                  # test_single_task's parser sees everything else
     scenes = _SynthWithDecoy(opt.decoy)
     saved = sys.argv, test_single_task.evaluation, test_single_task.synth
     sys.argv = [sys.argv[0]] + rest
-    test_single_task.evaluation = _EvaluationWithMask(opt.mask, opt.mask_max_sigma, scenes)
+    test_single_task.evaluation = _EvaluationWithMask(opt.mask, opt.mask_max_sigma, scenes, opt.refine)
     test_single_task.synth = scenes
     try:
         test_single_task.main()

@@ -11,7 +11,8 @@ from crossloc_amd.dsacstar import *  # noqa: F401,F403
 from crossloc_amd.dsacstar import (RANSAC_SEED, MAX_HYPOTHESES_TRIES, MAX_REF_STEPS, backward_rgb,  # noqa: F401
                                    backward_rgb_batch, backward_rgb_masked_batch, backward_rgbd, backward_rgbd_batch,
                                    camera_coordinates, forward_rgb,
-                                   forward_rgb_batch, forward_rgb_masked_batch, forward_rgbd, forward_rgbd_batch, set_image_index)
+                                   forward_rgb_batch, forward_rgb_masked_batch, forward_rgbd, forward_rgbd_batch,
+                                   pose_quality_masked_batch, refine_pose_masked_batch, set_image_index)
 from crossloc_amd import dsacstar as _impl
 
 NATIVE = None

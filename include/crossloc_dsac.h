@@ -92,9 +92,9 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
  * Identity A: with an all-ones mask every output equals xl_dsac_forward_rgb_batch's bit for bit.
  * Identity B: the values stored at masked-out cells influence no output bit.
  *
- * XL_ERR_ARG for a null mask and for everything xl_dsac_forward_rgb_batch refuses, before any HIP call.  Not covered: the
- * quality and refinement passes, the RGB-D solver and its backward pass and the single-image host entry point take no mask
- * (the RGB backward pass does: xl_dsac_backward_rgb_masked_batch).
+ * XL_ERR_ARG for a null mask and for everything xl_dsac_forward_rgb_batch refuses, before any HIP call.  The backward pass
+ * and the two passes behind the solver take the same mask (xl_dsac_backward_rgb_masked_batch, xl_dsac_pose_quality_masked_batch,
+ * xl_dsac_refine_pose_masked_batch).  Not covered: the RGB-D solver and its passes and the single-image host entry point.
  */
 int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                      int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
@@ -207,17 +207,30 @@ int xl_dsac_backward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64
  *     [31..51] Sigma = sigma_px^2 (JtJ)^-1, upper triangle row-major
  *     [52..57] Sigma_C = A Sigma A^T, upper triangle: covariance of the camera centre C = -R^T t in world coordinates,
  *              A = [ -R^T [t]x , -R^T ] (3x6)
- *     [58..63] 0.0 (reserved)
+ *     [58]     n_masked: 0.0; xl_dsac_pose_quality_masked_batch: the cells its mask rules out
+ *     [59..63] 0.0 (reserved)
  *
  *   Parameters of JtJ and Sigma: (wx, wy, wz, tx, ty, tz) with R' = Exp(w) R, t' = t + d on the world->camera pose, the
  *   increment of the Levenberg-Marquardt refinement.  With status 1 or 2, [7..9] and [31..57] are NaN and the rest is valid;
  *   with status 3 every field except [0] and [6] is NaN.
+ *
+ * xl_dsac_pose_quality_masked_batch is the same pass over the per-cell validity mask of xl_dsac_forward_rgb_masked_batch
+ * (mask_dev [B,Ho,Wo] uint8 contiguous, nonzero = usable; usually the mask the solver read): the mask byte of a cell is read
+ * before anything else of it, and a masked-out cell is skipped - its coordinate is not loaded, it is no inlier and adds to no
+ * sum.  [0] stays Ho*Wo, [1] and [3..57] run over usable cells only, [2] sums the usable cells with the same factor
+ * alpha / Wo / Ho (the masked solver's score), [58] counts the masked-out cells (NaN with status 3, like its neighbours).
+ * With an all-ones mask every output equals xl_dsac_pose_quality_batch's bit for bit; the values stored at masked-out cells
+ * influence no output bit.  A null mask is XL_ERR_ARG, before any HIP call.
  */
 #define XL_DSAC_QUALITY_DOUBLES 64
 int xl_dsac_pose_quality_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                                int B, int Ho, int Wo, const float *poses_dev /* [B,16] cam->world */,
                                float thr, float focal, float ppx, float ppy, float alpha, float max_reproj, int sub,
                                const float *focals_dev, double *rows_dev /* [B,64] */, void *stream);
+int xl_dsac_pose_quality_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                      int B, int Ho, int Wo, const uint8_t *mask_dev, const float *poses_dev /* [B,16] cam->world */,
+                                      float thr, float focal, float ppx, float ppy, float alpha, float max_reproj, int sub,
+                                      const float *focals_dev, double *rows_dev /* [B,64] */, void *stream);
 
 /*
  * Batched RGB-D forward pass: the solver of dsacstar_rgbd_forward (dsacstar.cpp:495-612) for B independent images in one
@@ -441,7 +454,7 @@ int xl_dsac_pose_quality_rgbd_batch(const float *coords_dev, int64_t sb, int64_t
  *     [52..57] Sigma_C, covariance of the camera centre as in the pose-quality row
  *     [58]     rounds completed       [59] normal-equation evaluations       [60] converged (1 / 0)
  *     [61]     rotation between input and output pose, degrees               [62] distance of their camera centres, metres
- *     [63]     0.0
+ *     [63]     n_masked: 0.0; xl_dsac_refine_pose_masked_batch: the cells its mask rules out
  *   NaN pattern as in the pose-quality row.  With status 1 or 2 no round completed: [1] = [2], [4] = [3] and [10..30] come from
  *   the first evaluation at the input pose, [7..9] and [31..57] are NaN, [58] and [60..62] are 0.  With status 3 every field
  *   except [0] and [6] is NaN.  With status 0, [8], [9] and [31..57] are NaN if J^T W J at the output pose has no Cholesky factor.
@@ -451,6 +464,16 @@ int xl_dsac_pose_quality_rgbd_batch(const float *coords_dev, int64_t sb, int64_t
  * The image is staged in the LDS of one CU as four float planes: Ho * Wo <= XL_DSAC_REFINE_MAX_CELLS, else XL_ERR_GRID.
  * XL_ERR_ARG: a null coords / poses / out_poses / rows pointer, B, Ho, Wo or sub not positive, s0 not above 0, max_rounds out
  * of range.  Both are returned before any HIP call.
+ *
+ * xl_dsac_refine_pose_masked_batch is the same pass over the per-cell validity mask of xl_dsac_forward_rgb_masked_batch
+ * (mask_dev [B,Ho,Wo] uint8 contiguous, nonzero = usable; usually the mask the solver read).  No plane is added to the LDS, so
+ * the cell limit is the same: every thread keeps the mask bytes of its own cells as a 64-bit word.  A masked-out cell is not
+ * staged and is passed by in every round before its sigma is checked and before its error is formed: it is in no inlier set
+ * and neither its coordinate nor its sigma enters any arithmetic.  [5] counts usable cells only, [63] the masked-out cells
+ * (NaN with status 3); everything else keeps its meaning.  An image with fewer than four usable cells has status 1 and its
+ * input pose comes back bit for bit (behind the masked solver: the identity it wrote).  With an all-ones mask every output
+ * equals xl_dsac_refine_pose_batch's bit for bit; the values stored at masked-out cells influence no output bit.  A null mask
+ * is XL_ERR_ARG, before any HIP call.
  */
 #define XL_DSAC_REFINE_DOUBLES 64
 #define XL_DSAC_REFINE_MAX_CELLS 10128      /* (160 KiB - reduction scratch) / 16 bytes per cell */
@@ -461,6 +484,12 @@ int xl_dsac_refine_pose_batch(const float *coords_dev, int64_t sb, int64_t sc, i
                               float *out_poses_dev /* [B,16] */, double *rows_dev /* [B,64] */, double *w2c_dev /* [B,12] or NULL */,
                               float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
                               const float *focals_dev, float s0, int max_rounds, void *stream);
+int xl_dsac_refine_pose_masked_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                     const float *sigma_dev, int64_t gb, int64_t gy, int64_t gx,
+                                     int B, int Ho, int Wo, const uint8_t *mask_dev, const float *poses_dev /* [B,16] cam->world */,
+                                     float *out_poses_dev /* [B,16] */, double *rows_dev /* [B,64] */, double *w2c_dev /* [B,12] or NULL */,
+                                     float thr, float focal, float ppx, float ppy, float max_reproj, int sub,
+                                     const float *focals_dev, float s0, int max_rounds, void *stream);
 
 /*
  * Ray-aware uncertainty-weighted pose refinement behind the RGB-D solver (no reference counterpart): ONE given pose per image -

@@ -22,7 +22,13 @@ hypotheses on 60 x 90 and 1 frame, the same four legs (ground truth: the frames'
 into and never read), the expected loss of the two decoy legs in place of the pose error.  `--backward --unmasked_only` is
 the parent-commit leg as above.
 
-    python tools/masked_timing.py [--backward] [--json out.json] [--unmasked_only]
+`--quality` / `--refine` time the passes behind the solver (dsacstar.pose_quality_masked_batch / refine_pose_masked_batch against
+pose_quality_batch / refine_pose_batch): 95 frames x 256 hypotheses on 60 x 90 and 1 frame.  Every leg is the masked solver plus
+the pass behind it, as a masked evaluation runs them: `unmasked` the all-ones solver and the UNMASKED pass, `all_ones`, `half`
+and `decoy_band` the solver and the masked pass over that mask (the refinement weighted by a sigma map of 0.5 m, make_scene's
+noise).  With `--unmasked_only` the first leg alone, which the parent commit can run too.
+
+    python tools/masked_timing.py [--backward | --quality | --refine] [--json out.json] [--unmasked_only]
 """
 import argparse
 import json
@@ -115,6 +121,62 @@ def backward_rows(opt, dev):
     return results
 
 
+def pass_rows(opt, dev):
+    """the rows of --quality / --refine: 95 frames and 1 frame; every leg is the masked solver plus the pass behind it"""
+    quality = opt.quality
+    intr, tail = ARGS[:4], ((ARGS[4],) if quality else ()) + ARGS[5:]          # the refinement takes no alpha
+    results = []
+    for B in (95, 1):
+        scenes = [synth.make_scene(2021 + i) for i in range(B)]
+        co = torch.from_numpy(np.stack([s["coords"] for s in scenes])).to(dev)
+        sg = torch.full((B, 60, 90), 0.5, device=dev)                          # make_scene's noise: 0.5 m per axis
+        ones = torch.ones((B, 60, 90), dtype=torch.uint8, device=dev)
+        poses = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
+
+        def behind(coords, mask, solve=True):
+            """the solver over `mask`, then the pass: over the same mask, or (mask None: after the all-ones solver) unmasked;
+            solve=False: the pass alone, at the poses the last solver call left"""
+            if solve:
+                dsacstar.forward_rgb_masked_batch(coords, ones if mask is None else mask, poses, opt.hypotheses, *ARGS)
+            if quality:
+                if mask is None:
+                    return dsacstar.pose_quality_batch(coords, poses, *intr, *tail)
+                return dsacstar.pose_quality_masked_batch(coords, mask, poses, *intr, *tail)
+            if mask is None:
+                return dsacstar.refine_pose_batch(coords, sg, poses, *intr, *tail)[1]
+            return dsacstar.refine_pose_masked_batch(coords, mask, sg, poses, *intr, *tail)[1]
+
+        row = dict(solver_pass="forward + " + ("quality" if quality else "refine"), frames=B, hypotheses=opt.hypotheses, grid=[60, 90])
+        if opt.unmasked_only:
+            (tu, tp), (su, sp) = time_legs((lambda: behind(co, None), lambda: behind(co, None, False)), opt.warmup, opt.iters,
+                                           opt.rounds)
+            row.update(unmasked_ms=tu, unmasked_spread_ms=su, unmasked_pass_ms=tp, unmasked_pass_spread_ms=sp)
+            results.append(row)
+            continue
+
+        decoys = [synth.make_decoy_scene(2021 + i, decoy=0.6) for i in range(B)]
+        dco = torch.from_numpy(np.stack([s["coords"] for s in decoys])).to(dev)
+        band = torch.from_numpy(np.stack([s["mask"] for s in decoys])).to(dev)
+        half = torch.from_numpy((np.random.default_rng(2021).random((B, 60, 90)) < 0.5).astype(np.uint8)).to(dev)
+        ra, rb = behind(co, None), behind(co, ones)
+        torch.cuda.synchronize()
+        assert torch.equal(ra.nan_to_num(nan=-7.0), rb.nan_to_num(nan=-7.0)), "the all-ones mask must give the unmasked pass's rows"
+        legs = (("unmasked", lambda: behind(co, None)), ("all_ones", lambda: behind(co, ones)),
+                ("half", lambda: behind(co, half)), ("decoy_band", lambda: behind(dco, band)))
+        med, spread = time_legs([fn for _, fn in legs], opt.warmup, opt.iters, opt.rounds)
+        for (name, _), t, s in zip(legs, med, spread):
+            row.update({name + "_ms": t, name + "_spread_ms": s})
+        # the pass alone, at the poses of the all-ones solver: where the mask's own cost shows beside the solver's 2 ms
+        behind(co, ones)
+        alone = (("unmasked", lambda: behind(co, None, False)), ("all_ones", lambda: behind(co, ones, False)),
+                 ("half", lambda: behind(co, half, False)))
+        med, spread = time_legs([fn for _, fn in alone], opt.warmup, opt.iters, opt.rounds)
+        for (name, _), t, s in zip(alone, med, spread):
+            row.update({name + "_pass_ms": t, name + "_pass_spread_ms": s})
+        results.append(row)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -123,8 +185,12 @@ def main():
     ap.add_argument("--hypotheses", type=int, default=256)
     ap.add_argument("--unmasked_only", action="store_true")
     ap.add_argument("--backward", action="store_true", help="time the backward passes (24 frames and 1 frame)")
+    ap.add_argument("--quality", action="store_true", help="time the masked solver plus the quality pass behind it")
+    ap.add_argument("--refine", action="store_true", help="time the masked solver plus the refinement behind it")
     ap.add_argument("--json", type=str, default=None)
     opt = ap.parse_args()
+    if opt.backward + opt.quality + opt.refine > 1:
+        raise SystemExit("masked_timing: one of --backward, --quality and --refine")
     if opt.rounds < 5:
         raise SystemExit("masked_timing: at least 5 rounds")
     if not torch.cuda.is_available():
@@ -138,8 +204,8 @@ def main():
     torch.cuda.synchronize()
     del x
 
-    results = backward_rows(opt, dev) if opt.backward else []
-    for B in (() if opt.backward else (95, 1)):
+    results = backward_rows(opt, dev) if opt.backward else pass_rows(opt, dev) if (opt.quality or opt.refine) else []
+    for B in (() if results else (95, 1)):
         co = torch.from_numpy(np.stack([synth.make_scene(2021 + i)["coords"] for i in range(B)])).to(dev)
         poses = torch.zeros((B, 4, 4), dtype=torch.float32, device=dev)
 
