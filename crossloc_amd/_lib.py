@@ -59,6 +59,11 @@ def lib():
         L.xl_dsac_forward_rgb_masked_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
                                                        c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp,
                                                        c_u64, c_u64, c_u64, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp]
+        L.xl_dsac_forward_rgb_masked_sampled_batch.restype = c_i32                # (`sampler` after the mask)
+        L.xl_dsac_forward_rgb_masked_sampled_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                                               c_vp, c_vp,
+                                                               c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_i32, c_vp,
+                                                               c_u64, c_u64, c_u64, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp]
         L.xl_dsac_forward_sub_blocks.restype = c_i32
         L.xl_dsac_forward_sub_blocks.argtypes = [c_i32, c_i32]
         L.xl_dsac_forward_rgb_host.restype = c_i32
@@ -74,6 +79,11 @@ def lib():
                                                         c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
                                                         c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32,
                                                         c_vp, c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
+        L.xl_dsac_backward_rgb_masked_sampled_batch.restype = c_i32
+        L.xl_dsac_backward_rgb_masked_sampled_batch.argtypes = [c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32,
+                                                                c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
+                                                                c_i32, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i32,
+                                                                c_vp, c_u64, c_u64, c_u64, c_u32, c_vp, c_vp]
         L.xl_dsac_backward_sub_blocks.restype = c_i32
         L.xl_dsac_backward_sub_blocks.argtypes = [c_i32, c_i32]
         L.xl_dsac_pose_quality_batch.restype = c_i32

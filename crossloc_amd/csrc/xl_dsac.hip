@@ -128,28 +128,73 @@ __device__ __forceinline__ int stage_mask(const uint8_t *gm, int N, uint32_t *sM
     return cnt;
 }
 
+// the mask mode of the forward kernel: the unmasked solver, and the masked solver behind either sampler (XL_DSAC_SAMPLER_*)
+constexpr int kMaskNone = 0, kMaskReject = 1, kMaskCompact = 2;
+
+// rank plane of the mask (compact sampler): nWords + 1 words in LDS behind the bit plane, rank[w] = usable cells in words
+// 0 .. w-1 (mask_rank_plane of xl_dsac_math.h).  Thread t owns words 2t and 2t+1, so a wave owns 128 consecutive words: it sums
+// the words of the waves before it (at most three pairs per lane and one butterfly) and scans its own, which needs no exchange
+// between waves and one barrier after the writes.  nUsable is the workgroup's count from stage_mask (= rank[nWords]).  Call after
+// the barrier that follows stage_mask.
+__device__ __forceinline__ void build_rank_plane(const uint32_t *sMask, uint32_t *sRank, int nWords, int nUsable, int wave, int lane)
+{
+    auto pair = [&](int w2, int &c0, int &c1) {
+        c0 = (w2 < nWords) ? __popc(sMask[w2]) : 0;
+        c1 = (w2 + 1 < nWords) ? __popc(sMask[w2 + 1]) : 0;
+    };
+    int before = 0;
+    for (int v = 0; v < wave; ++v) {
+        int c0, c1;
+        pair(2 * (v * 64 + lane), c0, c1);
+        before += c0 + c1;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) before += __shfl_xor(before, off);
+    const int w2 = 2 * (wave * 64 + lane);
+    int c0, c1;
+    pair(w2, c0, c1);
+    int incl = c0 + c1;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off);
+        if (lane >= off) incl += o;
+    }
+    const int excl = before + incl - (c0 + c1);
+    if (w2 < nWords) sRank[w2] = (uint32_t)excl;
+    if (w2 + 1 < nWords) sRank[w2 + 1] = (uint32_t)(excl + c0);
+    if (wave == 0 && lane == 0) sRank[nWords] = (uint32_t)nUsable;     // (512 words at the largest grid: past the last pair)
+}
+
 // one sampling try (dsacstar_util.h:159-219); returns accept flag, pose = try result (identity if P3P failed)
-// MASKED: the same four draws; a try that drew a masked-out cell is rejected before P3P (identity pose, like a failed P3P) and
-// the coordinates of such a cell are never read
-template <bool MASKED>
+// kMaskReject: the same four draws; a try that drew a masked-out cell is rejected before P3P (identity pose, like a failed P3P)
+// and the coordinates of such a cell are never read
+// kMaskCompact: four draws of a rank among the usable cells (compact_try_cells: LDS reads only); no try is rejected by the mask
+template <int MASK>
 __device__ bool sample_try(const Coords &co, const MaskBits &mb, const Cam &cam, uint64_t imageKey, uint32_t hyp, uint32_t t,
                            Pose &pose, int (&cells)[4])
 {
+    constexpr bool REJECT = MASK == kMaskReject;
     uint64_t st = try_state(imageKey, hyp, t);
     V3 P[4];
     double uv[4][2];
     float px[4], py[4];
+    if constexpr (MASK == kMaskCompact) compact_try_cells(st, mb.w, mb.w + ((cam.N + 31) >> 5), (cam.N + 31) >> 5, cells);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        int x = draw(st, 2 * j, cam.Wo);
-        int y = draw(st, 2 * j + 1, cam.Ho);
-        cells[j] = y * cam.Wo + x;
+        int x, y;
+        if constexpr (MASK == kMaskCompact) {
+            y = cells[j] / cam.Wo; x = cells[j] - y * cam.Wo;
+        } else {
+            x = draw(st, 2 * j, cam.Wo);
+            y = draw(st, 2 * j + 1, cam.Ho);
+            cells[j] = y * cam.Wo + x;
+        }
         px[j] = cell_px(&cam, x);
         py[j] = cell_px(&cam, y);
         uv[j][0] = (double)px[j]; uv[j][1] = (double)py[j];
-        if constexpr (!MASKED) co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
+        if constexpr (!REJECT) co.fetch(cells[j], P[j].x, P[j].y, P[j].z);
     }
-    if constexpr (MASKED) {
+    if constexpr (REJECT) {
         if (!(mb.usable(cells[0]) && mb.usable(cells[1]) && mb.usable(cells[2]) && mb.usable(cells[3]))) {
             pose_identity(&pose);
             return false;
@@ -322,11 +367,16 @@ __device__ __forceinline__ void refine_pose(const Coords &co, const Cam &cam, Sm
 // nor the NaN flag); an inlier is a usable cell below the threshold.  An image with fewer than four usable cells is dead: the
 // try loop is not entered, the identity pose and status 1 are written (the branch is uniform over the workgroup, and over the
 // workgroups of an image in the split form: each of them counts the same mask).  With an all-ones mask every output is the
-// unmasked kernel's, bit for bit.
-template <int PHASE, bool MASKED = false>
+// unmasked kernel's, bit for bit.  That is MASK = kMaskReject.
+// MASK = kMaskCompact (xl_dsac_forward_rgb_masked_sampled_batch, XL_DSAC_SAMPLER_COMPACT): the same, except that a try draws four
+// ranks among the usable cells and selects their cells through a rank plane kept behind the bit plane (build_rank_plane, one
+// more barrier; each workgroup of an image builds the same plane), so the mask rejects no try.  Score, select, refine, the dead
+// image and the NaN rule are the masked solver's.  An all-ones mask does not reproduce the unmasked kernel's draws.
+template <int PHASE, int MASK = kMaskNone>
 __global__ __launch_bounds__(kThreads, PHASE == 1 ? 2 : 1)     // (sample + score: LDS allows two workgroups per CU, 256 registers per wave)
 void xl_dsac_forward_kernel(Params P)
 {
+    constexpr bool MASKED = MASK != kMaskNone;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Smem &S = *reinterpret_cast<Smem *>(smem_raw);
     float *sCo = reinterpret_cast<float *>(smem_raw + ((sizeof(Smem) + 15) & ~size_t(15)));
@@ -380,6 +430,14 @@ void xl_dsac_forward_kernel(Params P)
             }
             return;
         }
+        if constexpr (MASK == kMaskCompact) {
+            // the rank plane behind the bit plane (every workgroup of the image builds the same one); PHASE 2 samples nothing
+            if (PHASE != 2) {
+                const int nWords = (N + 31) >> 5;
+                build_rank_plane(sMask, sMask + nWords, nWords, nUsable, wave, lane);
+                __syncthreads();
+            }
+        }
         usable = mb.slice(tid, N);
     }
 
@@ -403,7 +461,7 @@ void xl_dsac_forward_kernel(Params P)
             Pose p;
             int cc[4] = { 0, 0, 0, 0 };
             bool ok = false;
-            if (t < P.maxTries) ok = sample_try<MASKED>(co, mb, cam, imageKey, (uint32_t)h, t, p, cc);
+            if (t < P.maxTries) ok = sample_try<MASK>(co, mb, cam, imageKey, (uint32_t)h, t, p, cc);
             else pose_identity(&p);
             unsigned long long m = __ballot(ok);
             int src;
@@ -420,8 +478,13 @@ void xl_dsac_forward_kernel(Params P)
         // exp, divide) in flight - the kernel runs at 1-2 waves per SIMD and was bound by that latency.  Same operations per
         // cell, same order of the additions into `acc`: the bits do not change (XL_DSAC_PAIR_CELLS=0: one cell per trip)
         double acc = 0.0;
-        int i = lane;
-        CellWalk w0(lane, 128, cam.Wo), w1(lane + 64, 128, cam.Wo);
+        // compact sampler: the lane as the compiler cannot see through it, so that the walk's start (row, column, mask word of
+        // the first cells) is worked out per hypothesis - two integer divisions - instead of being hoisted out of the hypothesis
+        // loop, where at 256 registers it is spilled (16 bytes of scratch per lane without this; the other modes keep their code)
+        int lane0 = lane;
+        if constexpr (MASK == kMaskCompact) asm volatile("" : "+v"(lane0));
+        int i = lane0;
+        CellWalk w0(lane0, 128, cam.Wo), w1(lane0 + 64, 128, cam.Wo);
         if (P.pairCells)
         for (; i + 64 < N; i += 128) {
             float e0, e1;
@@ -564,6 +627,9 @@ struct BwdParams {
 // xl_dsac_forward_kernel<1, true> has then written neither poses nor cells) gets loss 0, status 1, zero records and an untouched
 // gradient: K1 decides that on its own count before it reads a score and publishes it in P.status, on which K2, K3 and K4 return
 // before they read anything of that image's workspace.
+// Under the compact sampler (backward_rgb_launch<kMaskCompact>: the sample + score launch is xl_dsac_forward_kernel<1, kMaskCompact>,
+// K1 - K4 are these MASKED instantiations) every hypothesis carries four usable cells, so K3's skip never fires and a hypothesis
+// whose tries ran out is differentiated as the unmasked pass differentiates one.
 
 // K1 (grid nHyp x B): soft-max probability of the hypothesis, refinement if it matters, loss, path-I quantities
 template <bool MASKED = false>
@@ -933,9 +999,9 @@ int xl_dsac_forward_sub_blocks(int B, int n_hyp)
 
 namespace {
 
-// the forward launch of both solvers: MASKED adds the mask and the status vector, the bit plane to the LDS carve, and launches
-// the masked instantiations (which keep an LDS limit of their own)
-template <bool MASKED>
+// the forward launch of the solvers: a mask mode other than kMaskNone adds the mask and the status vector and the bit plane to the
+// LDS carve, kMaskCompact the rank plane behind it; each mode launches its own instantiations (which keep an LDS limit of their own)
+template <int MASK>
 int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                        int B, int Ho, int Wo, const uint8_t *mask_dev, float *out_poses_dev, int32_t *status_dev,
                        int n_hyp, float thr, float focal, float ppx, float ppy,
@@ -946,6 +1012,7 @@ int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t 
 {
     if (!coords_dev || !out_poses_dev || B <= 0 || Ho <= 0 || Wo <= 0 || n_hyp <= 0 || sub <= 0 || max_tries == 0)
         return XL_ERR_ARG;
+    constexpr bool MASKED = MASK != kMaskNone;
     if (MASKED && !mask_dev) return XL_ERR_ARG;
     const int N = Ho * Wo;
     if (N > kMaxCells) return XL_ERR_GRID;
@@ -960,15 +1027,16 @@ int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t 
 
     size_t lds = ((sizeof(Smem) + 15) & ~size_t(15)) + (size_t)3 * P.Npad * sizeof(float);
     if (MASKED) lds += sizeof(uint32_t) * (size_t)((N + 31) / 32);          // the bit plane: 676 B at 60x90
+    if (MASK == kMaskCompact) lds += sizeof(uint32_t) * (size_t)((N + 31) / 32 + 1);     // the rank plane: 680 B at 60x90
     if (lds > 160 * 1024) return XL_ERR_GRID;
     static XlLdsLimit configured;
     int cfgDev;
     if (configured.needs(lds, &cfgDev)) {
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<0, MASKED>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<0, MASK>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASKED>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASK>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<2, MASKED>),
+        XL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<2, MASK>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         configured.done(lds, cfgDev);
     }
@@ -980,12 +1048,12 @@ int forward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t 
     static const int cellWalk = getenv("XL_DSAC_CELL_WALK") ? atoi(getenv("XL_DSAC_CELL_WALK")) : 1;
     P.cellWalk = cellWalk;
     if (S == 1) {
-        hipLaunchKernelGGL((xl_dsac_forward_kernel<0, MASKED>), dim3(B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<0, MASK>), dim3(B), dim3(kThreads), lds, st, P);
     } else {
         const size_t bytes = sizeof(double) * ((size_t)B * S * kWaves * 16 + (size_t)B * 12);
         XL_HIP(hipMallocAsync((void **)&P.part, bytes, st));
-        hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASKED>), dim3(S, B), dim3(kThreads), lds, st, P);
-        hipLaunchKernelGGL((xl_dsac_forward_kernel<2, MASKED>), dim3(B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASK>), dim3(S, B), dim3(kThreads), lds, st, P);
+        hipLaunchKernelGGL((xl_dsac_forward_kernel<2, MASK>), dim3(B), dim3(kThreads), lds, st, P);
         XL_HIP(hipFreeAsync(P.part, st));
     }
     XL_HIP(hipGetLastError());
@@ -1000,9 +1068,19 @@ int backward_sub_blocks(int B, int n_hyp)
     return S;
 }
 
-// the launch sequence of both backward passes: MASKED adds the mask and the status vector, the bit plane to the LDS carve, and
-// launches the masked instantiations (which keep an LDS limit of their own).  Everything is validated before the first HIP call.
+// the LDS limit of the backward kernels K1 and K3, one per instantiation: the masked pair serves both samplers
 template <bool MASKED>
+XlLdsLimit &backward_kernels_lds()
+{
+    static XlLdsLimit limit;
+    return limit;
+}
+
+// the launch sequence of the backward passes: a mask mode other than kMaskNone adds the mask and the status vector, the bit plane
+// to the LDS carve, and launches the masked instantiations of K1 - K4; the sample + score launch is the mode's own (kMaskCompact:
+// with the rank plane behind the bit plane), so the hypotheses differentiated are the ones that mode's forward produced.
+// Everything is validated before the first HIP call.
+template <int MASK>
 int backward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
                         int B, int Ho, int Wo, const uint8_t *mask_dev,
                         float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
@@ -1015,13 +1093,15 @@ int backward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t
     if (!coords_dev || !grad_dev || !gt_poses_dev || !out_loss_dev || B <= 0 || Ho <= 0 || Wo <= 0 || n_hyp <= 0 ||
         sub <= 0 || max_tries == 0)
         return XL_ERR_ARG;
+    constexpr bool MASKED = MASK != kMaskNone;
     if (MASKED && !mask_dev) return XL_ERR_ARG;
     const int N = Ho * Wo;
     if (N > kMaxCells) return XL_ERR_GRID;
     const int Npad = (N + 3) & ~3;
     size_t lds = ((sizeof(Smem) + 15) & ~size_t(15)) + (size_t)3 * Npad * sizeof(float);
     if (MASKED) lds += sizeof(uint32_t) * (size_t)((N + 31) / 32);          // the bit plane: 676 B at 60x90
-    if (lds > 160 * 1024) return XL_ERR_GRID;
+    const size_t ldsSample = lds + (MASK == kMaskCompact ? sizeof(uint32_t) * (size_t)((N + 31) / 32 + 1) : 0);     // + the rank plane
+    if (ldsSample > 160 * 1024) return XL_ERR_GRID;
     hipStream_t st = (hipStream_t)stream;
     const size_t nh = (size_t)B * n_hyp;
 
@@ -1066,17 +1146,22 @@ int backward_rgb_launch(const float *coords_dev, int64_t sb, int64_t sc, int64_t
 
     static XlLdsLimit configured;
     int cfgDev;
-    if (configured.needs(lds, &cfgDev)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASKED>),
+    if (configured.needs(ldsSample, &cfgDev)) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_forward_kernel<1, MASK>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsSample);
+        if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "hipFuncSetAttribute(backward_rgb)"); }
+        configured.done(ldsSample, cfgDev);
+    }
+    XlLdsLimit &configuredBwd = backward_kernels_lds<MASKED>();
+    if (configuredBwd.needs(lds, &cfgDev)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_hyp_kernel<MASKED>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_hyp_kernel<MASKED>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(xl_dsac_bwd_score_kernel<MASKED>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { (void)hipFreeAsync(ws, st); return hip_fail(e, "hipFuncSetAttribute(backward_rgb)"); }
-        configured.done(lds, cfgDev);
+        configuredBwd.done(lds, cfgDev);
     }
-    hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASKED>), dim3(S, B), dim3(kThreads), lds, st, P);
+    hipLaunchKernelGGL((xl_dsac_forward_kernel<1, MASK>), dim3(S, B), dim3(kThreads), ldsSample, st, P);
     hipLaunchKernelGGL((xl_dsac_bwd_hyp_kernel<MASKED>), dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
     hipLaunchKernelGGL((xl_dsac_bwd_expect_kernel<MASKED>), dim3(B), dim3(kThreads), 0, st, Q);
     hipLaunchKernelGGL((xl_dsac_bwd_score_kernel<MASKED>), dim3(n_hyp, B), dim3(kThreads), lds, st, Q);
@@ -1098,7 +1183,7 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
                               void *stream,
                               int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
 {
-    return forward_rgb_launch<false>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, out_poses_dev, nullptr, n_hyp, thr, focal,
+    return forward_rgb_launch<kMaskNone>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, out_poses_dev, nullptr, n_hyp, thr, focal,
                                      ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream,
                                      cells_dev, tries_dev, scores_dev, dbg_dev);
 }
@@ -1111,9 +1196,30 @@ int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_
                                      void *stream,
                                      int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
 {
-    return forward_rgb_launch<true>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, out_poses_dev, status_dev, n_hyp, thr, focal,
-                                    ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream,
-                                    cells_dev, tries_dev, scores_dev, dbg_dev);
+    return xl_dsac_forward_rgb_masked_sampled_batch(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, XL_DSAC_SAMPLER_REJECT,
+                                                    out_poses_dev, status_dev, n_hyp, thr, focal, ppx, ppy, alpha, max_reproj, sub,
+                                                    focals_dev, seed, image0, image_stride, max_tries, stream,
+                                                    cells_dev, tries_dev, scores_dev, dbg_dev);
+}
+
+int xl_dsac_forward_rgb_masked_sampled_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                             int B, int Ho, int Wo, const uint8_t *mask_dev, int sampler,
+                                             float *out_poses_dev, int32_t *status_dev,
+                                             int n_hyp, float thr, float focal, float ppx, float ppy,
+                                             float alpha, float max_reproj, int sub, const float *focals_dev,
+                                             uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                                             void *stream,
+                                             int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev)
+{
+    if (sampler == XL_DSAC_SAMPLER_REJECT)
+        return forward_rgb_launch<kMaskReject>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, out_poses_dev, status_dev, n_hyp, thr,
+                                               focal, ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride,
+                                               max_tries, stream, cells_dev, tries_dev, scores_dev, dbg_dev);
+    if (sampler == XL_DSAC_SAMPLER_COMPACT)
+        return forward_rgb_launch<kMaskCompact>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, out_poses_dev, status_dev, n_hyp, thr,
+                                                focal, ppx, ppy, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride,
+                                                max_tries, stream, cells_dev, tries_dev, scores_dev, dbg_dev);
+    return XL_ERR_ARG;                                           // unknown sampler: before any device work
 }
 
 // The reference's call shape (utils/evaluation.py:160-172): ONE frame, host tensors in, host pose out, blocking.  Round 6: the device
@@ -1213,7 +1319,7 @@ int xl_dsac_backward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, 
                                const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                uint32_t max_tries, void *stream, double *rec_dev)
 {
-    return backward_rgb_launch<false>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev,
+    return backward_rgb_launch<kMaskNone>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, nullptr, grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev,
                                       out_loss_dev, nullptr, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans, soft_clamp, alpha,
                                       max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream, rec_dev);
 }
@@ -1227,9 +1333,32 @@ int xl_dsac_backward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64
                                       const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                       uint32_t max_tries, void *stream, double *rec_dev)
 {
-    return backward_rgb_launch<true>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev,
-                                     out_loss_dev, status_dev, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans, soft_clamp, alpha,
-                                     max_reproj, sub, focals_dev, seed, image0, image_stride, max_tries, stream, rec_dev);
+    return xl_dsac_backward_rgb_masked_sampled_batch(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, XL_DSAC_SAMPLER_REJECT,
+                                                     grad_dev, gsb, gsc, gsy, gsx, gt_poses_dev, out_loss_dev, status_dev, n_hyp, thr,
+                                                     focal, ppx, ppy, w_rot, w_trans, soft_clamp, alpha, max_reproj, sub, focals_dev,
+                                                     seed, image0, image_stride, max_tries, stream, rec_dev);
+}
+
+int xl_dsac_backward_rgb_masked_sampled_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                              int B, int Ho, int Wo, const uint8_t *mask_dev, int sampler,
+                                              float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                                              const float *gt_poses_dev, double *out_loss_dev, int32_t *status_dev,
+                                              int n_hyp, float thr, float focal, float ppx, float ppy,
+                                              float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
+                                              const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
+                                              uint32_t max_tries, void *stream, double *rec_dev)
+{
+    if (sampler == XL_DSAC_SAMPLER_REJECT)
+        return backward_rgb_launch<kMaskReject>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, grad_dev, gsb, gsc, gsy, gsx,
+                                                gt_poses_dev, out_loss_dev, status_dev, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans,
+                                                soft_clamp, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride,
+                                                max_tries, stream, rec_dev);
+    if (sampler == XL_DSAC_SAMPLER_COMPACT)
+        return backward_rgb_launch<kMaskCompact>(coords_dev, sb, sc, sy, sx, B, Ho, Wo, mask_dev, grad_dev, gsb, gsc, gsy, gsx,
+                                                 gt_poses_dev, out_loss_dev, status_dev, n_hyp, thr, focal, ppx, ppy, w_rot, w_trans,
+                                                 soft_clamp, alpha, max_reproj, sub, focals_dev, seed, image0, image_stride,
+                                                 max_tries, stream, rec_dev);
+    return XL_ERR_ARG;                                           // unknown sampler: before any device work
 }
 
 int xl_dsac_forward_rgbd(void) { return XL_ERR_UNSUPPORTED; }

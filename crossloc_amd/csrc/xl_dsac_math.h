@@ -2,7 +2,8 @@
  * xl_dsac_math.h — the lane-local arithmetic of the DSAC* pose solver, written once.
  *
  * Everything one GPU lane (or one iteration of a CPU loop) computes on its own is here: the deterministic
- * transcendentals, the counter-based RNG, the camera record and the pixel centre of a cell (cam_make, cell_px), projection,
+ * transcendentals, the counter-based RNG, the rank plane and selection of the masked solver's compact sampler
+ * (mask_rank_plane, mask_select), the camera record and the pixel centre of a cell (cam_make, cell_px), projection,
  * cell error and the soft-inlier sigmoid, the Ferrari quartic, P3P with its Newton polish and 4th-point selection, the
  * pieces of the Levenberg-Marquardt refinement (the per-cell normal equations, plain and weighted, the 6x6 Cholesky step,
  * the step-size stop and its constants, the not-NaN test of the result), the pose forms (12 doubles, float 4x4
@@ -180,6 +181,46 @@ XL_MATH_FN int draw(uint64_t state, int j, int n)
     uint64_t r = mix64(state + 0x9e3779b97f4a7c15ULL * (uint64_t)(j + 1));
     uint32_t hi = (uint32_t)(r >> 32);
     return (int)(((uint64_t)hi * (uint64_t)(uint32_t)n) >> 32);
+}
+
+/* ------------------------------------------------------------------------------ compact sampler of the masked solver */
+
+/* The validity mask as a bit plane (bit i & 31 of word i >> 5 <-> cell i, bits past the last cell zero) and its rank plane:
+ * rank[w] = usable cells in words 0 .. w-1, for w = 0 .. nWords, so rank[nWords] = nUsable.  The kernel builds the plane with a
+ * wave-level scan (xl_dsac.hip: build_rank_plane); this serial statement is the restatements'. */
+XL_MATH_FN void mask_rank_plane(const uint32_t *words, int nWords, uint32_t *rank)
+{
+    uint32_t acc = 0;
+    for (int w = 0; w < nWords; ++w) { rank[w] = acc; acc += (uint32_t)__builtin_popcount(words[w]); }
+    rank[nWords] = acc;
+}
+
+/* cell index of the usable cell of rank k in row-major order, 0 <= k < rank[nWords]: binary search for the word w with
+ * rank[w] <= k < rank[w + 1] (at most 9 steps at 16384 cells), then the set bit of rank k - rank[w] within it by popcount
+ * halving.  Integers only. */
+XL_MATH_FN int mask_select(const uint32_t *words, const uint32_t *rank, int nWords, int k)
+{
+    int lo = 0, hi = nWords;                               /* rank[lo] <= k < rank[hi] */
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (rank[mid] <= (uint32_t)k) lo = mid; else hi = mid;
+    }
+    uint32_t v = words[lo];
+    int r = k - (int)rank[lo], pos = 0;
+    XL_MATH_UNROLL
+    for (int width = 16; width >= 1; width >>= 1) {
+        const int c = __builtin_popcount(v & ((1u << width) - 1u));
+        if (r >= c) { r -= c; v >>= width; pos += width; }
+    }
+    return (lo << 5) + pos;
+}
+
+/* the four cells of a compact try: draw j is a rank in [0, nUsable), independent and with replacement */
+XL_MATH_FN void compact_try_cells(uint64_t st, const uint32_t *words, const uint32_t *rank, int nWords, int *cells)
+{
+    const int nUsable = (int)rank[nWords];
+    XL_MATH_UNROLL
+    for (int j = 0; j < 4; ++j) cells[j] = mask_select(words, rank, nWords, draw(st, j, nUsable));
 }
 
 /* ------------------------------------------------------------------------------ projection + cell error */

@@ -18,7 +18,8 @@ is the exact call utils/evaluation.py:162-172 makes.  Differences, all additive:
     stored there cannot influence the result.  It returns a status per image (1: fewer than four usable cells, identity pose).
     `backward_rgb_masked_batch` is backward_rgb_batch over the same mask: masked-out cells are no evidence and get no gradient.
     `pose_quality_masked_batch` and `refine_pose_masked_batch` carry the mask through the two passes behind the solver: a
-    masked-out cell is never read, is never an inlier and is counted in `n_masked` only.  The mask does not reach the RGB-D solver
+    masked-out cell is never read, is never an inlier and is counted in `n_masked` only.  `sampler="compact"` (MASK_SAMPLERS) makes
+    the masked solver and its backward pass draw from the usable cells only.  The mask does not reach the RGB-D solver
     and its passes, forward_rgb or backward_rgb.
   * `backward_rgb` (dsacstar.cpp:200-483, exported by the reference but never called by CrossLoc) and its batched
     form `backward_rgb_batch` run on the GPU as well.
@@ -42,6 +43,7 @@ from . import _lib
 RANSAC_SEED = 1305                      # thread_rand.h:101 default seed of the reference
 MAX_HYPOTHESES_TRIES = 1000000          # dsacstar.cpp:48
 MAX_REF_STEPS = 100                     # dsacstar.cpp:47 (compiled into the kernel)
+MASK_SAMPLERS = ("reject", "compact")    # samplers of the masked RGB solver: XL_DSAC_SAMPLER_* of include/crossloc_dsac.h, by position
 _image_index = 0
 
 
@@ -75,6 +77,13 @@ def _check_coords(t, batched):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _sampler_code(fn, sampler):
+    """The sampler of a masked call as the C interface's code; an unknown name raises before any device work."""
+    if sampler not in MASK_SAMPLERS:
+        raise RuntimeError("%s: unknown sampler %r (one of %s)" % (fn, sampler, ", ".join(MASK_SAMPLERS)))
+    return MASK_SAMPLERS.index(sampler)
 
 
 def _check_mask(fn, sceneCoordinates, mask, out, out_name):
@@ -136,18 +145,24 @@ def forward_rgb_batch(sceneCoordinates, outPoses, ransacHypotheses, inlierThresh
 
 def forward_rgb_masked_batch(sceneCoordinates, mask, outPoses, ransacHypotheses, inlierThreshold, focalLength, ppointX,
                              ppointY, inlierAlpha, maxReproj, subSampling, image0=0, image_stride=1, focals=None,
-                             seed=None, max_tries=None, debug=False):
+                             seed=None, max_tries=None, debug=False, sampler="reject"):
     """forward_rgb_batch over the cells `mask` admits.  mask: uint8 or bool [B,Ho,Wo] CUDA contiguous on the device of
-    sceneCoordinates, nonzero = usable; the other arguments as in forward_rgb_batch.  A try that drew a masked-out cell is rejected
-    before P3P (the draws themselves are the unmasked solver's, so the expected number of tries grows as (usable fraction)^-4),
-    the score sums the usable cells only, and an inlier of the refinement is a usable cell below the threshold; the values stored
-    at masked-out cells (NaN and Inf included) influence no output bit, and with an all-ones mask every output is
-    forward_rgb_batch's bit for bit.  An image with fewer than four usable cells gets the 4x4 identity and status 1 (with
+    sceneCoordinates, nonzero = usable; the other arguments as in forward_rgb_batch.  `sampler` (one of MASK_SAMPLERS) says how the
+    four cells of a try are drawn.  "reject", the default: a try that drew a masked-out cell is rejected before P3P (the draws
+    themselves are the unmasked solver's, so the expected number of tries grows as (usable fraction)^-4), and with an all-ones
+    mask every output is forward_rgb_batch's bit for bit.  "compact": every draw is a rank among the usable cells of the image in
+    row-major order, so no try is rejected by the mask and the number of tries stays at the unmasked solver's level whatever the
+    usable fraction; the hypotheses come from the same distribution as under "reject" (uniform over usable quadruples) but are
+    not the same ones, and an all-ones mask does not reproduce forward_rgb_batch.  Under both, the score sums the usable cells
+    only, an inlier of the refinement is a usable cell below the threshold, and the values stored at masked-out cells (NaN and
+    Inf included) influence no output bit.  No draw is weighted.  An image with fewer than four usable cells gets the 4x4 identity and status 1 (with
     debug: tries 0, scores 0, cells -1, winner -1).  Returns status, int32 [B] on the device (asynchronous on the current stream);
     with debug=True the debug dict of forward_rgb_batch with `status` in it.  Shape, dtype and device mismatches raise
-    RuntimeError before any device work.  The backward pass over the same mask is backward_rgb_masked_batch, the passes behind
-    the solver are pose_quality_masked_batch and refine_pose_masked_batch; the RGB-D solver and its backward pass and the
-    single-image forward_rgb take no mask."""
+    RuntimeError before any device work, an unknown sampler name too.  The backward pass over the same mask is
+    backward_rgb_masked_batch (give it the same sampler), the passes behind the solver are pose_quality_masked_batch and
+    refine_pose_masked_batch (they take a pose, not a sampler); the RGB-D solver and its backward pass, the single-image
+    forward_rgb and the compiled binding take neither mask nor sampler."""
+    sampler = _sampler_code("forward_rgb_masked_batch", sampler)
     _check_coords(sceneCoordinates, True)
     mask = _check_mask("forward_rgb_masked_batch", sceneCoordinates, mask, outPoses, "outPoses")
     B, _, Ho, Wo = sceneCoordinates.shape
@@ -172,8 +187,8 @@ def forward_rgb_masked_batch(sceneCoordinates, mask, outPoses, ransacHypotheses,
     sb, sc, sy, sx = sceneCoordinates.stride()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        rc = _lib.lib().xl_dsac_forward_rgb_masked_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), _ptr(outPoses), _ptr(status),
+        rc = _lib.lib().xl_dsac_forward_rgb_masked_sampled_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), sampler, _ptr(outPoses), _ptr(status),
             int(ransacHypotheses), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY),
             float(inlierAlpha), float(maxReproj), int(subSampling), _ptr(focals),
             int(RANSAC_SEED if seed is None else seed), int(image0), int(image_stride),
@@ -415,15 +430,17 @@ def backward_rgb_batch(sceneCoordinates, outSceneCoordinatesGrad, gtPoses, ransa
 
 def backward_rgb_masked_batch(sceneCoordinates, mask, outSceneCoordinatesGrad, gtPoses, ransacHypotheses, inlierThreshold,
                               focalLength, ppointX, ppointY, wLossRot, wLossTrans, softClamp, inlierAlpha, maxReproj,
-                              subSampling, randomSeed, image0=0, image_stride=1, focals=None, max_tries=None, debug=False):
-    """backward_rgb_batch over the cells `mask` admits (mask: as in forward_rgb_masked_batch, the other arguments as in
-    backward_rgb_batch): the hypotheses, scores and soft-max distribution are the masked forward solver's, every hypothesis is
+                              subSampling, randomSeed, image0=0, image_stride=1, focals=None, max_tries=None, debug=False,
+                              sampler="reject"):
+    """backward_rgb_batch over the cells `mask` admits (mask and sampler: as in forward_rgb_masked_batch, the other arguments as in
+    backward_rgb_batch): the hypotheses, scores and soft-max distribution are the masked forward solver's under `sampler`, every hypothesis is
     refined over usable cells only, the score path sums usable cells only, and the gradient at a masked-out cell keeps the
     caller's incoming value bit for bit.  The values stored at masked-out cells (NaN and Inf included) influence no bit of loss,
-    record or gradient, and with an all-ones mask all three are backward_rgb_batch's.  An image with fewer than four usable cells
+    record or gradient, and with an all-ones mask and the "reject" sampler all three are backward_rgb_batch's.  An image with fewer than four usable cells
     gets loss 0.0, status 1, zero records and an untouched gradient.  Returns (losses float64 [B], status int32 [B]) on the device
     (asynchronous on the current stream); with debug=True (losses, rec, status).  Shape, dtype and device mismatches raise
-    RuntimeError before any device work."""
+    RuntimeError before any device work, an unknown sampler name too."""
+    sampler = _sampler_code("backward_rgb_masked_batch", sampler)
     _check_coords(sceneCoordinates, True)
     g = outSceneCoordinatesGrad
     mask = _check_mask("backward_rgb_masked_batch", sceneCoordinates, mask, g, "outSceneCoordinatesGrad")
@@ -445,8 +462,8 @@ def backward_rgb_masked_batch(sceneCoordinates, mask, outSceneCoordinatesGrad, g
     gb, gc, gy, gx = g.stride()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
-        rc = _lib.lib().xl_dsac_backward_rgb_masked_batch(
-            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), _ptr(g), gb, gc, gy, gx, _ptr(gt), _ptr(loss),
+        rc = _lib.lib().xl_dsac_backward_rgb_masked_sampled_batch(
+            _ptr(sceneCoordinates), sb, sc, sy, sx, B, Ho, Wo, _ptr(mask), sampler, _ptr(g), gb, gc, gy, gx, _ptr(gt), _ptr(loss),
             _ptr(status), int(ransacHypotheses), float(inlierThreshold), float(focalLength), float(ppointX), float(ppointY),
             float(wLossRot), float(wLossTrans), float(softClamp), float(inlierAlpha), float(maxReproj),
             int(subSampling), _ptr(focals), int(randomSeed), int(image0), int(image_stride),

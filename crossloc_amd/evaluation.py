@@ -282,12 +282,17 @@ def _is_masked_quality(quality):
     return isinstance(quality, str) and quality == "masked"
 
 
-def _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine):
-    """The mask reaches the RGB solver and, through the masked modes, the two passes behind it.  -> whether the masked solver
-    runs"""
+def _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine, mask_sampler="reject"):
+    """The mask reaches the RGB solver and, through the masked modes, the two passes behind it; `mask_sampler` is the masked
+    solver's (dsacstar.MASK_SAMPLERS), so any but the default needs a mask.  -> whether the masked solver runs"""
+    import dsacstar
+    if mask_sampler not in dsacstar.MASK_SAMPLERS:
+        raise RuntimeError("unknown mask_sampler %r (one of %s)" % (mask_sampler, ", ".join(dsacstar.MASK_SAMPLERS)))
     asked = [("quality", quality)] if _is_masked_quality(quality) else []
     if isinstance(refine, str) and refine in MASKED_REFINE_MODES:
         asked.append(("refine", refine))
+    if mask_sampler != "reject":
+        asked.append(("mask_sampler", mask_sampler))
     if mask is None and mask_max_sigma is None:
         for name, mode in asked:
             raise RuntimeError("%s=%r runs behind the masked RGB solver: it needs mask= or mask_max_sigma=" % (name, mode))
@@ -395,7 +400,7 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
                    threshold=10.0, inlier_alpha=100.0, max_pixel_error=100.0, scene_coords=None, plant=None,
                    quality=False, depth=None, cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0,
                    refine=False, sigma=None, sigma_floor_px=1.0, depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01,
-                   mask=None, mask_max_sigma=None):
+                   mask=None, mask_max_sigma=None, mask_sampler="reject"):
     """One batch of the test_single_task.py:347-366 loop on the GPU: eval-mode CNN forward, sigma dropped
     (:354) unless `refine="sigma"` asks for it, HIP DSAC* on all images of the batch.  Returns (poses [B,4,4] cuda,
     predictions [B,4,Ho,Wo]).
@@ -431,11 +436,14 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
     `quality="masked"` (dsacstar.pose_quality_masked_batch, behind the refinement: it rates the refined pose); the return is
     then (poses, pred[, quality rows][, refine rows], status) with the refined poses first.  These modes need a mask
     (RuntimeError without); a mask with `depth` / `cam_coords`, with `quality=True` / `"rgbd"` or with an unmasked `refine` mode
-    raises RuntimeError (those passes read every cell).  Without a mask nothing changes."""
+    raises RuntimeError (those passes read every cell).  `mask_sampler` (dsacstar.MASK_SAMPLERS; default "reject"): how the masked
+    solver draws the cells of a try; "compact" draws from the usable cells only, which keeps the number of tries at the unmasked
+    solver's level under a mask that keeps a minority of cells.  The masked passes work behind either sampler (they take a pose).
+    A sampler other than "reject" without a mask raises RuntimeError.  Without a mask nothing changes."""
     import dsacstar
     if depth is not None and cam_coords is not None:
         raise RuntimeError("localize_batch takes at most one of depth and cam_coords")
-    masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine)
+    masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine, mask_sampler)
     _check_quality_mode(quality, depth, cam_coords)
     refine = _check_refine_mode(refine, depth, cam_coords) and refine
     with torch.no_grad():
@@ -456,7 +464,7 @@ def localize_batch(network, images, n_hyp, focal, image_h, image_w, image0=0, im
         status = dsacstar.forward_rgb_masked_batch(coords, m, poses, n_hyp, threshold,
                                                    f0, float(image_w / 2), float(image_h / 2), inlier_alpha, max_pixel_error,
                                                    network.OUTPUT_SUBSAMPLE, image0=image0, image_stride=image_stride,
-                                                   focals=focals)
+                                                   focals=focals, sampler=mask_sampler)
         poses, tail = _masked_passes(refine, quality, coords, m, _refine_sigma(refine, sigma, pred, nt), poses, threshold, f0,
                                      float(image_w / 2), float(image_h / 2), inlier_alpha, max_pixel_error,
                                      network.OUTPUT_SUBSAMPLE, sigma_floor_px, focals)
@@ -540,7 +548,7 @@ class PipelinedLocalizer:
 
     def submit(self, images, image0=0, image_stride=1, scene_coords=None, plant=None, quality=False, depth=None,
                cam_coords=None, rgbd_threshold=10.0, max_dist_error=100.0, refine=False, sigma=None, sigma_floor_px=1.0,
-               depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01, mask=None, mask_max_sigma=None):
+               depth_sigma=None, depth_rel=0.0, sigma_floor_m=0.01, mask=None, mask_max_sigma=None, mask_sampler="reject"):
         """Enqueue one batch; returns (poses [B,4,4], predictions).  Both are valid after finish() (or after
         synchronising the side stream).  `quality=True`: the pose-quality pass runs directly behind the solver on the
         side stream and its rows [B,64] float64 are returned as a third value.  `depth` / `cam_coords` (at most one): the
@@ -553,11 +561,11 @@ class PipelinedLocalizer:
         `mask` / `mask_max_sigma` as in localize_batch: the masked RGB solver runs on the side stream and its status [B] int32 is
         appended as the last value; `refine="masked_inliers"` / `"masked_sigma"` and `quality="masked"` run the passes over the
         same mask behind it on the side stream, returned as (poses, pred[, quality rows][, refine rows], status).  Not with
-        `depth` / `cam_coords` or the unmasked `quality` / `refine` modes."""
+        `depth` / `cam_coords` or the unmasked `quality` / `refine` modes.  `mask_sampler` as in localize_batch (only with a mask)."""
         import dsacstar
         if depth is not None and cam_coords is not None:
             raise RuntimeError("submit takes at most one of depth and cam_coords")
-        masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine)
+        masked = _check_mask_mode(mask, mask_max_sigma, quality, depth, cam_coords, refine, mask_sampler)
         _check_quality_mode(quality, depth, cam_coords)
         refine = _check_refine_mode(refine, depth, cam_coords) and refine
         pred, events = self.forward_cnn(images, plant)
@@ -580,7 +588,8 @@ class PipelinedLocalizer:
                 solved = poses
                 status = dsacstar.forward_rgb_masked_batch(coords, m, solved, self.n_hyp, self.thr, f0, float(self.w / 2),
                                                            float(self.h / 2), self.alpha, self.maxerr, self.net.OUTPUT_SUBSAMPLE,
-                                                           image0=image0, image_stride=image_stride, focals=focals)
+                                                           image0=image0, image_stride=image_stride, focals=focals,
+                                                           sampler=mask_sampler)
                 poses, masked_tail = _masked_passes(refine, quality, coords, m,
                                                     _refine_sigma(refine, sigma, pred, self.net.num_task_channel), solved, self.thr,
                                                     f0, float(self.w / 2), float(self.h / 2), self.alpha, self.maxerr,

@@ -392,7 +392,8 @@ def expected_pose_loss_and_output_gradient(prediction, gt_poses, focals, image_h
                                            inlier_alpha, max_pixel_error, weight_rot, weight_trans, soft_clamp, seed,
                                            image0=0, image_stride=1, image_keys=None, clip_norm=0.0, weight=1.0,
                                            grad=None, beta=0.0, depth=None, cam_coords=None, rgbd_threshold=10.0,
-                                           max_dist_error=100.0, max_tries=E2E_MAX_TRIES, subsample=8, mask=None):
+                                           max_dist_error=100.0, max_tries=E2E_MAX_TRIES, subsample=8, mask=None,
+                                           mask_sampler="reject"):
     """The DSAC* expected pose loss of a batch and its gradient w.r.t. the network output, in the form the end-to-end step
     uses (the sibling of task_loss_and_output_gradient): `prediction` [B, C >= 3, Ho, Wo] (float32 CUDA) is read in place -
     its [:, :3] view goes to the solver as it is - dsacstar.backward_rgb_batch accumulates into a zeroed [B,3,Ho,Wo] buffer
@@ -412,8 +413,14 @@ def expected_pose_loss_and_output_gradient(prediction, gt_poses, focals, image_h
     masked-out cells are no evidence for the solver and their `grad[:, :3]` is exact zeros.  A frame with fewer than four usable
     cells is rejected like a frame whose loss is not finite: zeros contributed, not counted in `accepted`, not in the mean
     (its loss is turned into NaN on the device before the finishing op; nothing is read back).  The RGB-D path drops depth holes
-    by itself and takes no mask: with `depth` or `cam_coords` a mask raises RuntimeError."""
+    by itself and takes no mask: with `depth` or `cam_coords` a mask raises RuntimeError.  mask_sampler (dsacstar.MASK_SAMPLERS):
+    the masked solver's sampler; "compact" draws from the usable cells only, so a mask that keeps a minority of the cells does
+    not run the hypotheses out of their max_tries.  A sampler other than "reject" without a mask raises RuntimeError."""
     from . import dsacstar
+    if mask_sampler not in dsacstar.MASK_SAMPLERS:
+        raise RuntimeError("unknown mask_sampler %r (one of %s)" % (mask_sampler, ", ".join(dsacstar.MASK_SAMPLERS)))
+    if mask is None and mask_sampler != "reject":
+        raise RuntimeError("mask_sampler=%r is the masked solver's: it needs mask=" % (mask_sampler,))
     if mask is not None and (depth is not None or cam_coords is not None):
         raise RuntimeError("the RGB-D backward pass takes no mask (it drops depth holes itself): pass mask or depth / cam_coords")
     p = prediction.detach()
@@ -433,7 +440,8 @@ def expected_pose_loss_and_output_gradient(prediction, gt_poses, focals, image_h
     if mask is not None:
         losses, status = dsacstar.backward_rgb_masked_batch(
             coords, mask, g, gt_poses, hypotheses, threshold, 0.0, ppx, ppy, weight_rot, weight_trans, soft_clamp, inlier_alpha,
-            max_pixel_error, subsample, seed, image0=image0, image_stride=image_stride, focals=focals, max_tries=max_tries)
+            max_pixel_error, subsample, seed, image0=image0, image_stride=image_stride, focals=focals, max_tries=max_tries,
+            sampler=mask_sampler)
         losses = torch.where(status == 1, float("nan"), losses)                  # a dead frame: rejected below
     elif depth is None and cam_coords is None:
         losses = dsacstar.backward_rgb_batch(coords, g, gt_poses, hypotheses, threshold, 0.0, ppx, ppy, weight_rot,

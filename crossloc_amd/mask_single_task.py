@@ -19,6 +19,8 @@ Every option of test_single_task is accepted and means the same.  Added:
                             mask (needs --decoy); `sigma`: cells whose predicted standard deviation is at most --mask_max_sigma
                             (needs a network with an uncertainty channel)
   --mask_max_sigma S        metres (default 1.0)
+  --mask_sampler {reject,compact}  the masked solver's sampler (localize_batch's mask_sampler; needs a --mask other than `none`).
+                            `compact` draws the cells of a try from the usable cells only
   --refine {none,inliers,sigma}  default `none`: the report is unchanged character for character.  Otherwise the refinement runs
                             behind the solver of every batch and the report is about the refined poses: with a --mask other than
                             `none` over the solver's mask (localize_batch's refine="masked_inliers" / "masked_sigma"), with
@@ -33,7 +35,7 @@ import sys
 import numpy as np
 import torch
 
-from . import evaluation, synth, test_single_task
+from . import dsacstar, evaluation, synth, test_single_task
 
 
 class _SynthWithDecoy:
@@ -57,8 +59,8 @@ class _SynthWithDecoy:
 class _EvaluationWithMask:
     """crossloc_amd.evaluation as test_single_task.main() sees it during a masked run (see the module docstring)."""
 
-    def __init__(self, mode, max_sigma, scenes, refine='none'):
-        self.mode, self.max_sigma, self.scenes, self.refine = mode, max_sigma, scenes, refine
+    def __init__(self, mode, max_sigma, scenes, refine='none', sampler='reject'):
+        self.mode, self.max_sigma, self.scenes, self.refine, self.sampler = mode, max_sigma, scenes, refine, sampler
 
     def __getattr__(self, name):
         return getattr(evaluation, name)
@@ -69,6 +71,7 @@ class _EvaluationWithMask:
             kwargs["refine"] = self.refine if self.mode == 'none' else "masked_" + self.refine
         if self.mode == 'none':
             return evaluation.localize_batch(network, images, *args, **kwargs)[:2]
+        kwargs["mask_sampler"] = self.sampler
         if self.mode == 'sigma':
             out = evaluation.localize_batch(network, images, *args, mask_max_sigma=self.max_sigma, **kwargs)
         else:
@@ -85,11 +88,14 @@ def main():
     own.add_argument('--mask', choices=['none', 'truth', 'sigma'], default='none')
     own.add_argument('--mask_max_sigma', type=float, default=1.0)
     own.add_argument('--refine', choices=['none', 'inliers', 'sigma'], default='none')
+    own.add_argument('--mask_sampler', choices=list(dsacstar.MASK_SAMPLERS), default='reject')
     opt, rest = own.parse_known_args()                  # test_single_task's parser sees everything else
+    if opt.mask_sampler != 'reject' and opt.mask == 'none':
+        own.error("--mask_sampler %s is the masked solver's: it needs a --mask other than none" % opt.mask_sampler)
     scenes = _SynthWithDecoy(opt.decoy)
     saved = sys.argv, test_single_task.evaluation, test_single_task.synth
     sys.argv = [sys.argv[0]] + rest
-    test_single_task.evaluation = _EvaluationWithMask(opt.mask, opt.mask_max_sigma, scenes, opt.refine)
+    test_single_task.evaluation = _EvaluationWithMask(opt.mask, opt.mask_max_sigma, scenes, opt.refine, opt.mask_sampler)
     test_single_task.synth = scenes
     try:
         test_single_task.main()

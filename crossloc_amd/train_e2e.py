@@ -22,12 +22,14 @@ data.batch_canvas) - every frame draws its own scale and, with --aug_rotation DE
 warped onto a canvas of its own size; the solver and the --init_weight coord term read one focal length per frame.  The
 label grid stays 60 x 90, so --mode rgbd keeps the scale range 2/3 - 3/2 with it.  --mask labels (--mode rgb): the cells whose
 coord label is the scene's nodata value - sky, water, the empty border --aug_canvas and --aug_rotation leave around a warped
-frame - are masked out of the solver's backward pass, as --mode rgbd drops depth holes by itself.
+frame - are masked out of the solver's backward pass, as --mode rgbd drops depth holes by itself.  --mask_sampler compact (with
+--mask labels): the solver draws the cells of a try from the usable cells only; under the default, reject, the expected tries
+of a hypothesis grow as (usable fraction)^-4 and a frame that keeps a tenth of its cells exhausts every hypothesis.
 
 See crossloc_amd/training.py (make_e2e_step, Trainer) and loss.expected_pose_loss_and_output_gradient.
 """
 from . import training
-from .dsacstar import RANSAC_SEED
+from .dsacstar import MASK_SAMPLERS, RANSAC_SEED
 
 
 def _parser():
@@ -52,6 +54,9 @@ def _parser():
     p.add_argument('--mask', type=str, default='none', choices=('none', 'labels'),
                    help='labels: cells whose coord label is nodata (sky, water, the empty border of a warped frame) are no '
                         'evidence for the solver and get no pose gradient (--mode rgb)')
+    p.add_argument('--mask_sampler', type=str, default='reject', choices=MASK_SAMPLERS,
+                   help='how the masked solver draws the cells of a try (with --mask labels); compact: from the usable cells '
+                        'only, for masks that keep a minority of the cells')
     p.add_argument('--seed', type=int, default=RANSAC_SEED, help="the sampler's seed; step k draws with seed + k")
     return p
 
@@ -69,6 +74,8 @@ def _config_parser(argv=None):
         p.error("--aug_rotation is the half width of the angle range: it cannot be negative")
     if opt.mask == 'labels' and opt.mode == 'rgbd':
         p.error("--mask labels is for --mode rgb: the RGB-D solver drops depth holes itself and takes no mask")
+    if opt.mask_sampler != 'reject' and opt.mask != 'labels':
+        p.error("--mask_sampler %s is the masked solver's: it needs --mask labels" % opt.mask_sampler)
     if opt.real_only:
         assert opt.sim_data_chunk == 0
     return opt
@@ -105,6 +112,8 @@ def get_output_path(opt):
         b += '-canvas'
     if opt.mask != 'none':
         b += '-mask' + opt.mask
+    if getattr(opt, 'mask_sampler', 'reject') != 'reject':
+        b += '-' + opt.mask_sampler
     if opt.tiny:
         b += '-tiny'
     if opt.debug:

@@ -207,9 +207,12 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
     opt.aug_canvas the frames carry their own scale: the coord term then reads one focal length per frame.  With
     opt.mask == 'labels' (--mode rgb) every step builds evaluation.cell_mask from its coord labels: the cells whose label is the
     scene's nodata value - sky, water, the empty border of a warped frame - are no evidence for the solver and get no pose
-    gradient (dsacstar.backward_rgb_masked_batch)"""
+    gradient (dsacstar.backward_rgb_masked_batch), drawn by the sampler opt.mask_sampler names (default 'reject')"""
     rgbd = opt.mode == 'rgbd'
     label_mask = getattr(opt, 'mask', 'none') == 'labels'
+    mask_sampler = getattr(opt, 'mask_sampler', 'reject')
+    if mask_sampler != 'reject' and not label_mask:
+        raise RuntimeError("--mask_sampler %s is the masked solver's: it needs --mask labels" % mask_sampler)
     if label_mask and rgbd:
         raise RuntimeError("--mask labels is for --mode rgb: the RGB-D solver drops depth holes itself and takes no mask")
     canvas = bool(getattr(opt, 'aug_canvas', False))
@@ -243,7 +246,7 @@ def make_e2e_step(network, optimizer, opt, world_size=1, group=None, host_reduce
             predictions, gt_poses, focals, image_h, image_w, opt.hypotheses, opt.threshold, opt.inlieralpha,
             opt.maxpixelerror, opt.weightrot, opt.weighttrans, opt.softclamp, seed, image0=image0,
             clip_norm=opt.clip_norm, weight=1.0, grad=grad, beta=beta, depth=depth, rgbd_threshold=opt.threshold,
-            max_dist_error=opt.maxpixelerror, subsample=sub, mask=mask)
+            max_dist_error=opt.maxpixelerror, subsample=sub, mask=mask, mask_sampler=mask_sampler)
         predictions.backward(grad)
         if world_size > 1:
             allreduce_flat_gradients(network, world_size, group, host_reduce)

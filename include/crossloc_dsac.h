@@ -79,7 +79,8 @@ int xl_dsac_forward_rgb_batch(const float *coords_dev, int64_t sb, int64_t sc, i
  *         the workgroup counts the usable cells.  A grid whose planes fit in 160 KB only without it returns XL_ERR_GRID.
  * sample  the four cells of a try are drawn exactly as in the unmasked solver (same generator state, same draws).  A try
  *         that drew a masked-out cell is rejected before P3P: its pose is the identity, like a failed P3P, and it counts as
- *         a try.  The first accepted try still wins; the expected number of tries grows as (usable fraction)^-4.  After
+ *         a try.  The first accepted try still wins; the expected number of tries grows as (usable fraction)^-4
+ *         (xl_dsac_forward_rgb_masked_sampled_batch offers a sampler that draws from the usable cells only).  After
  *         max_tries the hypothesis is the last try's result - the identity pose if the mask rejected that try.
  * score   the sum runs over the usable cells; the term of a masked-out cell is selected away, never multiplied by zero, so
  *         whatever is stored there (NaN, Inf) reaches neither the sum nor the NaN flag.  The factor stays alpha / Wo / Ho.
@@ -103,6 +104,39 @@ int xl_dsac_forward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64_
                                      uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
                                      void *stream,
                                      int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
+
+/*
+ * The masked RGB solver with a choice of sampler: xl_dsac_forward_rgb_masked_batch plus `sampler` after the mask.
+ *
+ *   XL_DSAC_SAMPLER_REJECT    the sampler described above; xl_dsac_forward_rgb_masked_batch is this call, bit for bit.
+ *   XL_DSAC_SAMPLER_COMPACT   draws the four cells of a try from the usable cells only.  stage: behind the bit plane the kernel
+ *                             keeps a rank plane of ceil(Ho*Wo / 32) + 1 words (680 B at 60x90): rank[w] = usable cells in
+ *                             mask words 0 .. w-1 (xl_dsac_math.h: mask_rank_plane).  sample: with st the try's generator
+ *                             state as before, cell j is the usable cell of rank draw(st, j, nUsable) in row-major order
+ *                             (mask_select: a binary search over the rank plane, then a select within the word; integers
+ *                             only); the four draws are independent and with replacement.  No try is rejected by the mask,
+ *                             so the number of tries stays at the unmasked solver's level whatever the usable fraction, and
+ *                             a hypothesis whose tries ran out carries four usable cells and its last P3P result.
+ *                             Everything behind the cells (P3P, the four-cell check, tries, score, select, refine, the dead
+ *                             image) is the masked solver's.  Conditional on acceptance the reject sampler is uniform over
+ *                             usable quadruples, so both samplers draw hypotheses from the same distribution; they do not
+ *                             draw the same ones, and Identity A does not hold for this sampler (the unmasked solver draws
+ *                             x and y separately).  Identity B holds.  No weights: every usable cell is equally likely.
+ *
+ * XL_ERR_ARG for any other sampler value and for everything xl_dsac_forward_rgb_masked_batch refuses, XL_ERR_GRID for a grid
+ * whose planes fit in 160 KB only without the planes of the chosen sampler; all before any HIP call.  The passes behind the
+ * solver take a pose, not a sampler.  Not covered: the RGB-D solver, the single-image host entry point and any weighted draw.
+ */
+#define XL_DSAC_SAMPLER_REJECT 0
+#define XL_DSAC_SAMPLER_COMPACT 1
+int xl_dsac_forward_rgb_masked_sampled_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                             int B, int Ho, int Wo, const uint8_t *mask_dev, int sampler,
+                                             float *out_poses_dev, int32_t *status_dev,
+                                             int n_hyp, float thr, float focal, float ppx, float ppy,
+                                             float alpha, float max_reproj, int sub, const float *focals_dev,
+                                             uint64_t seed, uint64_t image0, uint64_t image_stride, uint32_t max_tries,
+                                             void *stream,
+                                             int32_t *cells_dev, int32_t *tries_dev, double *scores_dev, double *dbg_dev);
 
 /*
  * Reference-shaped single-image call on HOST memory: same argument meaning as
@@ -180,6 +214,23 @@ int xl_dsac_backward_rgb_masked_batch(const float *coords_dev, int64_t sb, int64
                                       float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
                                       const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
                                       uint32_t max_tries, void *stream, double *rec_dev);
+
+/*
+ * xl_dsac_backward_rgb_masked_batch plus `sampler` after the mask (XL_DSAC_SAMPLER_*, as in
+ * xl_dsac_forward_rgb_masked_sampled_batch): the sample + score launch runs that sampler, so the pass differentiates the
+ * hypotheses the forward call with the same sampler, seed and image keys produced.  Under XL_DSAC_SAMPLER_COMPACT no hypothesis
+ * carries a masked-out cell, so K3 never skips the perturbed solves; a hypothesis whose tries ran out is treated as
+ * xl_dsac_backward_rgb_batch treats one.  Identities B and C hold for both samplers, Identity A for XL_DSAC_SAMPLER_REJECT only.
+ * XL_ERR_ARG for any other sampler value, before any HIP call.
+ */
+int xl_dsac_backward_rgb_masked_sampled_batch(const float *coords_dev, int64_t sb, int64_t sc, int64_t sy, int64_t sx,
+                                              int B, int Ho, int Wo, const uint8_t *mask_dev, int sampler,
+                                              float *grad_dev, int64_t gsb, int64_t gsc, int64_t gsy, int64_t gsx,
+                                              const float *gt_poses_dev, double *out_loss_dev, int32_t *status_dev,
+                                              int n_hyp, float thr, float focal, float ppx, float ppy,
+                                              float w_rot, float w_trans, float soft_clamp, float alpha, float max_reproj, int sub,
+                                              const float *focals_dev, uint64_t seed, uint64_t image0, uint64_t image_stride,
+                                              uint32_t max_tries, void *stream, double *rec_dev);
 
 /*
  * Per-frame pose quality (no reference counterpart): how far the pose of an image can be trusted.  A stand-alone pass over

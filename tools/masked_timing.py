@@ -28,7 +28,13 @@ the pass behind it, as a masked evaluation runs them: `unmasked` the all-ones so
 and `decoy_band` the solver and the masked pass over that mask (the refinement weighted by a sigma map of 0.5 m, make_scene's
 noise).  With `--unmasked_only` the first leg alone, which the parent commit can run too.
 
-    python tools/masked_timing.py [--backward | --quality | --refine] [--json out.json] [--unmasked_only]
+`--sampler compact` (forward and `--backward`) adds the compact sampler's legs: every masked leg once more under
+sampler="compact" (`<leg>_compact`), and a seeded random 10 % mask under both samplers (`tenth`, `tenth_compact`; max_tries at
+its default, so the reject leg does find its hypotheses - at some 10^4 tries each).  What to read off: the compact legs' mean
+tries stay at the unmasked leg's whatever the usable fraction; `all_ones_compact` against `all_ones` is the price of the rank
+plane and the selection.
+
+    python tools/masked_timing.py [--backward | --quality | --refine] [--sampler compact] [--json out.json] [--unmasked_only]
 """
 import argparse
 import json
@@ -106,15 +112,25 @@ def backward_rows(opt, dev):
         def decoy_band():
             return dsacstar.backward_rgb_masked_batch(dco, band, g, dgt, opt.hypotheses, *BWD_ARGS)
 
+        def sampled(coords, mask, poses, sampler):
+            return lambda: dsacstar.backward_rgb_masked_batch(coords, mask, g, poses, opt.hypotheses, *BWD_ARGS, sampler=sampler)
+
         ga, gb = torch.zeros_like(co), torch.zeros_like(co)
         la = dsacstar.backward_rgb_batch(co, ga, gt, opt.hypotheses, *BWD_ARGS)
         lb, status = dsacstar.backward_rgb_masked_batch(co, ones, gb, gt, opt.hypotheses, *BWD_ARGS)
         torch.cuda.synchronize()
         assert torch.equal(la, lb) and torch.equal(ga, gb) and not status.any(), "identity A: the all-ones mask must give the unmasked pass's bits"
         legs = (("unmasked", unmasked), ("all_ones", all_ones), ("half", half_mask), ("decoy_band", decoy_band))
+        if opt.sampler == "compact":
+            tenth = torch.from_numpy((np.random.default_rng(2022).random((B, 60, 90)) < 0.1).astype(np.uint8)).to(dev)
+            legs += (("all_ones_compact", sampled(co, ones, gt, "compact")), ("half_compact", sampled(co, half, gt, "compact")),
+                     ("tenth", sampled(co, tenth, gt, "reject")), ("tenth_compact", sampled(co, tenth, gt, "compact")),
+                     ("decoy_band_compact", sampled(dco, band, dgt, "compact")))
         med, spread = time_legs([fn for _, fn in legs], opt.warmup, opt.iters, opt.rounds)
         for (name, _), t, s in zip(legs, med, spread):
             row.update({name + "_ms": t, name + "_spread_ms": s})
+        if opt.sampler == "compact":
+            row["decoy_band_compact_median_expected_loss"] = float(dict(legs)["decoy_band_compact"]()[0].median())
         row["decoy_band_median_expected_loss"] = float(decoy_band()[0].median())
         row["decoy_unmasked_median_expected_loss"] = float(dsacstar.backward_rgb_batch(dco, g, dgt, opt.hypotheses, *BWD_ARGS).median())
         results.append(row)
@@ -187,10 +203,14 @@ def main():
     ap.add_argument("--backward", action="store_true", help="time the backward passes (24 frames and 1 frame)")
     ap.add_argument("--quality", action="store_true", help="time the masked solver plus the quality pass behind it")
     ap.add_argument("--refine", action="store_true", help="time the masked solver plus the refinement behind it")
+    ap.add_argument("--sampler", choices=("reject", "compact"), default="reject",
+                    help="compact: add the compact sampler's legs and the 10 %% mask (forward and --backward)")
     ap.add_argument("--json", type=str, default=None)
     opt = ap.parse_args()
     if opt.backward + opt.quality + opt.refine > 1:
         raise SystemExit("masked_timing: one of --backward, --quality and --refine")
+    if opt.sampler != "reject" and (opt.quality or opt.refine or opt.unmasked_only):
+        raise SystemExit("masked_timing: --sampler is for the forward and the --backward legs")
     if opt.rounds < 5:
         raise SystemExit("masked_timing: at least 5 rounds")
     if not torch.cuda.is_available():
@@ -241,10 +261,31 @@ def main():
         torch.cuda.synchronize()
         assert torch.equal(poses, mposes), "identity A: the all-ones mask must give the unmasked solver's poses"
         legs = (("unmasked", unmasked), ("all_ones", all_ones), ("half", half_mask), ("decoy_band", decoy_band))
+        if opt.sampler == "compact":
+            tenth = torch.from_numpy((np.random.default_rng(2022).random((B, 60, 90)) < 0.1).astype(np.uint8)).to(dev)
+
+            def sampled(coords, mask, sampler):
+                return lambda debug=False: dsacstar.forward_rgb_masked_batch(coords, mask, mposes, opt.hypotheses, *ARGS, debug=debug,
+                                                                             sampler=sampler)
+
+            legs += (("all_ones_compact", sampled(co, ones, "compact")), ("half_compact", sampled(co, half, "compact")),
+                     ("tenth", sampled(co, tenth, "reject")), ("tenth_compact", sampled(co, tenth, "compact")),
+                     ("decoy_band_compact", sampled(dco, band, "compact")))
         med, spread = time_legs([fn for _, fn in legs], opt.warmup, opt.iters, opt.rounds)
         for (name, fn), t, s in zip(legs, med, spread):
             row.update({name + "_ms": t, name + "_spread_ms": s, name + "_mean_tries": mean_tries(fn(True))})
         gt = np.stack([s["pose"] for s in decoys])
+        if opt.sampler == "compact":
+            dict(legs)["decoy_band_compact"]()
+            torch.cuda.synchronize()
+            row["decoy_band_compact_median_t_err_m"] = float(np.median([synth.pose_error(g, p)[0]
+                                                                        for g, p in zip(gt, mposes.cpu().numpy())]))
+            truth = np.stack([synth.make_scene(2021 + i)["pose"] for i in range(B)])
+            for name in ("tenth", "tenth_compact"):
+                dict(legs)[name]()
+                torch.cuda.synchronize()
+                row[name + "_median_t_err_m"] = float(np.median([synth.pose_error(g, p)[0]
+                                                                 for g, p in zip(truth, mposes.cpu().numpy())]))
         decoy_band()
         torch.cuda.synchronize()
         row["decoy_band_median_t_err_m"] = float(np.median([synth.pose_error(g, p)[0] for g, p in zip(gt, mposes.cpu().numpy())]))
